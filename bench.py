@@ -2,6 +2,26 @@
 """Headline benchmark: Mrays/s + frame time, sponza proxy 1920x1080x256spp (BASELINE.json).
 
     python bench.py [--gpus N --steps K --warmup W]            (N>1: launched by torch.distributed.run)
+    python bench.py --full [...]                                the headline plus every side measurement
+    python bench.py --dump-outputs DIR [...]                    what the last timed step computed, as .npy
+
+A plain run does only what the headline needs: scene set-up, the first frame (timed as
+cold_ms_per_step), W warmup frames (at least one: the first counts the rays), K timed frames, the
+result line.  Its roofline, traffic and issue figures cost no run of their own (the counters of
+the counting warmup frame, the timed frames' own kernel times and the committed PMC summaries).
+--full adds the measurements that take frames or CPU time of their own: natural_order, fast_mode
+and cpu_baseline (null in a plain line); --natural-steps, --fast-steps and --no-cpu-baseline trim
+them.
+
+--dump-outputs DIR: after the timed frames rank 0 writes what the last one left to its caller:
+DIR/frame.npy (the gathered 8-bit frame, (H, W, 3), as float32), DIR/sums.npy (rank 0's shard
+of the per-pixel radiance sums before the frame finish, (rows, W, 3) float32, rows in shard
+order) and DIR/sums_nonfinite.npy ((rows, W) float32).  Every written value is finite: a sum
+that is NaN or infinite (two pixels of the default frame are NaN; the finished frame, equal to the
+reference's, has 0 there) is written as 0 in sums.npy, and its pixel's entry in sums_nonfinite.npy says
+what it was: the sum over the channels c = 0, 1, 2 of 4^c x (1 NaN, 2 +inf, 3 -inf; 0 finite).
+The scene is seeded and the parity path deterministic, so two runs with the same
+arguments write the same bytes.
 
 A step = one full frame of the workload: every pixel of the 1920x1080 frame traced at
 256 spp, depth 6, split into interleaved 8-row blocks over the N ranks (one MI355X each),
@@ -15,7 +35,8 @@ value    = scene closest-hit queries (rays, counted in-kernel during warmup; the
            timed region; nothing measured in one frame is reused by the next.
 cold_ms_per_step = the very first frame after the scene upload (one-time workspace
            allocation and code-object load included), max over ranks.
-natural_order = the same frame in row-major pixel order (RT_FLAG_NATURAL_ORDER, no pre-pass).
+natural_order = --full: the same frame in row-major pixel order (RT_FLAG_NATURAL_ORDER, no pre-pass).
+fast_mode = --full: the same frame in fast mode (RT_FLAG_FAST), with its own ray count.
 roofline = rank 0's render kernel.  Default (kernel 0, lane-resident rt_mega_kernel): the
            frame is one launch (the runahead kernel: 4- and 8-way shards) or one launch pair
            (the plain kernel, then the runahead kernel resuming its parked tail: the hand-off),
@@ -33,8 +54,8 @@ roofline = rank 0's render kernel.  Default (kernel 0, lane-resident rt_mega_ker
            gathers), weighted by the shapes' shares of the algorithmic bytes; `traffic_range`
            spans the shapes' factors, `traffic_undoubled` is FETCH_SIZE as counted (+ WRITE_SIZE),
            `traffic_frac` = traffic / launch time / peak.
-cpu_baseline: the reference itself (oracle/_ref/ref_render, built from /root/reference's
-           sources) timing its Scene::render loop on the host cores this process may use
+cpu_baseline: --full: the reference itself (oracle/_ref/ref_render, built by oracle/Makefile from
+           the reference's sources) timing its Scene::render loop on the host cores this process may use
            (min(nproc, cgroup CPU quota) threads; `cores` says how many) over a bounded sample
            of the same frame (every 8th row, 16 spp); a counting build of the same sources
            counts its rays.  Falls back to the build's CPU restatement (oracle/) when _ref is
@@ -256,6 +277,15 @@ def pmc_traffic(fetch_csv, write_csv, kname, shares):
                                                                 "source": src}
 
 
+def finite_sums(sums):
+    """--dump-outputs: the (rows, W, 3) float32 sums with every NaN or infinite value written as
+    0, and the (rows, W) float32 map of what those values were: per pixel the sum over the
+    channels c of 4^c x (0 finite, 1 NaN, 2 +inf, 3 -inf)."""
+    code = np.isnan(sums) * 1 + (sums == np.inf) * 2 + (sums == -np.inf) * 3
+    klass = (code * np.array([1, 4, 16])).sum(axis=-1).astype(np.float32)
+    return np.where(code == 0, sums, np.float32(0)).astype(np.float32), klass
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -281,9 +311,17 @@ def main():
                     help="PMC summaries for roofline.traffic: a path prefix P (P_fetch*.csv / P_write*.csv from "
                          "tools/profile.sh of this same command), 'auto' (the committed profiles/ pair when the "
                          "workload is the default one) or 'none'")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: natural order, fast mode and the CPU baseline "
+                         "(a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (frame.npy, sums.npy, sums_nonfinite.npy; "
+                         "finite float32) to DIR")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    world =int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
@@ -361,7 +399,9 @@ def main():
         all_reduce(t, dist.ReduceOp.MAX)
         return float(t.item()), sts
 
-    # the very first frame of this scene on this device: nothing from an earlier render
+    # the very first frame of this scene on this device: nothing from an earlier render.  It is
+    # the warmup of the timed kernel (the counting frame below runs another instantiation), so
+    # timing it costs a plain run nothing
     cold_s, _ = timed(1)
     # warmup; the first one counts rays / tests (deterministic per frame, so valid for every step)
     counts = None
@@ -389,15 +429,22 @@ def main():
     # digest of the gathered 8-bit frame (outside the timed region): the parity path is
     # bit-exact whatever the sharding, so this must agree across --gpus 1/2/4/8 runs
     digest = hashlib.sha1(frame.cpu().numpy().tobytes()).hexdigest()[:16] if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back: the gathered frame and this rank's sums
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "frame.npy"), frame.cpu().numpy().astype(np.float32))
+        sums, klass = finite_sums(out.cpu().numpy().reshape(max_rows, W, 3))
+        np.save(os.path.join(args.dump_outputs, "sums.npy"), sums)
+        np.save(os.path.join(args.dump_outputs, "sums_nonfinite.npy"), klass)
 
     natural_s = None
-    if args.natural_steps > 0 and args.kernel == 0:
+    if args.full and args.natural_steps > 0 and args.kernel == 0:
         natural_s, _ = timed(args.natural_steps, natural=True)
 
     # fast mode (RT_FLAG_FAST): same frame, per-(pixel, sample) Philox streams, samples as
     # independent work units; its own ray count (other random paths), same timing protocol
     fast_line = None
-    if args.fast_steps > 0 and args.kernel == 0:
+    if args.full and args.fast_steps > 0 and args.kernel == 0:
         fc = step(count=True, fast=True)
         torch.cuda.synchronize()
         barrier()
@@ -510,6 +557,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "cold_ms_per_step": round(cold_s * 1e3, 3),
             "higher_is_better": True,
@@ -566,7 +614,7 @@ def main():
         line["slowest_rank"] = {"rank": slow["rank"], "render_ms": slow["render_ms"],
                                 "spread_ms": round(slow["render_ms"] - min(x["render_ms"] for x in ranks), 3),
                                 "gather_and_host_ms": round(elapsed / args.steps * 1e3 - slow["render_ms"], 3)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the host cores this process may use: min(nproc, cgroup quota); --cpu-threads overrides
             quota = cpu_quota()
             usable = os.cpu_count() or 1

@@ -12,12 +12,12 @@ mkdir -p gpurun_out
 out=gpurun_out/configs_$tag.jsonl; : > $out
 for c in "practice6_1 256 256 4" "cornell 512 512 64" "sponza 1024 1024 256"; do
   set -- $c
-  timeout -k 10 300 python bench.py --scene $1 --width $2 --height $3 --spp $4 --steps 3 --warmup 1 \
+  timeout -k 10 300 python bench.py --full --scene $1 --width $2 --height $3 --spp $4 --steps 3 --warmup 1 \
       --traffic-from none --cpu-rows $(( $3 < 135 ? $3 : 135 )) --cpu-spp $(( $4 < 16 ? $4 : 16 )) \
       --cpu-stride $(( $3 / 135 > 0 ? $3 / 135 : 1 )) >> $out 2>>gpurun_out/configs_$tag.err || exit 1
 done
 timeout -k 10 300 python tools/runahead_ab.py --spp 1024 --worlds 8 --off 0 --steps 1 >> $out 2>>gpurun_out/configs_$tag.err || exit 1
-timeout -k 10 300 python bench.py --scene sponza_dragon --width 3840 --height 2160 --spp 16 --steps 2 --warmup 1 \
+timeout -k 10 300 python bench.py --full --scene sponza_dragon --width 3840 --height 2160 --spp 16 --steps 2 --warmup 1 \
     --traffic-from none --no-cpu-baseline >> $out 2>>gpurun_out/configs_$tag.err || exit 1
 timeout -k 10 300 python tools/runahead_ab.py --scene sponza_dragon --width 3840 --height 2160 --spp 4096 --worlds 8 \
     --max-ranks 1 --full 0 --off 0 --steps 1 >> $out 2>>gpurun_out/configs_$tag.err || exit 1

@@ -12,7 +12,7 @@
 #   tests[=K]            pytest -m gpu (-k K when given)                    gpu_tests.txt
 #   debugtests           the same on the index-checked build (make debug)   debug_gpu_tests.txt
 #   smoke                __graft_entry__.smoke()                            smoke.txt
-#   bench[=ARGS]         bench.py --steps 3 --warmup 1 (or ARGS, comma-separated)   bench.json
+#   bench[=ARGS]         bench.py --steps 3 --warmup 1 --full (or ARGS, comma-separated)   bench.json
 #   ab=N,REPS,LIB+LIB    per library: the 1-GPU frame + every shard of the N-way split, with
 #                        the sha1 of both (tools/order_ab.py), REPS rounds   ab.jsonl
 #   splits=N[,LIB]       every shard of the N-way split only                splits.jsonl
@@ -57,7 +57,7 @@ for step in "$@"; do
         || fail smoke "$OUT/smoke.txt"
       cat "$OUT/smoke.txt" ;;
     bench)
-      A=(--steps 3 --warmup 1); [ -n "$arg" ] && IFS=, read -r -a A <<< "$arg"
+      A=(--steps 3 --warmup 1 --full); [ -n "$arg" ] && IFS=, read -r -a A <<< "$arg"
       timeout -k 10 400 python -u bench.py "${A[@]}" >> "$OUT/bench.json" 2>> "$OUT/bench.err" || fail bench "$OUT/bench.err"
       tail -c 600 "$OUT/bench.json" ;;
     ab)
