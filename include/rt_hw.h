@@ -207,6 +207,56 @@ int rt_render_multi(rt_scene *scene, const rt_params *params, int32_t n_devices,
 int rt_render_frame(rt_scene *scene, const rt_params *params, int32_t n_shards, const int32_t *devices,
                     uint8_t *out_rgb, float *out_sum, rt_stats *stats);
 
+/* --- progressive rendering (additive in ABI 6) ---------------------------------------- */
+/* An accumulator owns the per-pixel chain state of one shard on one device (per pixel: next
+ * sample, minstd_rand state, polar-normal cache, running float sum) and renders further
+ * samples in passes of any size.  After passes of n1, n2, ..., nk samples its sums are
+ * bit-identical to rt_render at spp = n1 + ... + nk, for every split and every schedule flag:
+ * a pixel's samples still run in order from the carried state and add in order to the carried
+ * sum.  This is the seam for the reference's Scene::render(ProgressFunc): previews, progress,
+ * early stop, more samples on a finished frame, checkpoint and resume.
+ *
+ * Parity mode on the lane-resident kernel only: RT_FLAG_NATURAL_ORDER, RT_FLAG_HEAVY_ORDER and
+ * RT_FLAG_NO_RUNAHEAD are honoured; RT_FLAG_FAST, RT_FLAG_LIGHT_SPLIT, RT_FLAG_KERNEL_TIMES,
+ * count != 0 and kernel != RT_KERNEL_LANE fail with RT_ERR_ARG.  The pixel order is chosen per
+ * pass by rt_render's rule on the pass's own sample count (pre-pass at >= 128 samples or with
+ * HEAVY_ORDER); bits never depend on it.
+ *
+ * A pass uses the device scene's workspace: the rule "one render per (scene, device) in
+ * flight" covers accumulator passes too (passes of two accumulators of one scene on one
+ * device, or a pass and an rt_render_device, must not overlap).  Free an accumulator before
+ * its scene. */
+typedef struct rt_accum rt_accum;
+/* Uses rank, world, row_block, device and flags of params (spp is ignored); the scene must be
+ * uploaded to that device (rt_scene_upload).  No samples yet: sums are 0. */
+int rt_accum_create(rt_scene *scene, const rt_params *params, rt_accum **out);
+/* Renders samples [done, done + n_samples) of every owned pixel on HIP stream `stream`;
+ * asynchronous unless stats != NULL, like rt_render_device (stats->samples = pixels x
+ * n_samples; schedule, render_ms, order_ms as there).  n_samples < 1: RT_ERR_ARG; a total of
+ * 2^20 or more: RT_ERR_LIMIT (nothing is launched). */
+int rt_accum_add(rt_accum *accum, int32_t n_samples, void *stream, rt_stats *stats);
+int32_t rt_accum_samples(const rt_accum *accum); /* samples done */
+/* The sums so far in host memory, in rt_render's shard layout (waits for the last pass). */
+int rt_accum_sums(rt_accum *accum, float *out_sum);
+/* The same sums on the device: valid until rt_accum_free, written by every pass. */
+const float *rt_accum_device_sums(rt_accum *accum);
+/* The shard finished to 8 bits at spp = samples done (rt_tonemap_u8_device): rows x W x 3. */
+int rt_accum_frame_u8(rt_accum *accum, uint8_t *out_rgb);
+/* Test / inspection entry: n_pixels x 4 words per pixel: next sample, engine state, cache
+ * flag, cached value bits. */
+int rt_accum_state(rt_accum *accum, uint32_t *out);
+/* Checkpoint: a 128-byte header (magic "RTACCUM\0", u32 version 1; i32 width, height,
+ * ray_depth, rank, world, row_block; u32 n_tris, n_nodes, n_lights; i64 n_pixels; i32 samples
+ * done, i32 0; 14 floats cam_pos, cam_axes, tan_half_fov; 8 bytes 0), then n_pixels records of
+ * 8 words (pixel, next sample, engine state | cache flag << 31, cached value, sum x, y, z, 0).
+ * rt_accum_load checks the file before any device call: missing RT_ERR_IO; bad magic, version
+ * or length RT_ERR_FORMAT; a header that does not fit the scene RT_ERR_ARG.  It then uploads
+ * the scene to `device` if need be; the loaded accumulator (rank, world and row_block of the
+ * file, default schedule flags) continues bit-identically. */
+int rt_accum_save(rt_accum *accum, const char *path);
+int rt_accum_load(rt_scene *scene, int32_t device, const char *path, rt_accum **out);
+void rt_accum_free(rt_accum *accum);
+
 /* Closest hit + light pdf for n explicit rays (BVH::intersect bvh.cpp:239-243 and
  * ManyLightsDistribution::pdf random.cpp:179-188; origin/dir as given to Ray::Ray, which
  * normalises dir).  Host arrays: org/dir n x 3; out_f n x 4 (t, u, v, light_pdf);

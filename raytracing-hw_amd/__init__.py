@@ -103,6 +103,17 @@ ABI = {
     "rt_device_count": (ctypes.c_int32, []),
     "rt_device_synchronize": (ctypes.c_int, []),
     "rt_device_selfcheck": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)]),
+    # progressive rendering: a shard's per-pixel chain state kept between passes
+    "rt_accum_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtParams), ctypes.POINTER(ctypes.c_void_p)]),
+    "rt_accum_add": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(RtStats)]),
+    "rt_accum_samples": (ctypes.c_int32, [ctypes.c_void_p]),
+    "rt_accum_sums": (ctypes.c_int, [ctypes.c_void_p, _c_f]),
+    "rt_accum_device_sums": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "rt_accum_frame_u8": (ctypes.c_int, [ctypes.c_void_p, _c_b]),
+    "rt_accum_state": (ctypes.c_int, [ctypes.c_void_p, _c_u]),
+    "rt_accum_save": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    "rt_accum_load": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "rt_accum_free": (None, [ctypes.c_void_p]),
 }
 
 _lib_handle = None
@@ -326,6 +337,19 @@ class Scene:
         _after_render()
         return st.as_dict() if st else None
 
+    def accumulator(self, rank=0, world=1, row_block=8, device=0, natural_order=False, heavy_order=False,
+                    runahead=True):
+        """Progressive rendering (rt_accum_create): the shard's per-pixel chain state on
+        `device` (uploaded here if need be), rendered further in passes of any size; after
+        passes of n1 + ... + nk samples the sums are those of render_sums(n1 + ... + nk), bit
+        for bit."""
+        self.upload(device)
+        p = self._params(0, rank, world, row_block, False, KERNEL_LANE, device=device, natural_order=natural_order,
+                         runahead=runahead, heavy_order=heavy_order)
+        h = ctypes.c_void_p()
+        _check(lib().rt_accum_create(self._h, ctypes.byref(p), ctypes.byref(h)))
+        return Accumulator(self, h.value, rank, world, row_block)
+
     def render(self):
         """Scene::render (scene.cpp:17-65): sample loop on the GPU, then the 8-bit frame finish."""
         sums, _ = self.render_sums(self.samples)
@@ -336,6 +360,72 @@ class Scene:
         if self.canvas is None:
             raise RtError("render() first")
         write_ppm(filename, self.canvas)
+
+
+class Accumulator:
+    """A shard's chain state between passes (include/rt_hw.h rt_accum): add(n) renders the
+    next n samples of every owned pixel; sums() / frame() are the shard so far."""
+
+    def __init__(self, scene, handle, rank, world, row_block):
+        self._scene = scene   # (kept alive: the accumulator is freed before its scene)
+        self._h = ctypes.c_void_p(handle)
+        self.rank, self.world, self.row_block = rank, world, row_block
+        self.rows = shard_rows(scene.height, rank, world, row_block)
+
+    @classmethod
+    def load(cls, scene, path, device=0):
+        """rt_accum_load: the accumulator rt_accum_save wrote, checked against `scene`."""
+        h = ctypes.c_void_p()
+        _check(lib().rt_accum_load(scene.handle, device, os.fsencode(path), ctypes.byref(h)))
+        with open(path, "rb") as f:   # rank, world, row_block: int32 words 6-8 of the header
+            hdr = np.frombuffer(f.read(36), np.int32)
+        return cls(scene, h.value, int(hdr[6]), int(hdr[7]), int(hdr[8]))
+
+    def add(self, n, stats=True, stream_ptr=None):
+        """Render samples [samples, samples + n) (rt_accum_add); returns the pass's stats
+        (waits), or None with stats=False (asynchronous on the stream)."""
+        st = RtStats() if stats else None
+        _check(lib().rt_accum_add(self._h, int(n), ctypes.c_void_p(stream_ptr or 0), ctypes.byref(st) if st else None))
+        _after_render()
+        return st.as_dict() if st else None
+
+    @property
+    def samples(self):
+        return int(lib().rt_accum_samples(self._h))
+
+    def sums(self):
+        """(rows, W, 3) float sums so far, as render_sums returns them."""
+        out = np.zeros((len(self.rows), self._scene.width, 3), np.float32)
+        _check(lib().rt_accum_sums(self._h, out.ctypes.data_as(_c_f)))
+        return out
+
+    @property
+    def device_sums_ptr(self):
+        return int(lib().rt_accum_device_sums(self._h) or 0)
+
+    def frame(self):
+        """(rows, W, 3) uint8: the shard finished at spp = samples (on the device)."""
+        out = np.zeros((len(self.rows), self._scene.width, 3), np.uint8)
+        _check(lib().rt_accum_frame_u8(self._h, out.ctypes.data_as(_c_b)))
+        return out
+
+    def state(self):
+        """(pixels, 4) uint32 per shard pixel: next sample, engine state, cache flag, cached value bits."""
+        out = np.zeros((len(self.rows) * self._scene.width, 4), np.uint32)
+        _check(lib().rt_accum_state(self._h, out.ctypes.data_as(_c_u)))
+        return out
+
+    def save(self, path):
+        _check(lib().rt_accum_save(self._h, os.fsencode(path)))
+
+    def free(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib_handle is not None:
+            _lib_handle.rt_accum_free(h)
+        self._h = None
+
+    def __del__(self):
+        self.free()
 
 
 def make_view(a):

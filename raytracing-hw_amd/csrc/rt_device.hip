@@ -198,9 +198,10 @@ struct rt_device_scene {
     void *buf = nullptr;               // one allocation holding every scene array
     DevScene ds{};
     unsigned long long *counters = nullptr;  // 16 x u64: [0, 8) the render, [8, 16) the order pre-pass
-    unsigned long long *queue = nullptr;     // 8 x u64: work counters of the render and the pre-pass, the
-                                             // hand-off's park count (u32), its runahead launch's claims and
-                                             // the address of its park list (rt_mega_kernel `mode`)
+    unsigned long long *queue = nullptr;     // 32 x u64: [0, 8) work counters of the render and the pre-pass,
+                                             // the hand-off's park count (u32), its runahead launch's claims and
+                                             // the address of its park list (rt_mega_kernel `mode`); [16] the
+                                             // accumulator's chain buffer (rt_mega.h kChainWord: its own line)
     int cu_count = 0;
     // vertex records (lane-resident) / path state and queues (wavefront)
     void *wf_buf = nullptr;
@@ -367,11 +368,17 @@ struct TbAcc {
 //              (per: resume_pct percent of the slots over the grid's waves, at most 64), skips
 //              the empty ones and enters its tail at once; the slots past the grid's share are
 //              claimed in the tail (rt_mega.h SpecClaim) through the counter at queue + 3.
-template <bool COUNT, bool FAST = false, bool LSPLIT = false, bool SPEC = false>
+// CHAIN (rt_accum_add; parity renders without counting, plain and runahead kernels only): the
+// pass of an accumulator.  `spp` is the absolute sample the pass ends at; a pixel starts from its
+// record in the chain buffer and the lane that adds its last sample stores the record back
+// (rt_mega.h, chain buffer; the buffer's address in queue[16], read where used).  Separate
+// instantiations again: the one-shot kernels are the code they were.
+template <bool COUNT, bool FAST = false, bool LSPLIT = false, bool SPEC = false, bool CHAIN = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SPEC ? kMegaWpeSpec : kMegaWpe, 8)))
 rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out, unsigned long long *counters,
                unsigned long long *queue, const int *order, unsigned *cost, int cs, int mode) {
     constexpr bool kSpec = SPEC && !COUNT && !FAST && !LSPLIT;
+    constexpr bool kChain = CHAIN && !COUNT && !FAST && !LSPLIT;
     const int park_below = mode & 255, resume_pct = (mode >> 8) & 255;
     const uint4 *resume = kSpec && resume_pct > 0 ? (const uint4 *)queue[4] : nullptr;
     const long long n_items = FAST ? g.n_pixels * (long long)((spp + cs - 1) / cs) : (kSpec && resume) ? st.n : g.n_pixels;
@@ -501,6 +508,8 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
                     const long long p = (long long)base + below;
                     if (p < n_items) {
                         if (FAST) rtd::mega_assign_fast<COUNT>(L, sc, g, p, cs, spp, root, cnt);
+                        else if constexpr (kChain)
+                            rtd::mega_assign_chain<COUNT>(L, sc, g, order ? order[p] : (int)p, root, cnt, rtd::chain_of(queue));
                         else rtd::mega_assign<COUNT>(L, sc, g, order ? order[p] : (int)p, root, cnt);
                     }
                 }
@@ -510,7 +519,11 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
         if constexpr (kSpec) {
             if (exhausted && !tail) {
                 if (lane == 0) rtd::spec_hint_take();
-                rtd::spec_convert(L, sc, g, rtd::SpecView{(uint4 *)st.mid, st.lanes, rtd::mega_slot() - lane}, lane);
+                if constexpr (kChain)
+                    rtd::spec_convert_chain(L, sc, g, rtd::SpecView{(uint4 *)st.mid, st.lanes, rtd::mega_slot() - lane}, lane,
+                                            rtd::chain_of(queue));
+                else
+                    rtd::spec_convert(L, sc, g, rtd::SpecView{(uint4 *)st.mid, st.lanes, rtd::mega_slot() - lane}, lane);
                 tail = true;
                 wave_room = false;
 #ifdef RT_MEGA_PROF
@@ -524,7 +537,7 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
                     const long long c0 = clock64();
                     tbk.c[5] += 1;
 #endif
-                    wave_room = rtd::spec_manage(rtd::SpecLanes{L}, sc, g,
+                    wave_room = rtd::spec_manage<kChain>(rtd::SpecLanes{L}, sc, g,
                                                  rtd::SpecView{(uint4 *)st.mid, st.lanes, rtd::mega_slot() - lane}, spp,
                                                  out, root, claim);
 #ifdef RT_MEGA_PROF
@@ -608,15 +621,16 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
             if (L.state == rtd::M_READY) {
                 L.T.phase = 0;   // dead in a READY lane (its stack is empty: T.sp == 0)
                 L.T.sp = 0;
-                rtd::mega_shade<COUNT, FAST>(L, sc, g, st, spp, out, cost, root, S, cnt, kSpec && tail, park);
+                rtd::mega_shade<COUNT, FAST, kChain>(L, sc, g, st, spp, out, cost, root, S, cnt, kSpec && tail, park, queue);
             } else {
                 L.T.phase = (int)(pk & 3u);
                 L.state = (int)((pk >> 2) & 7u);
                 L.T.sp = (int)(pk >> 5);
             }
         } else {
-            rtd::mega_iterate<COUNT, decltype(S), decltype(nodes), FAST, LSPLIT>(L, shade_now, sc, g, st, spp, out, cost,
-                                                                               root, S, nodes, cnt, kSpec && tail);
+            rtd::mega_iterate<COUNT, decltype(S), decltype(nodes), FAST, LSPLIT, kChain>(L, shade_now, sc, g, st, spp, out,
+                                                                                       cost, root, S, nodes, cnt,
+                                                                                       kSpec && tail, false, queue);
             // RT_INV_RECOMPUTE: 1 / direction is recomputed after a shading pass (the same IEEE
             // division as make_ray, so the same bits), so a traversing lane does not hold it
             // through the pass's register peak (plain kernel 48 -> 42 spilled VGPRs; 39 with
@@ -1010,7 +1024,7 @@ int ensure_device_scene(rt_scene *s, int device) {
     hipError_t e = hipMalloc(&d->buf, b.bytes.size());
     if (e == hipSuccess) e = hipMemcpy(d->buf, b.bytes.data(), b.bytes.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc((void **)&d->counters, 16 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc((void **)&d->queue, 8 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc((void **)&d->queue, 32 * sizeof(unsigned long long));
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
     if (e != hipSuccess) {
@@ -1241,7 +1255,19 @@ int check_flags(const rt_params *p, const char *who) {
     return RT_OK;
 }
 
-int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt_stats *st) {
+// An accumulator's pass (rt_accum_add): the chain buffer and the samples the pass adds.  The
+// render's spp is then the absolute sample the pass ends at; the pixel order and the stats go
+// by the pass's own sample count.
+struct ChainPass {
+    uint4 *chain;
+    int n;
+};
+
+// One shard on one device: rt_render_device, and with `cp` a pass of rt_accum_add (the caller
+// has checked that the parameters select a parity render on the lane-resident kernel).  A
+// one-shot render launches exactly what it launched before the accumulator existed.
+int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt_stats *st,
+           const ChainPass *cp = nullptr) {
     if (!s || !p || !d_out) return rt_fail(RT_ERR_ARG, "rt_render: NULL argument");
     if (int rc = check_flags(p, "rt_render")) return rc;
     if (p->device < 0 || p->device >= kRtMaxDevices || !s->dev[p->device])
@@ -1300,13 +1326,15 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
             // Speculative sample runahead (rt_mega.h) where the frame is mostly tail: a shard of
             // at most kSpecPixelsPerLane pixels per resident lane (the 8-way split of the
             // headline: 342 -> 304 ms in round 2; at 4-way, 2 pixels per lane, 359 -> 348 ms in round 3).
-            const long long full_blocks = resident_blocks(d, rt_mega_kernel<false, false, false, true>);
+            const long long full_blocks = cp ? resident_blocks(d, rt_mega_kernel<false, false, false, true, true>)
+                                             : resident_blocks(d, rt_mega_kernel<false, false, false, true>);
             const bool spec = !fast && !lsplit && !count && !(p->flags & RT_FLAG_NO_RUNAHEAD) &&
                               g.n_pixels * kClaimStride <= kSpecPixelsPerLane * full_blocks * 256;
             auto mk = fast ? (count ? rt_mega_kernel<true, true> : rt_mega_kernel<false, true>)
                            : lsplit ? (count ? rt_mega_kernel<true, false, true> : rt_mega_kernel<false, false, true>)
                                     : count ? rt_mega_kernel<true>
                                             : spec ? rt_mega_kernel<false, false, false, true> : rt_mega_kernel<false>;
+            if (cp) mk = spec ? rt_mega_kernel<false, false, false, true, true> : rt_mega_kernel<false, false, false, false, true>;
             sched = fast ? RT_SCHED_FAST : lsplit ? RT_SCHED_LIGHT_SPLIT : spec ? RT_SCHED_RUNAHEAD : RT_SCHED_LANE;
             const bool handoff = !spec && !fast && !lsplit && !count && !(p->flags & RT_FLAG_NO_RUNAHEAD) &&
                                  kClaimStride == 1;
@@ -1327,7 +1355,8 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
             }
             w.round_min = d->ds.n_nodes < kCoopRoundNodes ? kCoopRoundMinSpec : 65;
             int *order = nullptr;
-            if (!fast && !(p->flags & RT_FLAG_NATURAL_ORDER) && (spp >= kOrderMinSpp || (p->flags & RT_FLAG_HEAVY_ORDER))) {
+            const int order_spp = cp ? cp->n : spp;   // (a pass is ordered by the rule on its own samples)
+            if (!fast && !(p->flags & RT_FLAG_NATURAL_ORDER) && (order_spp >= kOrderMinSpp || (p->flags & RT_FLAG_HEAVY_ORDER))) {
                 // the spread deals one pixel of every cost stratum to each claim of 64 of the
                 // launch's first round (one per wave)
                 rc = launch_order(d, g, stream, 4LL * blocks, 64, &order);
@@ -1352,6 +1381,11 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
                 HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_tb), ztb.data(), ztb.size() * 8, 0, hipMemcpyHostToDevice, stream));
             }
 #endif
+            if (cp) {   // the chain buffer's address, where the chain kernels read it
+                hipLaunchKernelGGL(rt_set_u64_kernel, dim3(1), dim3(1), 0, stream, d->queue + rtd::kChainWord,
+                                   (unsigned long long)(uintptr_t)cp->chain);
+                HIP_TRY(hipGetLastError());
+            }
             hipLaunchKernelGGL(mk, dim3(blocks), dim3(256), 0, stream, d->ds, g, w, spp, k_out, d->counters, d->queue,
                                (const int *)order, (unsigned *)nullptr, cs, handoff ? kHandoffBelow : 0);
             HIP_TRY(hipGetLastError());
@@ -1389,9 +1423,9 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
                 rtd::WfState w2 = w;
                 w2.lanes = full_blocks * 256;
                 w2.n = slots;   // the park list's slots
-                hipLaunchKernelGGL((rt_mega_kernel<false, false, false, true>), dim3((unsigned)full_blocks), dim3(256), 0,
-                                   stream, d->ds, g, w2, spp, k_out, d->counters, d->queue, (const int *)nullptr,
-                                   (unsigned *)nullptr, 0, kHandoffPct << 8);
+                auto rk = cp ? rt_mega_kernel<false, false, false, true, true> : rt_mega_kernel<false, false, false, true>;
+                hipLaunchKernelGGL(rk, dim3((unsigned)full_blocks), dim3(256), 0, stream, d->ds, g, w2, spp, k_out,
+                                   d->counters, d->queue, (const int *)nullptr, (unsigned *)nullptr, 0, kHandoffPct << 8);
                 HIP_TRY(hipGetLastError());
             }
             if (fast) {
@@ -1528,7 +1562,7 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
         if (ordered) HIP_TRY(hipEventElapsedTime(&ms_order, e0, e_order));
         std::memset(st, 0, sizeof *st);
         st->pixels = (uint64_t)g.n_pixels;
-        st->samples = (uint64_t)g.n_pixels * (uint64_t)spp;
+        st->samples = (uint64_t)g.n_pixels * (uint64_t)(cp ? cp->n : spp);
         st->render_ms = ms;
         st->order_ms = ms_order;
         st->devices = 1;
@@ -1646,6 +1680,329 @@ int rt_render(rt_scene *s, const rt_params *p, float *out, rt_stats *st) {
     if (int rc = check_flags(p, "rt_render")) return rc;
     return render_host(s, p, out, st);
 }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------ accumulator
+// rt_accum_* (include/rt_hw.h): the per-pixel chain state of one shard on one device, kept
+// between passes (rt_mega.h, chain buffer).  The accumulator owns the chain buffer (32 B per
+// shard pixel) and the float sums its passes write; a pass is launch() with a ChainPass.
+struct rt_accum {
+    rt_scene *scene = nullptr;
+    rt_params p{};            // rank, world, row_block, device, flags (normalised)
+    long long n_pixels = 0;
+    int rows = 0;
+    int samples = 0;          // samples done
+    uint4 *chain = nullptr;   // n_pixels Parked records
+    float *sums = nullptr;    // n_pixels x 3
+    uint8_t *rgb = nullptr;   // n_pixels x 3, made by the first rt_accum_frame_u8
+    hipStream_t stream = nullptr;   // the last pass's stream (host reads wait for it)
+};
+
+__global__ void __launch_bounds__(256) rt_chain_init_kernel(DevScene sc, ShardGeom g, uint4 *chain, float *sums) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= g.n_pixels) return;
+    rtd::chain_init(chain, sc, g, (int)p);
+    sums[3 * p + 0] = 0.f;
+    sums[3 * p + 1] = 0.f;
+    sums[3 * p + 2] = 0.f;
+}
+
+namespace {
+
+// The checkpoint file (rt_accum_save): this header, then n_pixels records of 8 words in the
+// chain buffer's layout (pixel, next sample, engine state | cache flag << 31, cached value |
+// sum x, y, z, 0).  Little-endian, as the devices and their hosts are.
+constexpr char kAccumMagic[8] = {'R', 'T', 'A', 'C', 'C', 'U', 'M', '\0'};
+constexpr uint32_t kAccumVersion = 1;
+struct AccumHeader {
+    char magic[8];
+    uint32_t version;
+    int32_t width, height, ray_depth;
+    int32_t rank, world, row_block;
+    uint32_t n_tris, n_nodes, n_lights;
+    int64_t n_pixels;
+    int32_t samples, reserved;
+    float cam[14];   // cam_pos, cam_axes, tan_half_fov
+    uint32_t pad[2];
+};
+static_assert(sizeof(AccumHeader) == 128, "rt_accum file header is 128 bytes");
+
+void accum_header_fill(const rt_scene *s, AccumHeader &h) {
+    std::memset(&h, 0, sizeof h);
+    std::memcpy(h.magic, kAccumMagic, 8);
+    h.version = kAccumVersion;
+    h.width = s->width;
+    h.height = s->height;
+    h.ray_depth = s->ray_depth;
+    h.n_tris = (uint32_t)(s->tri.size() / 12);
+    h.n_nodes = (uint32_t)(s->node.size() / 8);
+    h.n_lights = (uint32_t)(s->light.size() / 16);
+    std::memcpy(h.cam, s->cam_pos, 12);
+    std::memcpy(h.cam + 3, s->cam_axes, 36);
+    std::memcpy(h.cam + 12, s->tan_half_fov, 8);
+}
+
+// What an accumulator renders with: a parity render on the lane-resident kernel.
+int accum_check_params(const rt_params *p, const char *who) {
+    if (int rc = check_flags(p, who)) return rc;
+    const std::string w = who;
+    if (p->flags & RT_FLAG_FAST) return rt_fail(RT_ERR_ARG, w + ": fast mode has no accumulator (its sum is defined per (spp, fast_chunk))");
+    if (p->flags & RT_FLAG_LIGHT_SPLIT) return rt_fail(RT_ERR_ARG, w + ": the light-split kernel has no accumulator");
+    if (p->flags & RT_FLAG_KERNEL_TIMES) return rt_fail(RT_ERR_ARG, w + ": RT_FLAG_KERNEL_TIMES is a wavefront option; accumulators run on kernel 0");
+    if (p->count != 0) return rt_fail(RT_ERR_ARG, w + ": counting renders have no accumulator (count must be 0)");
+    if (p->kernel != RT_KERNEL_LANE) return rt_fail(RT_ERR_ARG, w + ": accumulators run on the lane-resident kernel only (kernel 0)");
+    if ((p->flags & RT_FLAG_NATURAL_ORDER) && (p->flags & RT_FLAG_HEAVY_ORDER))
+        return rt_fail(RT_ERR_ARG, w + ": RT_FLAG_NATURAL_ORDER and RT_FLAG_HEAVY_ORDER exclude each other");
+    return RT_OK;
+}
+
+void accum_release(rt_accum *a) {
+    if (!a) return;
+    if (a->chain || a->sums || a->rgb) {
+        DeviceGuard guard(a->p.device);
+        if (a->chain) (void)hipFree(a->chain);
+        if (a->sums) (void)hipFree(a->sums);
+        if (a->rgb) (void)hipFree(a->rgb);
+    }
+    delete a;
+}
+
+// Host-side part of create / load: parameters and shard, no device call.
+int accum_new(rt_scene *s, const rt_params *p, const char *who, rt_accum **out) {
+    if (int rc = accum_check_params(p, who)) return rc;
+    if (p->device < 0 || p->device >= kRtMaxDevices) return rt_fail(RT_ERR_ARG, std::string(who) + ": bad device " + std::to_string(p->device));
+    if ((int64_t)s->width * s->height > INT32_MAX)
+        return rt_fail(RT_ERR_LIMIT, std::string(who) + ": frames above 2^31 pixels are not supported");
+    rt_accum *a = new rt_accum();
+    a->scene = s;
+    a->p = *p;
+    a->p.spp = 0;
+    a->p.world = p->world > 0 ? p->world : 1;
+    a->p.row_block = p->row_block > 0 ? p->row_block : 8;
+    const int64_t rows = rt_shard_rows_impl(s->height, a->p.rank, a->p.world, a->p.row_block, nullptr);
+    if (rows < 0) {
+        delete a;
+        return RT_ERR_ARG;
+    }
+    a->rows = (int)rows;
+    a->n_pixels = (long long)rows * s->width;
+    *out = a;
+    return RT_OK;
+}
+
+// Device buffers of a new accumulator (the scene is on the device).
+int accum_alloc(rt_accum *a) {
+    DeviceGuard guard(a->p.device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    const size_t n = (size_t)std::max<long long>(a->n_pixels, 1);
+    HIP_TRY(hipMalloc((void **)&a->chain, n * 32));
+    HIP_TRY(hipMalloc((void **)&a->sums, n * 3 * sizeof(float)));
+    return RT_OK;
+}
+
+int accum_wait(rt_accum *a) {
+    HIP_TRY(hipStreamSynchronize(a->stream));
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_accum_create(rt_scene *s, const rt_params *p, rt_accum **out) {
+    if (!s || !p || !out) return rt_fail(RT_ERR_ARG, "rt_accum_create: NULL argument");
+    *out = nullptr;
+    rt_accum *a = nullptr;
+    if (int rc = accum_new(s, p, "rt_accum_create", &a)) return rc;
+    if (!s->dev[a->p.device]) {
+        accum_release(a);
+        return rt_fail(RT_ERR_ARG, "rt_accum_create: scene not uploaded to device " + std::to_string(p->device));
+    }
+    int rc = accum_alloc(a);
+    if (rc == RT_OK && a->n_pixels > 0) {
+        DeviceGuard guard(a->p.device);
+        const ShardGeom g = rtd::shard_geom(s->width, a->p.rank, a->p.world, a->p.row_block, a->n_pixels);
+        hipLaunchKernelGGL(rt_chain_init_kernel, dim3((unsigned)((a->n_pixels + 255) / 256)), dim3(256), 0, nullptr,
+                           s->dev[a->p.device]->ds, g, a->chain, a->sums);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) rc = rt_fail(RT_ERR_DEVICE, std::string("rt_accum_create: ") + hipGetErrorString(e));
+    }
+    if (rc) {
+        accum_release(a);
+        return rc;
+    }
+    *out = a;
+    return RT_OK;
+}
+
+int rt_accum_add(rt_accum *a, int32_t n_samples, void *stream, rt_stats *st) {
+    if (!a) return rt_fail(RT_ERR_ARG, "rt_accum_add: NULL accumulator");
+    if (n_samples < 1) return rt_fail(RT_ERR_ARG, "rt_accum_add: n_samples must be >= 1");
+    if ((long long)a->samples + n_samples >= (1 << 20))
+        return rt_fail(RT_ERR_LIMIT, "rt_accum_add: total samples per pixel must be < 2^20");
+    rt_params p = a->p;
+    p.spp = a->samples + n_samples;   // the absolute sample this pass ends at
+    const ChainPass cp{a->chain, n_samples};
+    a->stream = (hipStream_t)stream;
+    int rc = launch(a->scene, &p, a->sums, (hipStream_t)stream, st, &cp);
+    if (rc) return rc;
+    a->samples += n_samples;
+    return RT_OK;
+}
+
+int32_t rt_accum_samples(const rt_accum *a) { return a ? a->samples : 0; }
+
+int rt_accum_sums(rt_accum *a, float *out_sum) {
+    if (!a || !out_sum) return rt_fail(RT_ERR_ARG, "rt_accum_sums: NULL argument");
+    DeviceGuard guard(a->p.device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = accum_wait(a)) return rc;
+    HIP_TRY(hipMemcpy(out_sum, a->sums, (size_t)a->n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+const float *rt_accum_device_sums(rt_accum *a) { return a ? a->sums : nullptr; }
+
+int rt_accum_frame_u8(rt_accum *a, uint8_t *out_rgb) {
+    if (!a || !out_rgb) return rt_fail(RT_ERR_ARG, "rt_accum_frame_u8: NULL argument");
+    if (a->samples < 1) return rt_fail(RT_ERR_ARG, "rt_accum_frame_u8: no samples yet");
+    if (a->n_pixels == 0) return RT_OK;
+    DeviceGuard guard(a->p.device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    if (!a->rgb) HIP_TRY(hipMalloc((void **)&a->rgb, (size_t)a->n_pixels * 3));
+    if (int rc = rt_tonemap_u8_device(a->sums, a->scene->width, a->rows, a->samples, a->rgb, a->stream)) return rc;
+    if (int rc = accum_wait(a)) return rc;
+    HIP_TRY(hipMemcpy(out_rgb, a->rgb, (size_t)a->n_pixels * 3, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// Host copy of the chain buffer (after the last pass).
+static int accum_records(rt_accum *a, std::vector<uint32_t> &rec) {
+    rec.resize((size_t)a->n_pixels * 8);
+    DeviceGuard guard(a->p.device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = accum_wait(a)) return rc;
+    if (a->n_pixels) HIP_TRY(hipMemcpy(rec.data(), a->chain, rec.size() * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_accum_state(rt_accum *a, uint32_t *out) {
+    if (!a || !out) return rt_fail(RT_ERR_ARG, "rt_accum_state: NULL argument");
+    std::vector<uint32_t> rec;
+    if (int rc = accum_records(a, rec)) return rc;
+    for (long long k = 0; k < a->n_pixels; ++k) {
+        out[4 * k + 0] = rec[8 * k + 1];
+        out[4 * k + 1] = rec[8 * k + 2] & 0x7fffffffu;   // (rt_mega.h rng_word_pack)
+        out[4 * k + 2] = rec[8 * k + 2] >> 31;
+        out[4 * k + 3] = rec[8 * k + 3];
+    }
+    return RT_OK;
+}
+
+int rt_accum_save(rt_accum *a, const char *path) {
+    if (!a || !path) return rt_fail(RT_ERR_ARG, "rt_accum_save: NULL argument");
+    std::vector<uint32_t> rec;
+    if (int rc = accum_records(a, rec)) return rc;
+    AccumHeader h;
+    accum_header_fill(a->scene, h);
+    h.rank = a->p.rank;
+    h.world = a->p.world;
+    h.row_block = a->p.row_block;
+    h.n_pixels = a->n_pixels;
+    h.samples = a->samples;
+    std::FILE *f = std::fopen(path, "wb");
+    if (!f) return rt_fail(RT_ERR_IO, std::string("rt_accum_save: cannot write ") + path);
+    bool ok = std::fwrite(&h, sizeof h, 1, f) == 1;
+    ok = ok && (rec.empty() || std::fwrite(rec.data(), 4, rec.size(), f) == rec.size());
+    ok = (std::fclose(f) == 0) && ok;
+    if (!ok) return rt_fail(RT_ERR_IO, std::string("rt_accum_save: short write to ") + path);
+    return RT_OK;
+}
+
+int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out) {
+    if (!s || !path || !out) return rt_fail(RT_ERR_ARG, "rt_accum_load: NULL argument");
+    *out = nullptr;
+    // the file is read and checked whole before any device call
+    const std::string who = std::string("rt_accum_load: ") + path;
+    std::FILE *f = std::fopen(path, "rb");
+    if (!f) return rt_fail(RT_ERR_IO, who + ": cannot open");
+    AccumHeader h;
+    std::vector<uint32_t> rec;
+    int rc = RT_OK;
+    if (std::fread(&h, sizeof h, 1, f) != 1) rc = rt_fail(RT_ERR_FORMAT, who + ": shorter than its header");
+    else if (std::memcmp(h.magic, kAccumMagic, 8) != 0) rc = rt_fail(RT_ERR_FORMAT, who + ": not an accumulator file (magic)");
+    else if (h.version != kAccumVersion)
+        rc = rt_fail(RT_ERR_FORMAT, who + ": version " + std::to_string(h.version) + ", this library reads " + std::to_string(kAccumVersion));
+    else if (h.n_pixels < 0 || h.n_pixels > INT32_MAX || h.samples < 0 || h.samples >= (1 << 20))
+        rc = rt_fail(RT_ERR_FORMAT, who + ": bad pixel or sample count");
+    else {
+        std::fseek(f, 0, SEEK_END);
+        const long long len = (long long)std::ftell(f);
+        if (len != (long long)sizeof h + h.n_pixels * 32)
+            rc = rt_fail(RT_ERR_FORMAT, who + ": " + std::to_string(len) + " bytes, expected " +
+                                            std::to_string((long long)sizeof h + h.n_pixels * 32));
+        else {
+            std::fseek(f, (long)sizeof h, SEEK_SET);
+            rec.resize((size_t)h.n_pixels * 8);
+            if (!rec.empty() && std::fread(rec.data(), 4, rec.size(), f) != rec.size())
+                rc = rt_fail(RT_ERR_IO, who + ": read failed");
+        }
+    }
+    std::fclose(f);
+    if (rc) return rc;
+    AccumHeader want;
+    accum_header_fill(s, want);
+    if (h.width != want.width || h.height != want.height || h.ray_depth != want.ray_depth)
+        return rt_fail(RT_ERR_ARG, who + ": made for a " + std::to_string(h.width) + " x " + std::to_string(h.height) +
+                                       " frame at ray depth " + std::to_string(h.ray_depth) + ", the scene is " +
+                                       std::to_string(want.width) + " x " + std::to_string(want.height) + " at " +
+                                       std::to_string(want.ray_depth));
+    if (h.n_tris != want.n_tris || h.n_nodes != want.n_nodes || h.n_lights != want.n_lights ||
+        std::memcmp(h.cam, want.cam, sizeof h.cam) != 0)
+        return rt_fail(RT_ERR_ARG, who + ": made for another scene or camera");
+    if (h.world < 1 || h.rank < 0 || h.rank >= h.world || h.row_block < 1)
+        return rt_fail(RT_ERR_ARG, who + ": bad shard (rank " + std::to_string(h.rank) + ", world " + std::to_string(h.world) +
+                                       ", row_block " + std::to_string(h.row_block) + ")");
+    rt_params p{};
+    p.rank = h.rank;
+    p.world = h.world;
+    p.row_block = h.row_block;
+    p.device = device;
+    rt_accum *a = nullptr;
+    if (int rc2 = accum_new(s, &p, "rt_accum_load", &a)) return rc2;
+    if (a->n_pixels != h.n_pixels) {
+        const long long have = a->n_pixels;
+        accum_release(a);
+        return rt_fail(RT_ERR_ARG, who + ": " + std::to_string(h.n_pixels) + " pixels, the shard (rank " + std::to_string(h.rank) +
+                                       ", world " + std::to_string(h.world) + ") of this scene has " + std::to_string(have));
+    }
+    for (long long k = 0; k < h.n_pixels; ++k)
+        if (rec[8 * k] != (uint32_t)k || rec[8 * k + 1] != (uint32_t)h.samples) {
+            accum_release(a);
+            return rt_fail(RT_ERR_FORMAT, who + ": record " + std::to_string(k) + " does not belong to this file");
+        }
+    rc = ensure_device_scene(s, device);   // (the file fits the scene: first device call)
+    if (rc == RT_OK) rc = accum_alloc(a);
+    if (rc == RT_OK && a->n_pixels > 0) {
+        DeviceGuard guard(device);
+        std::vector<float> sums((size_t)h.n_pixels * 3);
+        for (long long k = 0; k < h.n_pixels; ++k) std::memcpy(&sums[3 * k], &rec[8 * k + 4], 12);
+        hipError_t e = hipMemcpy(a->chain, rec.data(), rec.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(a->sums, sums.data(), sums.size() * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) rc = rt_fail(RT_ERR_DEVICE, std::string("rt_accum_load: ") + hipGetErrorString(e));
+    }
+    if (rc) {
+        accum_release(a);
+        return rc;
+    }
+    a->samples = h.samples;
+    *out = a;
+    return RT_OK;
+}
+
+void rt_accum_free(rt_accum *a) { accum_release(a); }
 
 // The whole frame as shards 0 .. n-1 of a (world n, row_block) split, shard r on device
 // devices[r] (include/rt_hw.h rt_render_frame).  One host thread per distinct device renders

@@ -4,6 +4,15 @@
 // behaviour on errors (std::runtime_error), rendering through librt_hw_amd on every GPU of
 // the node (rt_render_frame: one row-block shard per device, finished on its GPU and gathered
 // device-to-device onto GPU 0; RT_GPUS=n uses devices 0..n-1).
+// Progressive rendering (two more environment variables; unset, the run is the one above):
+//   RT_PASS_SPP=k       render in passes of k samples (one accumulator per device, rt_accum_*);
+//                       after every pass the frame so far is written to the output file and a
+//                       line "Progress: done / total samples" is printed.  The final file is
+//                       byte-identical to the one-shot run's.
+//   RT_CHECKPOINT=pfx   after every pass shard r of n is saved to pfx.<r>of<n>; if those files
+//                       exist at the start the run resumes from them (and fails with the
+//                       library's message when they do not fit the scene).
+#include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <cstdio>
@@ -17,6 +26,71 @@
 
 static void check(int rc) {
     if (rc != RT_OK) throw std::runtime_error(rt_last_error());
+}
+
+// The frame in passes: device d renders shard (rank d, world n) through its own accumulator.
+static void render_passes(rt_scene *scene, int width, int height, int samples, int n_gpus, int pass_spp,
+                          const char *ckpt, const std::string &output) {
+    const int n = n_gpus > 0 ? n_gpus : rt_device_count();
+    if (n < 1) throw std::runtime_error("no HIP device");
+    if (samples < 1) throw std::runtime_error("samples per pixel must be >= 1");
+    struct Accums {   // (freed on every way out)
+        std::vector<rt_accum *> v;
+        ~Accums() { for (rt_accum *a : v) rt_accum_free(a); }
+    } held;
+    held.v.assign((size_t)n, nullptr);
+    std::vector<rt_accum *> &acc = held.v;
+    auto file_of = [&](int r) { return std::string(ckpt) + "." + std::to_string(r) + "of" + std::to_string(n); };
+    bool resume = ckpt != nullptr;
+    for (int r = 0; resume && r < n; ++r) {
+        std::FILE *f = std::fopen(file_of(r).c_str(), "rb");
+        if (f) std::fclose(f);
+        else resume = false;
+    }
+    for (int r = 0; r < n; ++r) {
+        if (resume) {
+            check(rt_accum_load(scene, r, file_of(r).c_str(), &acc[(size_t)r]));
+        } else {
+            check(rt_scene_upload(scene, r));
+            rt_params p{};
+            p.rank = r;
+            p.world = n;
+            p.row_block = 8;
+            p.device = r;
+            check(rt_accum_create(scene, &p, &acc[(size_t)r]));
+        }
+    }
+    int done = rt_accum_samples(acc[0]);
+    for (int r = 1; r < n; ++r)
+        if (rt_accum_samples(acc[(size_t)r]) != done) throw std::runtime_error("checkpoint shards are at different sample counts");
+    if (done > samples)
+        throw std::runtime_error("checkpoint holds " + std::to_string(done) + " samples, more than the " +
+                                 std::to_string(samples) + " asked for");
+    if (resume) std::cout << "Resumed from " << ckpt << " at " << done << " samples." << std::endl;
+    std::vector<uint8_t> rgb((size_t)width * height * 3), part;
+    std::vector<int32_t> rows((size_t)height);
+    auto write_frame = [&]() {
+        for (int r = 0; r < n; ++r) {
+            const int64_t k = rt_shard_rows(height, r, n, 8, rows.data());
+            if (k < 0) check((int)k);
+            part.resize((size_t)k * width * 3);
+            check(rt_accum_frame_u8(acc[(size_t)r], part.data()));
+            for (int64_t i = 0; i < k; ++i)
+                std::copy(part.begin() + i * width * 3, part.begin() + (i + 1) * width * 3,
+                          rgb.begin() + (size_t)rows[(size_t)i] * width * 3);
+        }
+        check(rt_write_ppm(output.c_str(), rgb.data(), width, height));
+    };
+    if (done == samples && done > 0) write_frame();
+    while (done < samples) {
+        const int k = pass_spp > 0 ? std::min(pass_spp, samples - done) : samples - done;
+        for (int r = 0; r < n; ++r) check(rt_accum_add(acc[(size_t)r], k, nullptr, nullptr));   // (asynchronous: the devices overlap)
+        done += k;
+        write_frame();   // (waits for every device's pass)
+        if (ckpt)
+            for (int r = 0; r < n; ++r) check(rt_accum_save(acc[(size_t)r], file_of(r).c_str()));
+        std::cout << "Progress: " << done << " / " << samples << " samples" << std::endl;
+    }
 }
 
 static int int_arg(const char *s) { return std::stoi(std::string(s).substr(0, std::string(s).find(' '))); }
@@ -38,6 +112,23 @@ int main(int argc, char *argv[]) {
     std::cout << std::setprecision(6) << "Rendering scene." << std::endl;
     const char *g = std::getenv("RT_GPUS");
     const int n_gpus = g ? std::atoi(g) : 0;   // 0: every visible device
+    const char *pass_env = std::getenv("RT_PASS_SPP"), *ckpt = std::getenv("RT_CHECKPOINT");
+    if ((pass_env && *pass_env) || (ckpt && *ckpt)) {
+        const int pass_spp = pass_env && *pass_env ? std::atoi(pass_env) : 0;
+        if (pass_env && *pass_env && pass_spp < 1) throw std::runtime_error("RT_PASS_SPP must be >= 1");
+        try {
+            render_passes(scene, width, height, samples, n_gpus, pass_spp, ckpt && *ckpt ? ckpt : nullptr, output);
+        } catch (const std::exception &e) {   // (a checkpoint that does not fit, a failed pass: the message, status 1)
+            std::cerr << "rt_solution: " << e.what() << std::endl;
+            rt_scene_free(scene);
+            return 1;
+        }
+        double total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        std::cout << "      " << total << " seconds (" << total * 1000 << " ms) elapsed." << std::endl;
+        std::cout << "Frame drawn into " << output << std::endl;
+        rt_scene_free(scene);
+        return 0;
+    }
     rt_params p{};
     p.spp = samples;
     p.row_block = 8;

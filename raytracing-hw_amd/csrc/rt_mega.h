@@ -274,6 +274,45 @@ __device__ __forceinline__ void park_pixel(uint4 *park, long long slot, int pix,
     park[2 * slot] = make_uint4((uint32_t)pix, (uint32_t)s, rng_word_pack(r.x, r.saved_avail), __float_as_uint(r.saved));
     park[2 * slot + 1] = make_uint4(__float_as_uint(sum.x), __float_as_uint(sum.y), __float_as_uint(sum.z), 0u);
 }
+
+// ---------------------------------------------------------------- chain buffer (accumulator)
+// rt_accum_* (include/rt_hw.h): a shard's per-pixel chain state kept between renders, one
+// Parked record per shard pixel, indexed by the pixel: (pixel, next sample, start state of that
+// sample, sum of the samples before it).  A pass to absolute sample `spp` is the usual
+// schedule, except that a pixel starts from its record instead of its seed (mega_assign_chain,
+// spec_convert_chain) and that the lane adding the pixel's sample spp - 1 stores the record
+// back, with the state that sample ended in (the three pixel-done sites: mega_shade,
+// spec_job_end, spec_manage phase A).  The samples of a pixel still run in order from the
+// carried state and add to the carried sum in order, so passes of any sizes give the bits of
+// one render of their total.  The buffer's address rides in the kernel's queue block (word
+// kChainWord), read where it is used, like the park list's: no kernel argument, no register
+// held in the loop.  It has a 128-byte line of the block to itself: in the line of the work
+// counters (words 0-7), which every claim of every wave updates atomically, the two reads per
+// pixel queued behind those atomics and a pass of 8 samples over the headline frame took 90 ms
+// against 34 ms for the one-shot render of 8 samples (16: 131 against 67; 64: 265 against
+// 262); in its own line 34 and 67 ms.  CHAIN variants are their own instantiations
+// (rt_mega_kernel).
+constexpr int kChainWord = 16;
+__device__ __forceinline__ uint4 *chain_of(const unsigned long long *queue) { return (uint4 *)queue[kChainWord]; }
+__device__ __forceinline__ void chain_store(uint4 *chain, uint32_t pix, uint32_t s, const Rng &r, V3 sum) {
+    park_pixel(chain, (long long)pix, (int)pix, (int)s, r, sum);
+}
+// A fresh record: nothing rendered yet (rt_accum_create).
+__device__ __forceinline__ void chain_init(uint4 *chain, const DevScene &sc, const ShardGeom &g, int p) {
+    chain_store(chain, (uint32_t)p, 0u, pixel_seed(sc, g, p), V3{0.f, 0.f, 0.f});
+}
+// A pixel claimed from the queue: its next sample from its record, onto its record's sum.
+template <bool COUNT, class ML>
+__device__ __forceinline__ void mega_assign_chain(ML &L, const DevScene &sc, const ShardGeom &g, int p,
+                                                  const NodeRec &root, Counters &cnt, const uint4 *chain) {
+    const Parked q = parked(chain, p);
+    L.pix = p;
+    lane_ctr_set(L, LaneCtr{(int)q.s, 0, 0});
+    lane_sum_set(L, q.sum);
+    L.work0 = cnt.aabb + cnt.tri + cnt.laabb + cnt.ltri;
+    lane_rng_set(L, q.x);
+    mega_sample<COUNT>(L, sc, g, root, cnt);
+}
 // Shade the lane's closest hit (one vertex of scene.cpp:85-154); bounce, or end the path:
 // fold, accumulate, next sample or pixel done.
 // Set when a lane of the wave added its sample itself (spec_job_end): its pixel may take
@@ -299,19 +338,23 @@ inline bool spec_hint_take() {
 
 // End of a runahead job's sample (speculative runahead, below): adds it and starts the next
 // sample on this lane when no other job of its pixel is in flight, else waits (M_DONE_NEW).
-template <class ML>
+// CHAIN (here and below): the accumulator's instantiations; `queue` is the kernel's queue block
+// (rt_mega.h chain_of), only read by them.
+template <bool CHAIN = false, class ML>
 __device__ void spec_job_end(ML &L, const DevScene &sc, const ShardGeom &g, const WfState &st, int spp,
-                             float *out, const NodeRec &root, V3 color, LaneCtr c);
+                             float *out, const NodeRec &root, V3 color, LaneCtr c,
+                             const unsigned long long *queue = nullptr);
 
 // `tail` (wave-uniform): the wave runs runahead jobs (spec_manage below); a job's path end
 // goes to spec_job_end instead of the pixel sum in the lane.
 // `park` (wave-uniform; lane-resident kernel, hand-off): a path end that leaves the pixel
 // unfinished stops there (idle, still holding the pixel, for park_pixel) instead of starting
 // its next sample.
-template <bool COUNT, bool FAST = false, class Stack, class ML>
+template <bool COUNT, bool FAST = false, bool CHAIN = false, class Stack, class ML>
 __device__ __forceinline__ void mega_shade(ML &L, const DevScene &sc, const ShardGeom &g, const WfState &st,
                                            int spp, float *out, unsigned *cost, const NodeRec &root, Stack &stk,
-                                           Counters &cnt, bool tail = false, bool park = false) {
+                                           Counters &cnt, bool tail = false, bool park = false,
+                                           const unsigned long long *queue = nullptr) {
     LaneRec P{st.rec_ab, st.rec_c, mega_slot_of(L), st.lanes, V3{0.f, 0.f, 0.f}, 0, false};
     Hit h = L.T.best;
     LaneCtr c = lane_ctr(L);
@@ -342,7 +385,7 @@ __device__ __forceinline__ void mega_shade(ML &L, const DevScene &sc, const Shar
         return;
     }
     if (!COUNT && !FAST && tail) {   // runahead job: colour of sample c.s, end state in the RNG slot
-        spec_job_end(L, sc, g, st, spp, out, root, fold_path(P, c.nv, shaded), c);
+        spec_job_end<CHAIN>(L, sc, g, st, spp, out, root, fold_path(P, c.nv, shaded), c, queue);
         return;
     }
     const V3 sm = rtv::add(lane_sum(L), fold_path(P, c.nv, !FAST && shaded));
@@ -353,6 +396,9 @@ __device__ __forceinline__ void mega_shade(ML &L, const DevScene &sc, const Shar
         out[3 * o + 1] = sm.y;
         out[3 * o + 2] = sm.z;
         if (COUNT && cost) cost[L.pix] = (unsigned)(cnt.aabb + cnt.tri + cnt.laabb + cnt.ltri - L.work0);
+        // (accumulator: the record of the pixel's next pass; the lane's RNG is at the state its
+        // last sample ended in)
+        if constexpr (CHAIN && !FAST) chain_store(chain_of(queue), (uint32_t)L.pix, (uint32_t)c.s, lane_rng(L), sm);
         L.pix = -1;
         L.state = M_IDLE;
         return;
@@ -498,11 +544,12 @@ __device__ __forceinline__ void mega_shade_split(ML &L, const DevScene &sc, cons
 
 // One iteration of a wave's main loop for one lane, given the wave's decision: shade the
 // READY lanes this iteration (shade_now), or step the traversing lanes.
-template <bool COUNT, class Stack, class Nodes, bool FAST = false, bool LSPLIT = false, class ML>
+template <bool COUNT, class Stack, class Nodes, bool FAST = false, bool LSPLIT = false, bool CHAIN = false, class ML>
 __device__ __forceinline__ void mega_iterate(ML &L, bool shade_now, const DevScene &sc, const ShardGeom &g,
                                              const WfState &st, int spp, float *out, unsigned *cost,
                                              const NodeRec &root, Stack &stk, const Nodes &nodes, Counters &cnt,
-                                             bool tail = false, bool park = false) {
+                                             bool tail = false, bool park = false,
+                                             const unsigned long long *queue = nullptr) {
     if constexpr (LSPLIT) {
         if (shade_now) {
             if (L.state == M_READY || L.state == M_LREADY)
@@ -515,7 +562,8 @@ __device__ __forceinline__ void mega_iterate(ML &L, bool shade_now, const DevSce
         }
     }
     if (shade_now) {
-        if (L.state == M_READY) mega_shade<COUNT, FAST>(L, sc, g, st, spp, out, cost, root, stk, cnt, tail, park);
+        if (L.state == M_READY)
+            mega_shade<COUNT, FAST, CHAIN>(L, sc, g, st, spp, out, cost, root, stk, cnt, tail, park, queue);
     } else if (L.state == M_TRAV) {
         if (trav_step<COUNT>(sc, L.r, L.T, stk, nodes, cnt)) L.state = M_READY;
     }
@@ -806,6 +854,22 @@ __device__ __forceinline__ void spec_convert(MegaLane &L, const DevScene &sc, co
     }
 }
 
+// Accumulator: a pixel still at the sample its record names (its pass's first) has X_f in the
+// record, so its runahead can begin at once, as from a seed.  (The record is only rewritten
+// when the pixel's pass ends, and a pixel converted here has not ended.)
+__device__ __forceinline__ void spec_convert_chain(MegaLane &L, const DevScene &sc, const ShardGeom &g,
+                                                   const SpecView &V, int lane, const uint4 *chain, bool xk = false,
+                                                   Rng Xk = Rng{0u, 0u, 0.f}) {
+    if (L.pix >= 0 && !xk) {
+        const Parked q = parked(chain, L.pix);
+        if ((uint32_t)lane_ctr(L).s == q.s) {
+            xk = true;
+            Xk = q.x;
+        }
+    }
+    spec_convert(L, sc, g, V, lane, xk, Xk);
+}
+
 // Start job (record r, sample t, epoch e) on this lane from state Y.
 template <class ML>
 __device__ __forceinline__ void spec_start(ML &L, const DevScene &sc, const ShardGeom &g, const NodeRec &root,
@@ -824,9 +888,10 @@ __device__ __forceinline__ void spec_start(ML &L, const DevScene &sc, const Shar
 // waits for the next pass with its colour in the lane's sum slot.  Only this lane holds a job
 // of the pixel in the first case, and passes never overlap a shading step, so the record
 // update is this lane's alone.
-template <class ML>
+template <bool CHAIN, class ML>
 __device__ __forceinline__ void spec_job_end(ML &L, const DevScene &sc, const ShardGeom &g, const WfState &st,
-                                             int spp, float *out, const NodeRec &root, V3 color, LaneCtr c) {
+                                             int spp, float *out, const NodeRec &root, V3 color, LaneCtr c,
+                                             const unsigned long long *queue) {
     const int lane = (int)(mega_slot() & 63);
     const SpecView V{(uint4 *)st.mid, st.lanes, mega_slot() - lane};
     const uint4 j = *V.w(4, lane);
@@ -843,6 +908,7 @@ __device__ __forceinline__ void spec_job_end(ML &L, const DevScene &sc, const Sh
             out[o + 0] = sum.x;
             out[o + 1] = sum.y;
             out[o + 2] = sum.z;
+            if constexpr (CHAIN) chain_store(chain_of(queue), a.x, t + 1u, E, sum);   // (E: the state sample t ended in)
             *V.w(0, r) = make_uint4(a.x, t + 1u, t + 1u, a.w);
             *V.w(1, r) = v3_pack(sum, 0u);
             RT_SPEC_CHAIN_END(spp, a.x);
@@ -877,6 +943,9 @@ __device__ __forceinline__ void spec_job_end(ML &L, const DevScene &sc, const Sh
 // every pixel without one, then runahead jobs in record order: at the tail's start, lane
 // order is heaviest first, rt_order_spread_kernel).  Returns whether a record can still take
 // a job (the wave calls again when a lane is idle).
+// (CHAIN: claim.queue is word 3 of the kernel's queue block, so the chain buffer's address is
+// kChainWord - 3 words past it.)
+template <bool CHAIN = false>
 __device__ __forceinline__ bool spec_manage(SpecLanes lanes, const DevScene &sc, const ShardGeom &g,
                                             const SpecView &V, int spp, float *out, const NodeRec &root,
                                             SpecClaim &claim) {
@@ -947,6 +1016,8 @@ __device__ __forceinline__ bool spec_manage(SpecLanes lanes, const DevScene &sc,
                     out[o + 0] = sum.x;
                     out[o + 1] = sum.y;
                     out[o + 2] = sum.z;
+                    if constexpr (CHAIN)   // (e0: the state sample f - 1 ended in)
+                        chain_store((uint4 *)claim.queue[kChainWord - 3], rp.get(lane), f, e0, sum);
                     mm = 0u;
                     RT_SPEC_CHAIN_END(spp, rp.get(lane));
                 }
