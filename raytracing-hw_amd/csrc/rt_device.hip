@@ -12,6 +12,11 @@
 // owned rows; the bits do not depend on the kernel, the launch shape, the pixel order or the
 // partition.
 //
+// Host side of a render (launch(), below): rt_launch_plan.h decides what is launched (kernel
+// instantiation, schedule, grid; host only, tested without a GPU), rt_mega.h QueueWord names
+// the words of the queue block the host and the kernels share, and rt_mega_prof.h holds the
+// diagnostics build's counters and report (included under RT_MEGA_PROF only).
+//
 // Concurrency: one render per (scene, device) may be in flight at a time (the pixel queue,
 // counters, vertex records and order buffers of a device copy are shared by its launches);
 // renders of the same scene on different devices are independent (rt_render_multi).
@@ -35,6 +40,7 @@
 #include "rt_quant_lut.h"
 #include "rt_scene.h"
 #include "rt_bvh_layout.h"
+#include "rt_launch_plan.h"
 
 using rtd::Counters;
 using rtd::DevScene;
@@ -110,19 +116,12 @@ constexpr int kCoopLeavesSpec = RT_SPEC_COOP_LEAVES;   // the runahead kernel's 
 constexpr bool kSpecMaskLoad = RT_SPEC_MASK_LOAD != 0;
 // Leaf rounds per coop step (rt_wavefront.h trav_step_coop round_min): a further round
 // while at least this many leaf lanes are unserved.  Plain kernel: 8 (sponza 1080p 1292 ->
-// 1278 ms against one round per step).  Runahead kernel: 4 on scenes of fewer than
-// kCoopRoundNodes BVH nodes, where most traversal steps are leaf steps (cornell 512x512x64,
-// 36 triangles: 26.8 -> 16.7 ms), one round per step on larger ones (the 8-way sponza
-// shards: 1% slower with rounds) (profiles/r03_ab.jsonl r03q-s).
+// 1278 ms against one round per step).  The runahead kernel's depends on the scene
+// (rt_launch_plan.h kCoopRoundMinSpec, kCoopRoundNodes).
 #ifndef RT_COOP_ROUND_MIN
 #define RT_COOP_ROUND_MIN 8
 #endif
-#ifndef RT_SPEC_COOP_ROUND_MIN
-#define RT_SPEC_COOP_ROUND_MIN 4
-#endif
 constexpr int kCoopRoundMinPlain = RT_COOP_ROUND_MIN;
-constexpr int kCoopRoundMinSpec = RT_SPEC_COOP_ROUND_MIN;   // small scenes
-constexpr int kCoopRoundNodes = 4096;
 // Pixel order pre-pass (launch_order).  Compile-time only, for A/B builds (make variant).
 // Measured on sponza 1080p x256spp (tools/order_ab.py, profiles/r02_order_ab.jsonl): 1 spp and
 // a 9 x 9 box filter (1399 ms, pre-pass 6.8 ms) against row-major order (1436 ms), 2 spp
@@ -138,51 +137,9 @@ constexpr int kCoopRoundNodes = 4096;
 #endif
 constexpr int kOrderSpp = RT_ORDER_SPP;       // samples per pixel of the counting pre-pass
 constexpr int kOrderRadius = RT_ORDER_RADIUS;  // box filter of the pre-pass costs ((2r+1)^2 pixels)
-// The pre-pass and sort cost about one sample per pixel, so below kOrderMinSpp the order
-// is not built unless asked for (RT_FLAG_HEAVY_ORDER): row-major measured faster there
-// (profiles/r02_configs.jsonl: C1 256x256x4 4.5 vs 5.0 ms, C2 512x512x64 17.7 vs 18.0 ms, C5
-// 3840x2160 at 16 spp 378 vs 397 ms; at 256 spp the order wins, C3 748 vs 779 ms, headline
-// 1357 vs 1393 ms).
-constexpr int kOrderMinSpp = 128;
-constexpr int kFastMaxChunks = 128;  // fast mode: at most this many work units per pixel
-// Round 3 (runahead window 3): up to 2 pixels per lane, so the 4-way shards of the headline
-// (2 per lane) use it too: slowest 4-way shard 347.5 vs 358.7 ms; at 4 per lane (2-way)
-// 636 vs 625 (profiles/r03_ab.jsonl r03ah24).
-#ifndef RT_SPEC_PIXELS_PER_LANE
-#define RT_SPEC_PIXELS_PER_LANE 2
-#endif
-constexpr long long kSpecPixelsPerLane = RT_SPEC_PIXELS_PER_LANE;   // runahead kernel up to this many pixels per lane
-// Hand-off (round 6): a parity render on the plain kernel (more than kSpecPixelsPerLane pixels
-// per lane) ends its tail in the runahead kernel.  A plain wave whose queue is empty parks its
-// pixels once fewer than kHandoffBelow of its lanes hold one (each at its next sample end, with
-// its RNG state and sum), and a runahead launch over the whole resident grid resumes them
-// (kHandoffPct percent dealt at its start, the rest claimed in the tail): the plain kernel's
-// sparse tail waves, where most lanes idle while a few pixels finish their chains, become
-// runahead records.  Headline frame 1048.3 vs 1061.5 ms on one box, 2-way shards 578.6 vs
-// 580.6 ms, same bits; parking at 48 / 60 held pixels 1049.0 / 1050.8 ms, 70% dealt 1050.2 ms
-// (profiles/r06g_handoff_ab.jsonl).  RT_FLAG_NO_RUNAHEAD turns it off with the runahead.
-#ifndef RT_HANDOFF_BELOW
-#define RT_HANDOFF_BELOW 56
-#endif
-#ifndef RT_HANDOFF_PCT
-#define RT_HANDOFF_PCT 100
-#endif
-// RT_HANDOFF_SPREAD: the runahead launch deals the parked pixels with the most work left
-// ((samples left) x (pre-pass estimate)) one per wave, instead of in park-list slot order,
-// where a plain wave's consecutive claims (the last pixels of the order, those that end the
-// frame) sit together and share one wave's idle lanes.
-#ifndef RT_HANDOFF_SPREAD
-#define RT_HANDOFF_SPREAD 1
-#endif
-constexpr int kHandoffBelow = RT_HANDOFF_BELOW;
-constexpr int kHandoffPct = RT_HANDOFF_PCT;
-constexpr bool kHandoffSpread = RT_HANDOFF_SPREAD != 0;
-// Diagnostics (A/B builds only): only every k-th lane of a wave claims pixels, so a wave
-// holds at most 64 / k pixels and the grid grows k-fold (lockstep study).
-#ifndef RT_CLAIM_STRIDE
-#define RT_CLAIM_STRIDE 1
-#endif
-constexpr int kClaimStride = RT_CLAIM_STRIDE;
+// The schedule rules' constants (order threshold, fast chunks, runahead and hand-off limits,
+// claim stride) are rt_launch_plan.h's; the kernel itself reads the claim stride.
+using rtp::kClaimStride;
 constexpr int kWfRefill = 8;         // wavefront extend: idle lanes before a wave refills
 constexpr unsigned kWfChunk = 64;    // wavefront extend: queue entries claimed per atomic
 constexpr double kWfCompactBelow = 0.75;   // wavefront: dense queue until this active fraction
@@ -197,11 +154,8 @@ struct rt_device_scene {
     int device = -1;
     void *buf = nullptr;               // one allocation holding every scene array
     DevScene ds{};
-    unsigned long long *counters = nullptr;  // 16 x u64: [0, 8) the render, [8, 16) the order pre-pass
-    unsigned long long *queue = nullptr;     // 32 x u64: [0, 8) work counters of the render and the pre-pass,
-                                             // the hand-off's park count (u32), its runahead launch's claims and
-                                             // the address of its park list (rt_mega_kernel `mode`); [16] the
-                                             // accumulator's chain buffer (rt_mega.h kChainWord: its own line)
+    unsigned long long *counters = nullptr;  // rtd::kCounterWords x u64: the render's, then the order pre-pass's (kOrderCounters)
+    unsigned long long *queue = nullptr;     // the queue block: rtd::kQueueWords x u64 (rt_mega.h QueueWord)
     int cu_count = 0;
     // vertex records (lane-resident) / path state and queues (wavefront)
     void *wf_buf = nullptr;
@@ -313,39 +267,7 @@ __global__ void __launch_bounds__(256) rt_finish_kernel(const float *sum, long l
 // rt_mega.h: every lane runs whole pixels; traversal one unit per iteration, shading batched
 // per wave (READY lanes wait for kShadeMin of them or for no lane left traversing).
 #ifdef RT_MEGA_PROF
-// Diagnostics build (make prof): per-wave clock64() split of the main loop.
-// [0] shade-iteration cycles [1] traversal-iteration cycles [2] pixel-assign cycles
-// [3] shade iterations [4] traversal iterations [5] sum of ready lanes over shade iterations
-// [6] sum of traversing lanes over traversal iterations [7] waves
-__device__ unsigned long long g_mega_prof[8];
-__device__ unsigned long long g_mega_seg[8];   // shading segments (rt_path.h RT_PROF_SEG)
-// per-wave start and end (wall_clock64, 100 MHz): the distribution of wave finish times
-constexpr int kProfWaves = 16384;
-__device__ unsigned long long g_wave_t[2 * kProfWaves];
-__device__ unsigned int g_wave_n;
-// time buckets of 5 ms (wall clock since the wave's start; the waves of a launch start within
-// microseconds of each other): [0] traversal iterations [1] traversing lanes summed over them
-// [2] lanes holding work (state != idle) summed over them [3] shading passes [4] READY lanes
-// summed over them [5] management passes (runahead kernel)
-constexpr int kTb = 256, kTbN = 6;
-constexpr unsigned long long kTbTicks = 500000;   // 5 ms at 100 MHz
-__device__ unsigned long long g_tb[kTb * kTbN];
-struct TbAcc {
-    int b = 0;
-    unsigned long long c[kTbN] = {0, 0, 0, 0, 0, 0};
-    __device__ void at(unsigned long long t0) {   // (every lane; lane 0 flushes)
-        const unsigned long long e = (wall_clock64() - t0) / kTbTicks;
-        const int nb = e < (unsigned long long)kTb ? (int)e : kTb - 1;
-        if (nb != b) flush(nb);
-    }
-    __device__ void flush(int nb) {
-        if ((threadIdx.x & 63) == 0)
-            for (int k = 0; k < kTbN; ++k)
-                if (c[k]) atomicAdd(&g_tb[b * kTbN + k], c[k]);
-        for (int k = 0; k < kTbN; ++k) c[k] = 0;
-        b = nb;
-    }
-};
+#include "rt_mega_prof.h"   // diagnostics build (make prof): its counters, TbAcc and report
 #endif
 // FAST (RT_FLAG_FAST): queue items are (chunk, pixel) work units of `cs`
 // samples with per-sample Philox seeds; `out` is then the chunk-major partial buffer that
@@ -361,17 +283,19 @@ struct TbAcc {
 // kernel is short of SGPRs, which spill into VGPRs):
 //   bits 0-7   park_below > 0 (plain kernel): a wave whose queue is empty and that holds fewer
 //              than park_below pixels parks them, each at its next sample end, in the park list
-//              at its lane slot (rt_mega.h park_pixel; the list's address in queue[4], read where
-//              used: no register held in the loop);
+//              at its lane slot (rt_mega.h park_pixel; the list's address in the queue block,
+//              read where used: no register held in the loop);
 //   bits 8-15  resume_pct > 0 (SPEC): the items are that park list's slots (st.n of them); wave
 //              w of the grid takes slots [w * per, (w + 1) * per), its lanes below per one each
 //              (per: resume_pct percent of the slots over the grid's waves, at most 64), skips
 //              the empty ones and enters its tail at once; the slots past the grid's share are
-//              claimed in the tail (rt_mega.h SpecClaim) through the counter at queue + 3.
+//              claimed in the tail (rt_mega.h SpecClaim) through the resume claim counter.
+// `queue` is the queue block (rt_mega.h QueueWord names its words); the pre-pass gets the
+// address of its own claim counter instead.
 // CHAIN (rt_accum_add; parity renders without counting, plain and runahead kernels only): the
 // pass of an accumulator.  `spp` is the absolute sample the pass ends at; a pixel starts from its
 // record in the chain buffer and the lane that adds its last sample stores the record back
-// (rt_mega.h, chain buffer; the buffer's address in queue[16], read where used).  Separate
+// (rt_mega.h, chain buffer; the buffer's address in the queue block, read where used).  Separate
 // instantiations again: the one-shot kernels are the code they were.
 template <bool COUNT, bool FAST = false, bool LSPLIT = false, bool SPEC = false, bool CHAIN = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SPEC ? kMegaWpeSpec : kMegaWpe, 8)))
@@ -380,7 +304,7 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
     constexpr bool kSpec = SPEC && !COUNT && !FAST && !LSPLIT;
     constexpr bool kChain = CHAIN && !COUNT && !FAST && !LSPLIT;
     const int park_below = mode & 255, resume_pct = (mode >> 8) & 255;
-    const uint4 *resume = kSpec && resume_pct > 0 ? (const uint4 *)queue[4] : nullptr;
+    const uint4 *resume = kSpec && resume_pct > 0 ? (const uint4 *)queue[rtd::kQueueParkList] : nullptr;
     const long long n_items = FAST ? g.n_pixels * (long long)((spp + cs - 1) / cs) : (kSpec && resume) ? st.n : g.n_pixels;
     const int lane = threadIdx.x & 63;
     // sRGB texel-decode table in LDS: the shading's lane-dependent lookups become ds_reads (the
@@ -431,8 +355,9 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
 #endif
     // hand-off resume: the slots past waves * per are taken in the tail (rt_mega.h SpecClaim) by
     // waves below `per` active records
-    // (the resume map's address in queue[5], 0 = slot order: read where used)
-    rtd::SpecClaim claim{queue + 3, 0, n_items, resume, 0, false, resume ? (const int *)queue[5] : nullptr};
+    // (the resume map's address, 0 = slot order: read where used)
+    rtd::SpecClaim claim{queue + rtd::kQueueResume, 0, n_items, resume, 0, false,
+                         resume ? (const int *)queue[rtd::kQueueResumeMap] : nullptr};
     bool park = false;   // (plain kernel, hand-off: this wave parks its pixels)
     if constexpr (kSpec) {
         if (resume) {
@@ -488,7 +413,7 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
 #endif
         if (!kSpec && !COUNT && !FAST && park) {   // hand-off: lanes idle with a pixel park it
             if (L.state == rtd::M_IDLE && L.pix >= 0) {
-                rtd::park_pixel((uint4 *)queue[4], rtd::mega_slot_of(L), L.pix, rtd::lane_ctr(L).s, rtd::lane_rng(L),
+                rtd::park_pixel((uint4 *)queue[rtd::kQueueParkList], rtd::mega_slot_of(L), L.pix, rtd::lane_ctr(L).s, rtd::lane_rng(L),
                                 rtd::lane_sum(L));
                 L.pix = -1;
             }
@@ -502,7 +427,7 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
                 // claiming lanes below this one (mbcnt of the ballot: no per-lane mask held)
                 const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
                 unsigned long long base = 0;
-                if (need && below == 0) base = atomicAdd(queue, (unsigned long long)cm);   // the leader
+                if (need && below == 0) base = atomicAdd(queue + rtd::kQueueRender, (unsigned long long)cm);   // the leader
                 base = __shfl(base, leader, 64);
                 if (need) {
                     const long long p = (long long)base + below;
@@ -1023,8 +948,8 @@ int ensure_device_scene(rt_scene *s, int device) {
     d->device = device;
     hipError_t e = hipMalloc(&d->buf, b.bytes.size());
     if (e == hipSuccess) e = hipMemcpy(d->buf, b.bytes.data(), b.bytes.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&d->counters, 16 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc((void **)&d->queue, 32 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc((void **)&d->counters, rtd::kCounterWords * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc((void **)&d->queue, rtd::kQueueWords * sizeof(unsigned long long));
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
     if (e != hipSuccess) {
@@ -1091,9 +1016,9 @@ int ensure_wf(rt_device_scene *d, long long n, int D) {
     w.rec_c = take(D);
     w.mid = (float4 *)take(20);   // 5 planes of float4, stride = lane slots (<= cap)
     {   // the hand-off's park list (32 B per lane slot) is the first ray queue (48 B per slot, unused
-        // by the lane-resident kernels); its address goes where the kernel reads it (queue[4])
+        // by the lane-resident kernels); its address goes where the kernel reads it
         const unsigned long long park = (unsigned long long)(uintptr_t)d->wf_queue[0];
-        HIP_TRY(hipMemcpy(d->queue + 4, &park, sizeof park, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d->queue + rtd::kQueueParkList, &park, sizeof park, hipMemcpyHostToDevice));
     }
     d->wf_cap = cap;
     d->wf_D = D;
@@ -1199,6 +1124,47 @@ int launch_wavefront(rt_device_scene *d, const ShardGeom &g, int spp, int depth,
     return RT_OK;
 }
 
+// The rt_mega_kernel instantiation of a variant (rt_launch_plan.h): the nine that exist share
+// one signature.  The counting fast-mode kernel is also the order pre-pass; a pass of an
+// accumulator (chain) runs the CHAIN form of the runahead or the plain kernel.
+using MegaKernel = void (*)(DevScene, ShardGeom, rtd::WfState, int, float *, unsigned long long *, unsigned long long *,
+                            const int *, unsigned *, int, int);
+// (Defined after launch_order: the compiler emits the instantiations where they are first named,
+// and there the device listing keeps the kernel order of the builds before the selector, so
+// the two diff clean.)
+MegaKernel mega_kernel_of(const rtp::Variant &v);
+
+// The order buffer of a device copy (d->order_buf): five arrays of one 4-byte entry per shard
+// pixel, each 256-byte aligned, then the radix sort's scratch.  launch_order fills them: the
+// pre-pass costs (box-filtered through cost_sorted, back into cost), their descending sort
+// (cost_sorted, ids -> sorted) and the spread into `order`, which the main launch reads.
+// The hand-off's second sort runs after the main launch, when `order` and everything but the
+// filtered costs is dead, and reuses the arrays: cost stays the estimate it sorts by, its keys
+// go to cost_sorted and their sorted copy over `order`, ids / sorted hold the park-list slots,
+// and the resume map takes the keys' array once they are sorted.
+struct OrderBuf {
+    unsigned *cost, *cost_sorted;
+    int *ids, *sorted, *order;
+    void *tmp;
+    // the hand-off's names for the arrays it reuses
+    unsigned *park_keys, *park_keys_sorted;
+    int *resume_map;
+    static size_t array_bytes(long long n) { return (((size_t)n * 4 + 255) / 256) * 256; }
+    static size_t bytes(long long n, size_t tmp_bytes) { return 5 * array_bytes(n) + tmp_bytes; }
+    OrderBuf(void *base, long long n_pixels) {
+        uint8_t *b = (uint8_t *)base;
+        const size_t arr = array_bytes(n_pixels);
+        cost = (unsigned *)b;
+        cost_sorted = park_keys = (unsigned *)(b + arr);
+        ids = (int *)(b + 2 * arr);
+        sorted = (int *)(b + 3 * arr);
+        order = (int *)(b + 4 * arr);
+        tmp = b + 5 * arr;
+        park_keys_sorted = (unsigned *)order;
+        resume_map = (int *)park_keys;
+    }
+};
+
 // Heaviest-first, spread pixel order for a parity-mode render of shard g, built inside the
 // frame: a counting fast-mode pre-pass of kOrderSpp samples per pixel measures each pixel's
 // traversal work (its own Philox streams: the pre-pass never touches the render's RNG), a
@@ -1207,45 +1173,52 @@ int launch_wavefront(rt_device_scene *d, const ShardGeom &g, int spp, int depth,
 // `groups` waves.  Results never depend on the order; it only shortens the
 // frame's tail.  Returns the order in d_order.
 int launch_order(rt_device_scene *d, const ShardGeom &g, hipStream_t stream, long long groups, long long per,
-                 int **d_order) {
+                 const int **d_order) {
     const long long n = g.n_pixels;
-    // order buffer: cost, cost sorted, ids, ids sorted, order (n each), then the sort's scratch
     size_t tmp_bytes = 0;
     HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tmp_bytes, (unsigned *)nullptr, (unsigned *)nullptr,
                                                          (int *)nullptr, (int *)nullptr, (int)n, 0, 32, stream));
-    const size_t arr = (((size_t)n * 4 + 255) / 256) * 256;
-    HIP_TRY(grow(&d->order_buf, &d->order_bytes, 5 * arr + tmp_bytes));
-    uint8_t *b = (uint8_t *)d->order_buf;
-    unsigned *cost = (unsigned *)b, *cost_sorted = (unsigned *)(b + arr);
-    int *ids = (int *)(b + 2 * arr), *sorted = (int *)(b + 3 * arr), *order = (int *)(b + 4 * arr);
-    void *tmp = b + 5 * arr;
+    HIP_TRY(grow(&d->order_buf, &d->order_bytes, OrderBuf::bytes(n, tmp_bytes)));
+    const OrderBuf ob(d->order_buf, n);
     HIP_TRY(grow((void **)&d->fast_part, &d->fast_part_bytes, (size_t)n * 3 * sizeof(float)));
-    HIP_TRY(hipMemsetAsync(d->queue + 1, 0, sizeof(unsigned long long), stream));
-    auto pre = rt_mega_kernel<true, true>;
+    HIP_TRY(hipMemsetAsync(d->queue + rtd::kQueueOrder, 0, sizeof(unsigned long long), stream));
+    rtp::Variant counting_fast;
+    counting_fast.count = counting_fast.fast = true;
+    const MegaKernel pre = mega_kernel_of(counting_fast);
     const unsigned blocks = persistent_blocks(d, pre, n);   // <= ceil(n / 256): lane slots fit the workspace
     rtd::WfState w = d->wf;
     w.n = n;
     w.lanes = (long long)blocks * 256;
     hipLaunchKernelGGL(pre, dim3(blocks), dim3(256), 0, stream, d->ds, g, w, kOrderSpp, d->fast_part,
-                       d->counters + 8, d->queue + 1, (const int *)nullptr, cost, kOrderSpp, 0);
+                       d->counters + rtd::kOrderCounters, d->queue + rtd::kQueueOrder, (const int *)nullptr, ob.cost,
+                       kOrderSpp, 0);
     HIP_TRY(hipGetLastError());
     const unsigned nb = (unsigned)((n + 255) / 256);
     if (kOrderRadius > 0) {   // box-filtered costs: the pixel's neighbourhood estimates its expected work
-        hipLaunchKernelGGL(rt_order_box_kernel, dim3(nb), dim3(256), 0, stream, (const unsigned *)cost, cost_sorted, n,
+        hipLaunchKernelGGL(rt_order_box_kernel, dim3(nb), dim3(256), 0, stream, (const unsigned *)ob.cost, ob.cost_sorted, n,
                            g.width, kOrderRadius, 0);
-        hipLaunchKernelGGL(rt_order_box_kernel, dim3(nb), dim3(256), 0, stream, (const unsigned *)cost_sorted, cost, n,
+        hipLaunchKernelGGL(rt_order_box_kernel, dim3(nb), dim3(256), 0, stream, (const unsigned *)ob.cost_sorted, ob.cost, n,
                            g.width, kOrderRadius, 1);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(rt_order_iota_kernel, dim3(nb), dim3(256), 0, stream, ids, n);
+    hipLaunchKernelGGL(rt_order_iota_kernel, dim3(nb), dim3(256), 0, stream, ob.ids, n);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(tmp, tmp_bytes, cost, cost_sorted, ids, sorted, (int)n, 0, 32,
-                                                         stream));
-    hipLaunchKernelGGL(rt_order_spread_kernel, dim3(nb), dim3(256), 0, stream, (const int *)sorted, order, n, groups,
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(ob.tmp, tmp_bytes, ob.cost, ob.cost_sorted, ob.ids, ob.sorted, (int)n,
+                                                         0, 32, stream));
+    hipLaunchKernelGGL(rt_order_spread_kernel, dim3(nb), dim3(256), 0, stream, (const int *)ob.sorted, ob.order, n, groups,
                        per);
     HIP_TRY(hipGetLastError());
-    *d_order = order;
+    *d_order = ob.order;
     return RT_OK;
+}
+
+MegaKernel mega_kernel_of(const rtp::Variant &v) {
+    if (v.count && v.fast) return rt_mega_kernel<true, true>;
+    if (v.spec) return v.chain ? rt_mega_kernel<false, false, false, true, true> : rt_mega_kernel<false, false, false, true>;
+    if (v.fast) return rt_mega_kernel<false, true>;
+    if (v.lsplit) return v.count ? rt_mega_kernel<true, false, true> : rt_mega_kernel<false, false, true>;
+    if (!v.count && !v.chain) return rt_mega_kernel<false>;   // the plain kernel
+    return v.count ? rt_mega_kernel<true> : rt_mega_kernel<false, false, false, false, true>;
 }
 
 // Flag bits outside RT_FLAG_ALL (e.g. ABI 5's RT_FLAG_POOL) are an error, not ignored.
@@ -1255,334 +1228,214 @@ int check_flags(const rt_params *p, const char *who) {
     return RT_OK;
 }
 
+// The shard (p->rank of p->world, in blocks of p->row_block rows) of the scene's frame, with
+// the defaults filled in (world 1, row_block 8).
+int norm_world(const rt_params *p) { return p->world > 0 ? p->world : 1; }
+int norm_row_block(const rt_params *p) { return p->row_block > 0 ? p->row_block : 8; }
+struct Shard {
+    int world = 1, row_block = 8, rows = 0;
+    long long n_pixels = 0;
+    ShardGeom g{};
+};
+int shard_of(const rt_scene *s, const rt_params *p, const char *who, Shard &sh) {
+    if ((int64_t)s->width * s->height > INT32_MAX)
+        return rt_fail(RT_ERR_LIMIT, std::string(who) + ": frames above 2^31 pixels are not supported");
+    sh.world = norm_world(p);
+    sh.row_block = norm_row_block(p);
+    const int64_t rows = rt_shard_rows_impl(s->height, p->rank, sh.world, sh.row_block, nullptr);
+    if (rows < 0) return RT_ERR_ARG;
+    sh.rows = (int)rows;
+    sh.n_pixels = (long long)rows * s->width;
+    sh.g = rtd::shard_geom(s->width, p->rank, sh.world, sh.row_block, sh.n_pixels);
+    return RT_OK;
+}
+
 // An accumulator's pass (rt_accum_add): the chain buffer and the samples the pass adds.  The
 // render's spp is then the absolute sample the pass ends at; the pixel order and the stats go
-// by the pass's own sample count.
+// by the pass's own sample count (rt_launch_plan.h PlanIn.pass_spp).
 struct ChainPass {
     uint4 *chain;
     int n;
 };
+
+// One word of the queue block, written in stream order.
+int set_queue_word(rt_device_scene *d, int word, const void *address, hipStream_t stream) {
+    hipLaunchKernelGGL(rt_set_u64_kernel, dim3(1), dim3(1), 0, stream, d->queue + word,
+                       (unsigned long long)(uintptr_t)address);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// Hand-off, after the plain kernel's launch: the parked pixels, on the runahead kernel `rk`
+// over its whole resident grid.  With the pixel order's estimates at hand (gr.spread2) the
+// park-list slots go heaviest first (work left), spread one per wave of that grid
+// (RT_HANDOFF_SPREAD); else in slot order.  `w`: the main launch's workspace view.
+int launch_handoff(rt_device_scene *d, const ShardGeom &g, const rtp::Grid &gr, MegaKernel rk, rtd::WfState w, int spp,
+                   float *k_out, hipStream_t stream) {
+    const long long slots = gr.slots;
+    const int *map = nullptr;
+    if (gr.spread2) {
+        const OrderBuf ob(d->order_buf, g.n_pixels);   // (slots <= n_pixels: the arrays hold them)
+        size_t tmp_bytes = 0;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tmp_bytes, (unsigned *)nullptr, (unsigned *)nullptr,
+                                                             (int *)nullptr, (int *)nullptr, (int)slots, 0, 32, stream));
+        const unsigned nbs = (unsigned)((slots + 255) / 256);
+        hipLaunchKernelGGL(rt_park_keys_kernel, dim3(nbs), dim3(256), 0, stream, (const uint4 *)d->wf_queue[0], slots, spp,
+                           (const unsigned *)ob.cost, ob.park_keys, ob.ids);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(ob.tmp, tmp_bytes, ob.park_keys, ob.park_keys_sorted, ob.ids,
+                                                             ob.sorted, (int)slots, 0, 32, stream));
+        // (the runahead launch's static deal: per2 slots to each of its waves, as in the kernel)
+        hipLaunchKernelGGL(rt_order_spread_kernel, dim3(nbs), dim3(256), 0, stream, (const int *)ob.sorted, ob.resume_map,
+                           slots, gr.waves2, gr.per2);
+        HIP_TRY(hipGetLastError());
+        map = ob.resume_map;
+    }
+    if (int rc = set_queue_word(d, rtd::kQueueResumeMap, map, stream)) return rc;
+    w.lanes = gr.blocks2 * 256;
+    w.n = slots;   // the park list's slots
+    hipLaunchKernelGGL(rk, dim3((unsigned)gr.blocks2), dim3(256), 0, stream, d->ds, g, w, spp, k_out, d->counters, d->queue,
+                       (const int *)nullptr, (unsigned *)nullptr, 0, rtp::kHandoffPct << 8);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// The events a render with stats records: start, pixel order built, end.
+struct RenderEvents {
+    EventSet set;
+    hipEvent_t start = nullptr, ordered = nullptr, end = nullptr;
+};
+
+// rt_stats of one shard, once its last launch is queued (waits for it).
+int read_stats(rt_device_scene *d, const rtp::Schedule &plan, bool count, RenderEvents &ev, LaunchTimer &timer,
+               hipStream_t stream, rt_stats *st) {
+    HIP_TRY(hipEventRecord(ev.end, stream));
+    HIP_TRY(hipEventSynchronize(ev.end));
+    float ms = 0.f, ms_order = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev.start, ev.end));
+    if (plan.ordered) HIP_TRY(hipEventElapsedTime(&ms_order, ev.start, ev.ordered));
+    std::memset(st, 0, sizeof *st);
+    st->pixels = (uint64_t)plan.n_pixels;
+    st->samples = (uint64_t)plan.n_pixels * (uint64_t)plan.stats_spp;
+    st->render_ms = ms;
+    st->order_ms = ms_order;
+    st->devices = 1;
+    st->schedule = plan.sched;
+    double kms[2];
+    uint64_t kn[2];
+    HIP_TRY(timer.collect(kms, kn));
+    st->extend_ms = kms[0];
+    st->shade_ms = kms[1];
+    st->extend_launches = kn[0];
+    st->shade_launches = kn[1];
+    unsigned long long c[rtd::kOrderCounters];   // the render's counters (rt_wavefront.h counters_flush; [7]: wf_extend_kernel)
+    HIP_TRY(hipMemcpy(c, d->counters, sizeof c, hipMemcpyDeviceToHost));
+    st->extend_rays = c[7];
+    if (count) {
+        st->rays = c[0]; st->aabb_tests = c[1]; st->tri_tests = c[2];
+        st->light_queries = c[3]; st->light_aabb_tests = c[4]; st->light_tri_tests = c[5];
+        st->shading_hits = c[6];
+    }
+    return RT_OK;
+}
 
 // One shard on one device: rt_render_device, and with `cp` a pass of rt_accum_add (the caller
 // has checked that the parameters select a parity render on the lane-resident kernel).  A
 // one-shot render launches exactly what it launched before the accumulator existed.
 int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt_stats *st,
            const ChainPass *cp = nullptr) {
+    // validate and plan (rt_launch_plan.h)
     if (!s || !p || !d_out) return rt_fail(RT_ERR_ARG, "rt_render: NULL argument");
     if (int rc = check_flags(p, "rt_render")) return rc;
     if (p->device < 0 || p->device >= kRtMaxDevices || !s->dev[p->device])
         return rt_fail(RT_ERR_ARG, "rt_render: scene not uploaded to device " + std::to_string(p->device));
-    const int world = p->world > 0 ? p->world : 1, rank = p->rank, rb = p->row_block > 0 ? p->row_block : 8;
-    const int spp = p->spp > 0 ? p->spp : s->samples;
-    if (spp < 1) return rt_fail(RT_ERR_ARG, "rt_render: samples per pixel must be >= 1");
-    if (p->kernel != RT_KERNEL_LANE && p->kernel != RT_KERNEL_WAVEFRONT)
-        return rt_fail(RT_ERR_ARG, "rt_render: unknown kernel " + std::to_string(p->kernel) + " (0 lane-resident, 4 wavefront)");
-    const bool fast = (p->flags & RT_FLAG_FAST) != 0;
-    if ((fast || (p->flags & RT_FLAG_LIGHT_SPLIT)) && p->kernel != RT_KERNEL_LANE)
-        return rt_fail(RT_ERR_ARG, "rt_render: fast mode and the light-split kernel run on kernel 0 only");
-    if (p->fast_chunk < 0) return rt_fail(RT_ERR_ARG, "rt_render: fast_chunk must be >= 0");
-    if ((p->flags & RT_FLAG_NATURAL_ORDER) && (p->flags & RT_FLAG_HEAVY_ORDER))
-        return rt_fail(RT_ERR_ARG, "rt_render: RT_FLAG_NATURAL_ORDER and RT_FLAG_HEAVY_ORDER exclude each other");
-    if ((int64_t)s->width * s->height > INT32_MAX)
-        return rt_fail(RT_ERR_LIMIT, "rt_render: frames above 2^31 pixels are not supported");
-    const int64_t rows = rt_shard_rows_impl(s->height, rank, world, rb, nullptr);
-    if (rows < 0) return RT_ERR_ARG;
-    const ShardGeom g = rtd::shard_geom(s->width, rank, world, rb, (long long)rows * s->width);
+    rtp::PlanIn in;
+    in.flags = p->flags;
+    in.kernel = p->kernel;
+    in.count = p->count;
+    in.fast_chunk = p->fast_chunk;
+    in.spp = p->spp > 0 ? p->spp : s->samples;
+    in.pass_spp = cp ? cp->n : 0;
+    in.ray_depth = s->ray_depth;
+    if (const rtp::Refusal r = rtp::plan_check(in)) return rt_fail(r.code, r.msg);
+    Shard sh;
+    if (int rc = shard_of(s, p, "rt_render", sh)) return rc;
+    const ShardGeom &g = sh.g;
     rt_device_scene *d = s->dev[p->device];
     DeviceGuard guard(d->device);
     if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    in.n_pixels = g.n_pixels;
+    in.n_nodes = d->ds.n_nodes;
+    rtp::Variant runahead;
+    runahead.spec = true;
+    runahead.chain = cp != nullptr;
+    const MegaKernel rk = mega_kernel_of(runahead);   // (the hand-off's relaunch; its grid bounds the runahead shards)
+    if (in.kernel == RT_KERNEL_LANE && g.n_pixels > 0) in.spec_blocks = resident_blocks(d, rk);
+    const rtp::Schedule plan = rtp::plan_schedule(in);
+    if (plan.refused) return rt_fail(plan.refused.code, plan.refused.msg);
+    const MegaKernel mk = mega_kernel_of(plan.v);
+    rtp::Grid grid;
+    if (plan.lane) grid = rtp::plan_grid(plan, resident_blocks(d, mk));
+    if (grid.refused) return rt_fail(grid.refused.code, grid.refused.msg);
+
+    // counters and events
     const bool count = p->count != 0;
-    if (count || st) HIP_TRY(hipMemsetAsync(d->counters, 0, 8 * sizeof(unsigned long long), stream));
+    if (count || st) HIP_TRY(hipMemsetAsync(d->counters, 0, rtd::kOrderCounters * sizeof(unsigned long long), stream));
     LaunchTimer timer;
     timer.on = st != nullptr && (p->flags & RT_FLAG_KERNEL_TIMES) != 0;
-    HIP_TRY(hipMemsetAsync(d->queue, 0, sizeof(unsigned long long), stream));
-    EventSet events;
-    hipEvent_t e0 = nullptr, e_order = nullptr, e1 = nullptr;
+    HIP_TRY(hipMemsetAsync(d->queue + rtd::kQueueRender, 0, sizeof(unsigned long long), stream));
+    RenderEvents ev;
     if (st) {
-        HIP_TRY(events.make(e0));
-        HIP_TRY(events.make(e_order));
-        HIP_TRY(events.make(e1));
-        HIP_TRY(hipEventRecord(e0, stream));
+        HIP_TRY(ev.set.make(ev.start));
+        HIP_TRY(ev.set.make(ev.ordered));
+        HIP_TRY(ev.set.make(ev.end));
+        HIP_TRY(hipEventRecord(ev.start, stream));
     }
-    bool ordered = false;
-    uint64_t sched = 0;   // rt_stats.schedule (RT_SCHED_* bit of the kernel that ran)
-    if (g.n_pixels > 0) {
-        if (p->kernel == RT_KERNEL_WAVEFRONT) {
-            int rc = launch_wavefront(d, g, spp, s->ray_depth, d_out, stream, count, timer);
-            if (rc) return rc;
-            sched = RT_SCHED_WAVEFRONT;
-        } else {   // lane-resident (rt_mega.h), the default
-            if (s->ray_depth < 1 || s->ray_depth > 15) return rt_fail(RT_ERR_LIMIT, "ray_depth must be in [1, 15]");
-            if (spp >= (1 << 20)) return rt_fail(RT_ERR_LIMIT, "rt_render: spp must be < 2^20");
-            // fast mode (RT_FLAG_FAST): work units of `cs` samples, Philox seed per sample, at
-            // most kFastMaxChunks units per pixel (partials: pixels x chunks x 12 B)
-            int cs = 0, chunks = 1;
-            if (fast) {
-                cs = std::min(spp, std::max(p->fast_chunk > 0 ? p->fast_chunk : 2, (spp + kFastMaxChunks - 1) / kFastMaxChunks));
-                chunks = (spp + cs - 1) / cs;
-            }
-            const long long n_items = g.n_pixels * chunks;
-            const bool lsplit = !fast && (p->flags & RT_FLAG_LIGHT_SPLIT) != 0;
-            // Speculative sample runahead (rt_mega.h) where the frame is mostly tail: a shard of
-            // at most kSpecPixelsPerLane pixels per resident lane (the 8-way split of the
-            // headline: 342 -> 304 ms in round 2; at 4-way, 2 pixels per lane, 359 -> 348 ms in round 3).
-            const long long full_blocks = cp ? resident_blocks(d, rt_mega_kernel<false, false, false, true, true>)
-                                             : resident_blocks(d, rt_mega_kernel<false, false, false, true>);
-            const bool spec = !fast && !lsplit && !count && !(p->flags & RT_FLAG_NO_RUNAHEAD) &&
-                              g.n_pixels * kClaimStride <= kSpecPixelsPerLane * full_blocks * 256;
-            auto mk = fast ? (count ? rt_mega_kernel<true, true> : rt_mega_kernel<false, true>)
-                           : lsplit ? (count ? rt_mega_kernel<true, false, true> : rt_mega_kernel<false, false, true>)
-                                    : count ? rt_mega_kernel<true>
-                                            : spec ? rt_mega_kernel<false, false, false, true> : rt_mega_kernel<false>;
-            if (cp) mk = spec ? rt_mega_kernel<false, false, false, true, true> : rt_mega_kernel<false, false, false, false, true>;
-            sched = fast ? RT_SCHED_FAST : lsplit ? RT_SCHED_LIGHT_SPLIT : spec ? RT_SCHED_RUNAHEAD : RT_SCHED_LANE;
-            const bool handoff = !spec && !fast && !lsplit && !count && !(p->flags & RT_FLAG_NO_RUNAHEAD) &&
-                                 kClaimStride == 1;
-            if (handoff) sched |= RT_SCHED_RUNAHEAD;
-            const unsigned blocks = persistent_blocks(d, mk, n_items * kClaimStride);
-            const long long slots = (long long)blocks * 256;   // lane slots
-            // vertex records are addressed with 32-bit byte offsets (rt_path.h LaneRec)
-            if ((unsigned long long)slots * (unsigned long long)s->ray_depth * 32ull >= (1ull << 32))
-                return rt_fail(RT_ERR_LIMIT, "rt_render: vertex records beyond 4 GiB");
-            int rc = ensure_wf(d, std::max<long long>(g.n_pixels, slots), s->ray_depth);   // vertex records
-            if (rc) return rc;
-            rtd::WfState w = d->wf;
-            w.n = g.n_pixels;
-            w.lanes = slots;   // LaneRec slots (<= the workspace capacity)
-            if (handoff) {   // the park list: every slot "nothing parked"; the runahead launch's claim counter
-                HIP_TRY(hipMemsetAsync(d->wf_queue[0], 0xff, (size_t)slots * 32, stream));
-                HIP_TRY(hipMemsetAsync(d->queue + 3, 0, sizeof(unsigned long long), stream));
-            }
-            w.round_min = d->ds.n_nodes < kCoopRoundNodes ? kCoopRoundMinSpec : 65;
-            int *order = nullptr;
-            const int order_spp = cp ? cp->n : spp;   // (a pass is ordered by the rule on its own samples)
-            if (!fast && !(p->flags & RT_FLAG_NATURAL_ORDER) && (order_spp >= kOrderMinSpp || (p->flags & RT_FLAG_HEAVY_ORDER))) {
-                // the spread deals one pixel of every cost stratum to each claim of 64 of the
-                // launch's first round (one per wave)
-                rc = launch_order(d, g, stream, 4LL * blocks, 64, &order);
-                if (rc) return rc;
-                ordered = true;
-            }
-            if (st) HIP_TRY(hipEventRecord(e_order, stream));
-            float *k_out = d_out;
-            if (fast) {
-                HIP_TRY(grow((void **)&d->fast_part, &d->fast_part_bytes, (size_t)n_items * 3 * sizeof(float)));
-                k_out = d->fast_part;
-            }
-#ifdef RT_MEGA_PROF
-            {
-                const unsigned long long z[16] = {};
-                HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mega_prof), z, 8 * sizeof z[0], 0, hipMemcpyHostToDevice, stream));
-                HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mega_seg), z, 8 * sizeof z[0], 0, hipMemcpyHostToDevice, stream));
-                HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(rtd::g_spec_prof), z, sizeof z, 0, hipMemcpyHostToDevice, stream));
-                HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_wave_n), z, sizeof(unsigned), 0, hipMemcpyHostToDevice, stream));
-                HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(rtd::g_chain_n), z, sizeof(unsigned), 0, hipMemcpyHostToDevice, stream));
-                static const std::vector<unsigned long long> ztb(kTb * kTbN, 0ull);
-                HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_tb), ztb.data(), ztb.size() * 8, 0, hipMemcpyHostToDevice, stream));
-            }
-#endif
-            if (cp) {   // the chain buffer's address, where the chain kernels read it
-                hipLaunchKernelGGL(rt_set_u64_kernel, dim3(1), dim3(1), 0, stream, d->queue + rtd::kChainWord,
-                                   (unsigned long long)(uintptr_t)cp->chain);
-                HIP_TRY(hipGetLastError());
-            }
-            hipLaunchKernelGGL(mk, dim3(blocks), dim3(256), 0, stream, d->ds, g, w, spp, k_out, d->counters, d->queue,
-                               (const int *)order, (unsigned *)nullptr, cs, handoff ? kHandoffBelow : 0);
-            HIP_TRY(hipGetLastError());
-            if (handoff) {   // the parked pixels, on the runahead kernel over the whole resident grid
-                // with the pixel order's estimates at hand, the slots heaviest first (work left),
-                // spread one per wave (RT_HANDOFF_SPREAD); else slot order
-                unsigned long long map = 0;
-                if (kHandoffSpread && ordered && slots <= g.n_pixels) {   // (the order buffer holds n_pixels per array)
-                    const size_t arr = (((size_t)g.n_pixels * 4 + 255) / 256) * 256;
-                    uint8_t *b = (uint8_t *)d->order_buf;
-                    const unsigned *est = (const unsigned *)b;   // launch_order's filtered costs
-                    unsigned *keys = (unsigned *)(b + arr), *keys_sorted = (unsigned *)(b + 4 * arr);
-                    int *ids = (int *)(b + 2 * arr), *ids_sorted = (int *)(b + 3 * arr), *map_p = (int *)(b + arr);
-                    void *tmp = b + 5 * arr;
-                    size_t tmp_bytes = 0;
-                    HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tmp_bytes, (unsigned *)nullptr,
-                                                                         (unsigned *)nullptr, (int *)nullptr, (int *)nullptr,
-                                                                         (int)slots, 0, 32, stream));
-                    const unsigned nbs = (unsigned)((slots + 255) / 256);
-                    hipLaunchKernelGGL(rt_park_keys_kernel, dim3(nbs), dim3(256), 0, stream, (const uint4 *)d->wf_queue[0],
-                                       slots, spp, est, keys, ids);
-                    HIP_TRY(hipGetLastError());
-                    HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(tmp, tmp_bytes, keys, keys_sorted, ids, ids_sorted,
-                                                                         (int)slots, 0, 32, stream));
-                    // (the runahead launch's static deal: `per` slots to each of its waves, as in the kernel)
-                    const long long waves2 = 4LL * full_blocks, dealt = (slots * kHandoffPct + 99) / 100;
-                    const long long per2 = std::min<long long>(64, std::max<long long>(1, (dealt + waves2 - 1) / waves2));
-                    hipLaunchKernelGGL(rt_order_spread_kernel, dim3(nbs), dim3(256), 0, stream, (const int *)ids_sorted,
-                                       map_p, slots, waves2, per2);
-                    HIP_TRY(hipGetLastError());
-                    map = (unsigned long long)(uintptr_t)map_p;
-                }
-                hipLaunchKernelGGL(rt_set_u64_kernel, dim3(1), dim3(1), 0, stream, d->queue + 5, map);
-                HIP_TRY(hipGetLastError());
-                rtd::WfState w2 = w;
-                w2.lanes = full_blocks * 256;
-                w2.n = slots;   // the park list's slots
-                auto rk = cp ? rt_mega_kernel<false, false, false, true, true> : rt_mega_kernel<false, false, false, true>;
-                hipLaunchKernelGGL(rk, dim3((unsigned)full_blocks), dim3(256), 0, stream, d->ds, g, w2, spp, k_out,
-                                   d->counters, d->queue, (const int *)nullptr, (unsigned *)nullptr, 0, kHandoffPct << 8);
-                HIP_TRY(hipGetLastError());
-            }
-            if (fast) {
-                const long long n3 = g.n_pixels * 3;
-                hipLaunchKernelGGL(rt_fast_reduce_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, stream,
-                                   (const float *)d->fast_part, d_out, n3, chunks);
-                HIP_TRY(hipGetLastError());
-            }
-#ifdef RT_MEGA_PROF
-            {
-                unsigned long long pf[8];
-                HIP_TRY(hipMemcpyFromSymbolAsync(pf, HIP_SYMBOL(g_mega_prof), sizeof pf, 0, hipMemcpyDeviceToHost, stream));
-                HIP_TRY(hipStreamSynchronize(stream));
-                const double tot = (double)(pf[0] + pf[1] + pf[2]);
-                std::fprintf(stderr,
-                             "[mega prof] count=%d waves=%llu cycles/wave=%.3g shade=%.3f trav=%.3f assign=%.3f "
-                             "shade_iters/wave=%.0f trav_iters/wave=%.0f ready/shade=%.1f trav_lanes/iter=%.1f "
-                             "cyc/shade_iter=%.0f cyc/trav_iter=%.0f\n",
-                             (int)count, pf[7], tot / pf[7], pf[0] / tot, pf[1] / tot, pf[2] / tot,
-                             (double)pf[3] / pf[7], (double)pf[4] / pf[7], (double)pf[5] / pf[3],
-                             (double)pf[6] / pf[4], (double)pf[0] / pf[3], (double)pf[1] / pf[4]);
-                unsigned long long sg[8];
-                HIP_TRY(hipMemcpyFromSymbolAsync(sg, HIP_SYMBOL(g_mega_seg), sizeof sg, 0, hipMemcpyDeviceToHost, stream));
-                HIP_TRY(hipStreamSynchronize(stream));
-                std::fprintf(stderr, "[mega prof] shade segments, cycles per shade iteration: mesh+emission=%.0f "
-                             "normal=%.0f mr=%.0f sample=%.0f pdf=%.0f base+brdf=%.0f\n",
-                             (double)sg[0] / pf[3], (double)sg[1] / pf[3], (double)sg[2] / pf[3],
-                             (double)sg[3] / pf[3], (double)sg[4] / pf[3], (double)sg[5] / pf[3]);
-                {   // wave finish times relative to the first wave start: percentiles (ms)
-                    unsigned nw = 0;
-                    HIP_TRY(hipMemcpyFromSymbolAsync(&nw, HIP_SYMBOL(g_wave_n), sizeof nw, 0, hipMemcpyDeviceToHost, stream));
-                    HIP_TRY(hipStreamSynchronize(stream));
-                    nw = std::min<unsigned>(nw, (unsigned)kProfWaves);
-                    std::vector<unsigned long long> wt(2 * (size_t)nw);
-                    if (nw) HIP_TRY(hipMemcpyFromSymbolAsync(wt.data(), HIP_SYMBOL(g_wave_t), wt.size() * 8, 0, hipMemcpyDeviceToHost, stream));
-                    HIP_TRY(hipStreamSynchronize(stream));
-                    if (nw) {
-                        unsigned long long t0 = ~0ull;
-                        std::vector<double> ends(nw);
-                        for (unsigned i = 0; i < nw; ++i) t0 = std::min(t0, wt[2 * i]);
-                        for (unsigned i = 0; i < nw; ++i) ends[i] = (double)(wt[2 * i + 1] - t0) / 1e5;
-                        std::sort(ends.begin(), ends.end());
-                        std::fprintf(stderr, "[mega prof] wave end ms: p10=%.1f p25=%.1f p50=%.1f p75=%.1f p90=%.1f p99=%.1f max=%.1f\n",
-                                     ends[nw / 10], ends[nw / 4], ends[nw / 2], ends[3 * nw / 4], ends[9 * nw / 10],
-                                     ends[99 * (size_t)nw / 100], ends[nw - 1]);
-                        // per 5-ms bucket: waves alive, traversal iterations per alive wave, lanes per
-                        // iteration (traversing, holding work), shading passes, READY lanes per pass,
-                        // management passes
-                        std::vector<unsigned long long> tbv(kTb * kTbN);
-                        HIP_TRY(hipMemcpyFromSymbolAsync(tbv.data(), HIP_SYMBOL(g_tb), tbv.size() * 8, 0, hipMemcpyDeviceToHost, stream));
-                        HIP_TRY(hipStreamSynchronize(stream));
-                        const int nbk = std::min(kTb, (int)(ends[nw - 1] / 5.0) + 1);
-                        for (int b = 0; b < nbk; ++b) {
-                            double alive = 0;   // wave-buckets alive (fraction of the bucket)
-                            for (unsigned i = 0; i < nw; ++i) {
-                                const double s0 = (double)(wt[2 * i] - t0) / 1e5, e0 = (double)(wt[2 * i + 1] - t0) / 1e5;
-                                const double lo = std::max(s0, 5.0 * b), hi = std::min(e0, 5.0 * (b + 1));
-                                if (hi > lo) alive += (hi - lo) / 5.0;
-                            }
-                            const unsigned long long *c = &tbv[(size_t)b * kTbN];
-                            std::fprintf(stderr, "[mega tb] t=%3d-%3d ms waves=%.0f iters/wave=%.0f trav_lanes=%.1f busy_lanes=%.1f "
-                                         "shades/wave=%.1f ready/shade=%.1f passes/wave=%.1f\n", 5 * b, 5 * b + 5, alive,
-                                         alive > 0 ? c[0] / alive : 0.0, c[0] ? (double)c[1] / c[0] : 0.0,
-                                         c[0] ? (double)c[2] / c[0] : 0.0, alive > 0 ? c[3] / alive : 0.0,
-                                         c[3] ? (double)c[4] / c[3] : 0.0, alive > 0 ? c[5] / alive : 0.0);
-                        }
-                        // the runahead kernel's chain completions: when they end, and where the
-                        // last of them stood in the claim order (0 = the first pixel claimed)
-                        unsigned nc = 0;
-                        HIP_TRY(hipMemcpyFromSymbolAsync(&nc, HIP_SYMBOL(rtd::g_chain_n), sizeof nc, 0, hipMemcpyDeviceToHost, stream));
-                        HIP_TRY(hipStreamSynchronize(stream));
-                        nc = std::min<unsigned>(nc, (unsigned)rtd::kChainRec);
-                        if (nc) {
-                            std::vector<unsigned long long> ct(nc);
-                            std::vector<unsigned> cpx(nc);
-                            HIP_TRY(hipMemcpyFromSymbolAsync(ct.data(), HIP_SYMBOL(rtd::g_chain_t), nc * 8ull, 0, hipMemcpyDeviceToHost, stream));
-                            HIP_TRY(hipMemcpyFromSymbolAsync(cpx.data(), HIP_SYMBOL(rtd::g_chain_pix), nc * 4ull, 0, hipMemcpyDeviceToHost, stream));
-                            const long long np = g.n_pixels;
-                            std::vector<int> rank((size_t)np);
-                            if (order) {
-                                std::vector<int> ord((size_t)np);
-                                HIP_TRY(hipMemcpyAsync(ord.data(), order, (size_t)np * 4, hipMemcpyDeviceToHost, stream));
-                                HIP_TRY(hipStreamSynchronize(stream));
-                                for (long long q = 0; q < np; ++q)
-                                    if (ord[q] >= 0 && ord[q] < np) rank[ord[q]] = (int)q;
-                            } else {
-                                HIP_TRY(hipStreamSynchronize(stream));
-                                for (long long q = 0; q < np; ++q) rank[q] = (int)q;
-                            }
-                            std::vector<unsigned> ix(nc);
-                            for (unsigned q = 0; q < nc; ++q) ix[q] = q;
-                            std::sort(ix.begin(), ix.end(), [&](unsigned a, unsigned b) { return ct[a] < ct[b]; });
-                            auto ms = [&](unsigned q) { return (double)(ct[ix[q]] - t0) / 1e5; };
-                            std::fprintf(stderr, "[mega chains] runahead-kernel chain completions=%u, end ms: p10=%.1f p50=%.1f "
-                                         "p90=%.1f p99=%.1f max=%.1f\n", nc, ms(nc / 10), ms(nc / 2), ms(9 * nc / 10),
-                                         ms((unsigned)(99ull * nc / 100)), ms(nc - 1));
-                            const double fr[4] = {0.5, 0.1, 0.01, 0.001};
-                            for (double f : fr) {
-                                const unsigned k = std::max(1u, (unsigned)(f * nc));
-                                std::vector<double> rr(k);
-                                for (unsigned q = 0; q < k; ++q) {
-                                    const unsigned px = cpx[ix[nc - 1 - q]];
-                                    rr[q] = px < (unsigned)np ? (double)rank[px] / (double)np : -1.0;
-                                }
-                                std::sort(rr.begin(), rr.end());
-                                std::fprintf(stderr, "[mega chains] last %.1f%% (%u chains, from %.1f ms): claim-order position / pixels "
-                                             "p10=%.3f p50=%.3f p90=%.3f\n", 100.0 * f, k, ms(nc - k), rr[k / 10], rr[k / 2],
-                                             rr[9 * k / 10]);
-                            }
-                        }
-                    }
-                }
-                unsigned long long sp[16];
-                HIP_TRY(hipMemcpyFromSymbolAsync(sp, HIP_SYMBOL(rtd::g_spec_prof), sizeof sp, 0, hipMemcpyDeviceToHost, stream));
-                HIP_TRY(hipStreamSynchronize(stream));
-                std::fprintf(stderr, "[mega prof] runahead: tail waves=%llu passes/tail wave=%.1f cycles/pass=%.0f "
-                             "cycles in passes/wave=%.3g frontier jobs=%llu runahead jobs=%llu added=%llu "
-                             "runahead jobs proven=%llu invalidations=%llu\n", sp[7], sp[7] ? (double)sp[0] / sp[7] : 0.0,
-                             sp[0] ? (double)sp[1] / sp[0] : 0.0, (double)sp[1] / pf[7], sp[2], sp[3], sp[4], sp[5], sp[6]);
-                std::fprintf(stderr, "[mega prof] parked pixels claimed in the tail (hand-off): %llu\n", sp[8]);
-                std::fprintf(stderr, "[mega prof] runahead chains: proven share of runahead jobs=%.3f, pixels completed "
-                             "in the tail=%llu, mean time per chain link (completion / spp)=%.1f us\n",
-                             sp[3] ? (double)sp[5] / (double)sp[3] : 0.0, sp[15], sp[15] ? (double)sp[14] / sp[15] / 100.0 : 0.0);
-            }
-#endif
+
+    if (plan.sched == RT_SCHED_WAVEFRONT) {
+        if (int rc = launch_wavefront(d, g, in.spp, s->ray_depth, d_out, stream, count, timer)) return rc;
+    } else if (plan.lane) {   // lane-resident (rt_mega.h), the default
+        if (int rc = ensure_wf(d, std::max<long long>(g.n_pixels, grid.slots), s->ray_depth)) return rc;   // vertex records
+        rtd::WfState w = d->wf;
+        w.n = g.n_pixels;
+        w.lanes = grid.slots;   // LaneRec slots (<= the workspace capacity)
+        w.round_min = plan.round_min;
+        if (plan.handoff) {   // the park list: every slot "nothing parked"; the runahead launch's claim counter
+            HIP_TRY(hipMemsetAsync(d->wf_queue[0], 0xff, (size_t)grid.slots * 32, stream));
+            HIP_TRY(hipMemsetAsync(d->queue + rtd::kQueueResume, 0, sizeof(unsigned long long), stream));
         }
+        const int *order = nullptr;
+        if (plan.ordered)
+            if (int rc = launch_order(d, g, stream, grid.groups, grid.per, &order)) return rc;
+        if (st) HIP_TRY(hipEventRecord(ev.ordered, stream));
+        float *k_out = d_out;
+        if (plan.v.fast) {   // chunk-major partial sums, folded below
+            HIP_TRY(grow((void **)&d->fast_part, &d->fast_part_bytes, (size_t)plan.n_items * 3 * sizeof(float)));
+            k_out = d->fast_part;
+        }
+#ifdef RT_MEGA_PROF
+        if (int rc = mega_prof_reset(stream)) return rc;
+#endif
+        // the chain buffer's address, where the chain kernels read it
+        if (cp)
+            if (int rc = set_queue_word(d, rtd::kChainWord, cp->chain, stream)) return rc;
+        hipLaunchKernelGGL(mk, dim3((unsigned)grid.blocks), dim3(256), 0, stream, d->ds, g, w, in.spp, k_out, d->counters,
+                           d->queue, order, (unsigned *)nullptr, plan.cs, plan.handoff ? rtp::kHandoffBelow : 0);
         HIP_TRY(hipGetLastError());
-    }
-    if (st) {
-        HIP_TRY(hipEventRecord(e1, stream));
-        HIP_TRY(hipEventSynchronize(e1));
-        float ms = 0.f, ms_order = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        if (ordered) HIP_TRY(hipEventElapsedTime(&ms_order, e0, e_order));
-        std::memset(st, 0, sizeof *st);
-        st->pixels = (uint64_t)g.n_pixels;
-        st->samples = (uint64_t)g.n_pixels * (uint64_t)(cp ? cp->n : spp);
-        st->render_ms = ms;
-        st->order_ms = ms_order;
-        st->devices = 1;
-        st->schedule = sched;
-        double kms[2];
-        uint64_t kn[2];
-        HIP_TRY(timer.collect(kms, kn));
-        st->extend_ms = kms[0];
-        st->shade_ms = kms[1];
-        st->extend_launches = kn[0];
-        st->shade_launches = kn[1];
-        unsigned long long c[8];
-        HIP_TRY(hipMemcpy(c, d->counters, sizeof c, hipMemcpyDeviceToHost));
-        st->extend_rays = c[7];
-        if (count) {
-            st->rays = c[0]; st->aabb_tests = c[1]; st->tri_tests = c[2];
-            st->light_queries = c[3]; st->light_aabb_tests = c[4]; st->light_tri_tests = c[5];
-            st->shading_hits = c[6];
+        if (plan.handoff)
+            if (int rc = launch_handoff(d, g, grid, rk, w, in.spp, k_out, stream)) return rc;
+        if (plan.v.fast) {
+            const long long n3 = g.n_pixels * 3;
+            hipLaunchKernelGGL(rt_fast_reduce_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, stream,
+                               (const float *)d->fast_part, d_out, n3, plan.chunks);
+            HIP_TRY(hipGetLastError());
         }
+#ifdef RT_MEGA_PROF
+        if (int rc = mega_prof_report(stream, count, g.n_pixels, order, !grid.spread2)) return rc;
+#endif
     }
+    HIP_TRY(hipGetLastError());
+    if (st) return read_stats(d, plan, count, ev, timer, stream, st);
     return RT_OK;
 }
 
@@ -1590,10 +1443,9 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
 int render_host(rt_scene *s, const rt_params *p, float *out, rt_stats *st) {
     int rc = ensure_device_scene(s, p->device);
     if (rc) return rc;
-    const int world = p->world > 0 ? p->world : 1, rb = p->row_block > 0 ? p->row_block : 8;
-    const int64_t rows = rt_shard_rows_impl(s->height, p->rank, world, rb, nullptr);
-    if (rows < 0) return RT_ERR_ARG;
-    const size_t bytes = (size_t)rows * s->width * 3 * sizeof(float);
+    Shard sh;
+    if ((rc = shard_of(s, p, "rt_render", sh))) return rc;
+    const size_t bytes = (size_t)sh.n_pixels * 3 * sizeof(float);
     DeviceGuard guard(p->device);
     if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
     float *d_out = nullptr;
@@ -1692,6 +1544,7 @@ struct rt_accum {
     rt_params p{};            // rank, world, row_block, device, flags (normalised)
     long long n_pixels = 0;
     int rows = 0;
+    ShardGeom geom{};         // the shard (shard_of)
     int samples = 0;          // samples done
     uint4 *chain = nullptr;   // n_pixels Parked records
     float *sums = nullptr;    // n_pixels x 3
@@ -1752,7 +1605,7 @@ int accum_check_params(const rt_params *p, const char *who) {
     if (p->flags & RT_FLAG_KERNEL_TIMES) return rt_fail(RT_ERR_ARG, w + ": RT_FLAG_KERNEL_TIMES is a wavefront option; accumulators run on kernel 0");
     if (p->count != 0) return rt_fail(RT_ERR_ARG, w + ": counting renders have no accumulator (count must be 0)");
     if (p->kernel != RT_KERNEL_LANE) return rt_fail(RT_ERR_ARG, w + ": accumulators run on the lane-resident kernel only (kernel 0)");
-    if ((p->flags & RT_FLAG_NATURAL_ORDER) && (p->flags & RT_FLAG_HEAVY_ORDER))
+    if (rtp::order_flags_conflict(p->flags))
         return rt_fail(RT_ERR_ARG, w + ": RT_FLAG_NATURAL_ORDER and RT_FLAG_HEAVY_ORDER exclude each other");
     return RT_OK;
 }
@@ -1772,21 +1625,17 @@ void accum_release(rt_accum *a) {
 int accum_new(rt_scene *s, const rt_params *p, const char *who, rt_accum **out) {
     if (int rc = accum_check_params(p, who)) return rc;
     if (p->device < 0 || p->device >= kRtMaxDevices) return rt_fail(RT_ERR_ARG, std::string(who) + ": bad device " + std::to_string(p->device));
-    if ((int64_t)s->width * s->height > INT32_MAX)
-        return rt_fail(RT_ERR_LIMIT, std::string(who) + ": frames above 2^31 pixels are not supported");
+    Shard sh;
+    if (int rc = shard_of(s, p, who, sh)) return rc;
     rt_accum *a = new rt_accum();
     a->scene = s;
     a->p = *p;
     a->p.spp = 0;
-    a->p.world = p->world > 0 ? p->world : 1;
-    a->p.row_block = p->row_block > 0 ? p->row_block : 8;
-    const int64_t rows = rt_shard_rows_impl(s->height, a->p.rank, a->p.world, a->p.row_block, nullptr);
-    if (rows < 0) {
-        delete a;
-        return RT_ERR_ARG;
-    }
-    a->rows = (int)rows;
-    a->n_pixels = (long long)rows * s->width;
+    a->p.world = sh.world;
+    a->p.row_block = sh.row_block;
+    a->rows = sh.rows;
+    a->n_pixels = sh.n_pixels;
+    a->geom = sh.g;
     *out = a;
     return RT_OK;
 }
@@ -1822,9 +1671,8 @@ int rt_accum_create(rt_scene *s, const rt_params *p, rt_accum **out) {
     int rc = accum_alloc(a);
     if (rc == RT_OK && a->n_pixels > 0) {
         DeviceGuard guard(a->p.device);
-        const ShardGeom g = rtd::shard_geom(s->width, a->p.rank, a->p.world, a->p.row_block, a->n_pixels);
         hipLaunchKernelGGL(rt_chain_init_kernel, dim3((unsigned)((a->n_pixels + 255) / 256)), dim3(256), 0, nullptr,
-                           s->dev[a->p.device]->ds, g, a->chain, a->sums);
+                           s->dev[a->p.device]->ds, a->geom, a->chain, a->sums);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
         if (e != hipSuccess) rc = rt_fail(RT_ERR_DEVICE, std::string("rt_accum_create: ") + hipGetErrorString(e));
@@ -2038,7 +1886,7 @@ int rt_render_frame(rt_scene *s, const rt_params *p, int32_t n_shards, const int
     if (spp < 1) return rt_fail(RT_ERR_ARG, "rt_render_frame: samples per pixel must be >= 1");
     int rc = ensure_blob(s);   // built once here, copied to every device
     if (rc) return rc;
-    const int rb = p->row_block > 0 ? p->row_block : 8, W = s->width, H = s->height;
+    const int rb = norm_row_block(p), W = s->width, H = s->height;
     const int root = dev_of[0];
     // staging on the root: shard r's rows at row offset base[r]; frame_row_of[staging row]
     std::vector<int64_t> rows(n), base(n + 1, 0);

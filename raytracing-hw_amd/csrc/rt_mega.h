@@ -292,7 +292,24 @@ __device__ __forceinline__ void park_pixel(uint4 *park, long long slot, int pix,
 // against 34 ms for the one-shot render of 8 samples (16: 131 against 67; 64: 265 against
 // 262); in its own line 34 and 67 ms.  CHAIN variants are their own instantiations
 // (rt_mega_kernel).
-constexpr int kChainWord = 16;
+// The queue block: kQueueWords 64-bit words per device copy of a scene, shared by the host
+// (rt_device.hip) and the kernels.  A render launch's `queue` argument is the block; the
+// counting pre-pass is handed block + kQueueOrder as its `queue`, claims there and touches no
+// other word.
+enum QueueWord : int {
+    kQueueRender = 0,     // claim counter of the render's main launch (zeroed per render)
+    kQueueOrder = 1,      // claim counter of the order pre-pass
+    kQueueParkCount = 2,  // the hand-off's park count (u32); the park list is indexed by lane slot
+                          // (park_pixel), so no code reads or writes this word
+    kQueueResume = 3,     // claim counter of the hand-off's runahead launch (SpecClaim)
+    kQueueParkList = 4,   // address of the park list (written when the workspace is made)
+    kQueueResumeMap = 5,  // address of the resume launch's item -> slot map, 0 = slot order
+    kChainWord = 16,      // address of the accumulator's chain buffer (its own 128-byte line)
+    kQueueWords = 32,
+};
+// The counter block (rt_wavefront.h Counters as 64-bit words, counters_flush): the render's at
+// [0, kOrderCounters), the order pre-pass's from kOrderCounters.
+constexpr int kOrderCounters = 8, kCounterWords = 16;
 __device__ __forceinline__ uint4 *chain_of(const unsigned long long *queue) { return (uint4 *)queue[kChainWord]; }
 __device__ __forceinline__ void chain_store(uint4 *chain, uint32_t pix, uint32_t s, const Rng &r, V3 sum) {
     park_pixel(chain, (long long)pix, (int)pix, (int)s, r, sum);
@@ -943,8 +960,8 @@ __device__ __forceinline__ void spec_job_end(ML &L, const DevScene &sc, const Sh
 // every pixel without one, then runahead jobs in record order: at the tail's start, lane
 // order is heaviest first, rt_order_spread_kernel).  Returns whether a record can still take
 // a job (the wave calls again when a lane is idle).
-// (CHAIN: claim.queue is word 3 of the kernel's queue block, so the chain buffer's address is
-// kChainWord - 3 words past it.)
+// (CHAIN: claim.queue is word kQueueResume of the kernel's queue block, so the chain buffer's
+// address is kChainWord - kQueueResume words past it.)
 template <bool CHAIN = false>
 __device__ __forceinline__ bool spec_manage(SpecLanes lanes, const DevScene &sc, const ShardGeom &g,
                                             const SpecView &V, int spp, float *out, const NodeRec &root,
@@ -1017,7 +1034,7 @@ __device__ __forceinline__ bool spec_manage(SpecLanes lanes, const DevScene &sc,
                     out[o + 1] = sum.y;
                     out[o + 2] = sum.z;
                     if constexpr (CHAIN)   // (e0: the state sample f - 1 ended in)
-                        chain_store((uint4 *)claim.queue[kChainWord - 3], rp.get(lane), f, e0, sum);
+                        chain_store((uint4 *)claim.queue[kChainWord - kQueueResume], rp.get(lane), f, e0, sum);
                     mm = 0u;
                     RT_SPEC_CHAIN_END(spp, rp.get(lane));
                 }

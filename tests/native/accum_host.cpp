@@ -3,8 +3,8 @@
 // rt_device.hip makes them: a claimed pixel starts from its record (mega_assign_chain), a wave
 // entering its tail takes X_f from the record (spec_convert_chain), and the three pixel-done
 // sites store the record back (mega_shade, spec_job_end, spec_manage, all with CHAIN = true).
-// The queue block is the kernel's: word 3 the resume launch's claim counter, word kChainWord the
-// chain buffer's address.
+// The queue block is the kernel's (rt_mega.h QueueWord): kQueueRender the render's claim counter,
+// kQueueResume the resume launch's, kChainWord the chain buffer's address.
 #include "kernel_host.cpp"
 
 template <bool SPEC>
@@ -38,10 +38,10 @@ static int render_mega_chain(const rt_scene_view *v, int spp, int rank, int worl
     for (auto &L : lanes) { L.pix = -1; L.state = rtd::M_IDLE; }
     std::vector<char> exhausted(waves, 0), done(waves, 0), tail(waves, 0), wave_room(waves, 0);
     rtd::Counters cnt{0, 0, 0, 0, 0, 0, 0};
-    unsigned long long qblock[32] = {};
+    unsigned long long qblock[rtd::kQueueWords] = {};
     qblock[rtd::kChainWord] = (unsigned long long)(uintptr_t)chain;
-    unsigned long long &queue = qblock[0];
-    rtd::SpecClaim claim{qblock + 3, 0, 0, nullptr, 0, false, nullptr};
+    unsigned long long &queue = qblock[rtd::kQueueRender];
+    rtd::SpecClaim claim{qblock + rtd::kQueueResume, 0, 0, nullptr, 0, false, nullptr};
     const bool parking = !SPEC && g_park_below > 0, resuming = SPEC && g_resume_pct > 0;
     std::vector<char> park(waves, 0);
     if (parking) g_park_list.assign((size_t)2 * waves * 64, make_uint4(rtd::kNoPark, rtd::kNoPark, rtd::kNoPark, rtd::kNoPark));
@@ -53,7 +53,7 @@ static int render_mega_chain(const rt_scene_view *v, int spp, int rank, int worl
         res_n = (long long)g_park_list.size() / 2;
         const long long dealt = (res_n * g_resume_pct + 99) / 100;
         res_per = (int)std::min<long long>(64, std::max<long long>(1, (dealt + waves - 1) / waves));
-        claim = rtd::SpecClaim{qblock + 3, (long long)waves * res_per, res_n, g_park_list.data(), res_per,
+        claim = rtd::SpecClaim{qblock + rtd::kQueueResume, (long long)waves * res_per, res_n, g_park_list.data(), res_per,
                                (long long)waves * res_per < res_n, nullptr};
     }
     int live = waves;

@@ -1,0 +1,173 @@
+"""The render's launch plan without a GPU (raytracing-hw_amd/csrc/rt_launch_plan.h behind
+tests/native/plan_host.cpp): which kernel instantiation, schedule, work units, pixel order and
+grid launch() chooses, and what it refuses.  Resident block counts are inputs: 1280 for the
+plain kernel and 1024 for the runahead kernel (256 CUs at 5 and 4 blocks)."""
+import ctypes
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "native", "plan_host.cpp")
+PLAIN_BLOCKS, SPEC_BLOCKS = 1280, 1024
+LANE, RUNAHEAD, FAST, LIGHT_SPLIT, WAVEFRONT = 1, 2, 4, 8, 16          # RT_SCHED_*
+F_FAST, F_LSPLIT, F_NATURAL, F_NO_RUNAHEAD, F_HEAVY = 2, 4, 8, 16, 32   # RT_FLAG_*
+ERR_ARG, ERR_LIMIT = -1, -5
+HD = 1920 * 1080
+
+
+class In(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("flags", "kernel", "count", "fast_chunk", "spp", "pass_spp")] + \
+               [("n_pixels", ctypes.c_longlong), ("ray_depth", ctypes.c_int), ("n_nodes", ctypes.c_int),
+                ("spec_blocks", ctypes.c_longlong), ("variant_blocks", ctypes.c_longlong)]
+
+
+class Out(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("err", "lane", "v_count", "v_fast", "v_lsplit", "v_spec", "v_chain")] + \
+               [("sched", ctypes.c_ulonglong)] + \
+               [(n, ctypes.c_int) for n in ("handoff", "ordered", "cs", "chunks")] + \
+               [("n_items", ctypes.c_longlong), ("round_min", ctypes.c_int), ("stats_spp", ctypes.c_int)] + \
+               [(n, ctypes.c_longlong) for n in ("blocks", "slots", "groups", "per", "blocks2", "waves2", "dealt", "per2")] + \
+               [("spread2", ctypes.c_int), ("msg", ctypes.c_char * 192)]
+
+
+@pytest.fixture(scope="module")
+def ph(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("ph") / "libph.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-shared", "-fPIC", SRC, "-o", out], check=True)
+    lib = ctypes.CDLL(out)
+    lib.ph_plan.argtypes = [ctypes.POINTER(In), ctypes.POINTER(Out)]
+    lib.ph_plan.restype = ctypes.c_int
+
+    def plan(n_pixels=HD, spp=256, variant_blocks=None, **kw):
+        i = In(flags=0, kernel=0, count=0, fast_chunk=0, spp=spp, pass_spp=0, n_pixels=n_pixels, ray_depth=8,
+               n_nodes=100000, spec_blocks=SPEC_BLOCKS, variant_blocks=0)
+        for k, v in kw.items():
+            setattr(i, k, v)
+        o = Out()
+        if variant_blocks is None:   # the chosen kernel's: a first call tells which one that is
+            lib.ph_plan(ctypes.byref(i), ctypes.byref(o))
+            variant_blocks = SPEC_BLOCKS if o.v_spec else PLAIN_BLOCKS
+        i.variant_blocks = variant_blocks
+        rc = lib.ph_plan(ctypes.byref(i), ctypes.byref(o))
+        assert rc == o.err
+        return o
+    return plan
+
+
+def test_headline_frame_is_plain_kernel_with_handoff(ph):
+    o = ph(HD)
+    assert HD == 2073600
+    assert o.err == 0 and o.lane == 1
+    assert (o.v_count, o.v_fast, o.v_lsplit, o.v_spec, o.v_chain) == (0, 0, 0, 0, 0)
+    assert o.sched == LANE | RUNAHEAD and o.handoff == 1
+    assert (o.blocks, o.slots) == (1280, 327680)
+    assert o.ordered == 1 and (o.groups, o.per) == (5120, 64)
+    assert (o.cs, o.chunks, o.n_items) == (0, 1, HD)
+    assert o.stats_spp == 256
+
+
+@pytest.mark.parametrize("n_pixels,spec", [
+    (HD // 2, False),        # world 2: 1,036,800
+    (HD // 4, True),         # world 4: 518,400
+    (1024 * 512, True),      # 2 pixels per resident lane of the runahead kernel: the boundary
+    (1024 * 513, False)])
+def test_runahead_up_to_two_pixels_per_lane_then_handoff(ph, n_pixels, spec):
+    o = ph(n_pixels)
+    assert o.err == 0 and o.v_spec == int(spec) and o.handoff == int(not spec)
+    assert o.sched == (RUNAHEAD if spec else LANE | RUNAHEAD)
+    if spec:
+        assert o.blocks == 1024 and o.blocks2 == 0
+    if n_pixels == HD // 4:
+        assert n_pixels == 518400
+
+
+def test_handoff_relaunch_deal_is_the_kernels_resume_formula(ph):
+    # rt_mega_kernel's resume site: waves of the grid, dealt = ceil(items * pct / 100),
+    # per = min(64, max(1, ceil(dealt / waves))), with RT_HANDOFF_PCT 100
+    for blocks in (PLAIN_BLOCKS, 100, 3):
+        o = ph(600000, variant_blocks=blocks)
+        slots = blocks * 256
+        waves = 4 * SPEC_BLOCKS
+        assert o.handoff == 1 and (o.blocks, o.slots) == (blocks, slots)
+        assert (o.blocks2, o.waves2, o.dealt) == (SPEC_BLOCKS, waves, slots)
+        assert o.per2 == min(64, max(1, -(-slots // waves)))
+        assert o.spread2 == 1   # ordered, and the order buffer's arrays hold the slots
+    assert [ph(600000, variant_blocks=b).per2 for b in (PLAIN_BLOCKS, 100, 3)] == [64, 7, 1]
+    assert ph(600000, flags=F_NATURAL).spread2 == 0   # no estimates: slot order
+
+
+def test_other_schedules(ph):
+    for kw in (dict(count=1), dict(flags=F_NO_RUNAHEAD)):
+        for n in (HD, HD // 8):
+            o = ph(n, **kw)
+            assert o.err == 0 and o.sched == LANE and o.handoff == 0 and o.v_spec == 0
+            assert o.v_count == kw.get("count", 0)
+    for count in (0, 1):
+        o = ph(HD, flags=F_LSPLIT, count=count)
+        assert o.sched == LIGHT_SPLIT and (o.v_lsplit, o.v_count, o.v_spec, o.handoff) == (1, count, 0, 0)
+    o = ph(HD, kernel=4)
+    assert o.err == 0 and o.sched == WAVEFRONT and o.lane == 0
+    o = ph(0)   # a rank without rows launches nothing
+    assert o.err == 0 and o.sched == 0 and o.lane == 0
+    o = ph(HD // 8, count=1)
+    assert o.blocks == min(PLAIN_BLOCKS, -(-(HD // 8) // 256))
+
+
+@pytest.mark.parametrize("spp,fast_chunk,cs,chunks", [(256, 0, 2, 128), (1024, 0, 8, 128), (3, 0, 2, 2), (1, 0, 1, 1),
+                                                      (256, 16, 16, 16)])
+def test_fast_mode_work_units(ph, spp, fast_chunk, cs, chunks):
+    for flags in (F_FAST, F_FAST | F_HEAVY, F_FAST | F_LSPLIT):
+        o = ph(HD // 8, spp=spp, flags=flags, fast_chunk=fast_chunk)
+        assert o.err == 0 and o.sched == FAST and o.ordered == 0
+        assert (o.v_fast, o.v_lsplit, o.v_spec, o.handoff) == (1, 0, 0, 0)
+        assert (o.cs, o.chunks, o.n_items) == (cs, chunks, (HD // 8) * chunks)
+        assert o.blocks == min(PLAIN_BLOCKS, -(-o.n_items // 256))
+
+
+def test_ordering_rule(ph):
+    assert ph(spp=127).ordered == 0 and ph(spp=128).ordered == 1
+    assert ph(spp=4, flags=F_HEAVY).ordered == 1
+    assert ph(spp=256, flags=F_NATURAL).ordered == 0
+    # a pass is ordered by its own samples, and counted by them
+    o = ph(spp=256, pass_spp=64)
+    assert o.ordered == 0 and o.stats_spp == 64
+    o = ph(spp=256, pass_spp=128)
+    assert o.ordered == 1 and o.stats_spp == 128
+
+
+def test_round_min_by_scene_size(ph):
+    assert ph(n_nodes=4095).round_min == 4
+    assert ph(n_nodes=4096).round_min == 65
+
+
+def test_pass_variants_keep_the_one_shot_schedule(ph):
+    for n in (HD, HD // 8):
+        one, p = ph(n), ph(n, pass_spp=8)
+        assert p.v_chain == 1 and one.v_chain == 0
+        assert (p.v_spec, p.sched, p.handoff, p.blocks, p.slots) == (one.v_spec, one.sched, one.handoff, one.blocks, one.slots)
+        assert (p.v_count, p.v_fast, p.v_lsplit) == (0, 0, 0)
+
+
+@pytest.mark.parametrize("kw,code,text", [
+    (dict(kernel=3), ERR_ARG, "rt_render: unknown kernel 3 (0 lane-resident, 4 wavefront)"),
+    (dict(spp=0), ERR_ARG, "rt_render: samples per pixel must be >= 1"),
+    (dict(spp=1 << 20), ERR_LIMIT, "rt_render: spp must be < 2^20"),
+    (dict(ray_depth=0), ERR_LIMIT, "ray_depth must be in [1, 15]"),
+    (dict(ray_depth=16), ERR_LIMIT, "ray_depth must be in [1, 15]"),
+    (dict(kernel=4, flags=F_FAST), ERR_ARG, "rt_render: fast mode and the light-split kernel run on kernel 0 only"),
+    (dict(kernel=4, flags=F_LSPLIT), ERR_ARG, "rt_render: fast mode and the light-split kernel run on kernel 0 only"),
+    (dict(fast_chunk=-1), ERR_ARG, "rt_render: fast_chunk must be >= 0"),
+    (dict(flags=F_NATURAL | F_HEAVY), ERR_ARG, "rt_render: RT_FLAG_NATURAL_ORDER and RT_FLAG_HEAVY_ORDER exclude each other"),
+    (dict(n_pixels=40000 * 256, ray_depth=15, variant_blocks=40000), ERR_LIMIT, "rt_render: vertex records beyond 4 GiB")])
+def test_refusals(ph, kw, code, text):
+    o = ph(**kw)
+    assert o.err == code and o.msg.decode() == text
+
+
+def test_limits_just_inside(ph):
+    assert ph(spp=(1 << 20) - 1).err == 0 and ph(ray_depth=1).err == 0 and ph(ray_depth=15).err == 0
+    # 2^32 / (256 * 15 * 32) = 34952.5 blocks
+    assert ph(n_pixels=40000 * 256, ray_depth=15, variant_blocks=34952).err == 0
+    assert ph(n_pixels=40000 * 256, ray_depth=15, variant_blocks=34953).err == ERR_LIMIT
