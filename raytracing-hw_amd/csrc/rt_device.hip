@@ -15,7 +15,9 @@
 // Host side of a render (launch(), below): rt_launch_plan.h decides what is launched (kernel
 // instantiation, schedule, grid; host only, tested without a GPU), rt_mega.h QueueWord names
 // the words of the queue block the host and the kernels share, and rt_mega_prof.h holds the
-// diagnostics build's counters and report (included under RT_MEGA_PROF only).
+// diagnostics build's counters and report (included under RT_MEGA_PROF only).  The whole-frame
+// render (rt_render_frame) takes its devices, row partition and buffer layout from
+// rt_frame_plan.h (host only as well).
 //
 // Concurrency: one render per (scene, device) may be in flight at a time (the pixel queue,
 // counters, vertex records and order buffers of a device copy are shared by its launches);
@@ -41,6 +43,7 @@
 #include "rt_scene.h"
 #include "rt_bvh_layout.h"
 #include "rt_launch_plan.h"
+#include "rt_frame_plan.h"
 
 using rtd::Counters;
 using rtd::DevScene;
@@ -172,17 +175,19 @@ struct rt_device_scene {
     // pixel order of the current render (heaviest first, spread; see launch_order)
     void *order_buf = nullptr;
     size_t order_bytes = 0;
-    // rt_render_frame, kept between frames: the device's render and copy streams, two shard
+    // rt_render_frame's, kept between frames: the device's render and copy streams, two shard
     // buffers (float sums then 8-bit rows) and the events that order their reuse; on the root
-    // device also the staging / frame buffers and the row map (FrameRoot)
-    hipStream_t fr_stream = nullptr, cp_stream = nullptr;
-    void *fr_buf[2] = {nullptr, nullptr};
-    size_t fr_bytes[2] = {0, 0};
-    hipEvent_t fr_copied[2] = {nullptr, nullptr};   // copy of buffer b done (reuse after it)
-    hipEvent_t fr_finished = nullptr;               // shard finished to 8 bits (copy may start)
-    hipEvent_t fr_last = nullptr;                   // the device's last copy of the frame done
-    void *root_buf = nullptr;
-    size_t root_bytes = 0;
+    // device also the root buffer: staging, frame and row map (sizes and offsets: rt_frame_plan.h)
+    struct Frame {
+        hipStream_t stream = nullptr, cp_stream = nullptr;
+        void *buf[2] = {nullptr, nullptr};
+        size_t bytes[2] = {0, 0};
+        hipEvent_t copied[2] = {nullptr, nullptr};   // copy of buffer b done (reuse after it)
+        hipEvent_t finished = nullptr;               // shard finished to 8 bits (copy may start)
+        hipEvent_t last = nullptr;                   // the device's last copy of the frame done
+        void *root_buf = nullptr;
+        size_t root_bytes = 0;
+    } fr;
 };
 
 #define HIP_TRY(expr)                                                                          \
@@ -833,7 +838,7 @@ namespace {
 
 template <class T>
 size_t append(std::vector<uint8_t> &blob, const std::vector<T> &v, size_t pre = 0) {
-    size_t off = ((blob.size() + 255) & ~size_t(255)) + pre;
+    size_t off = rtp::align_up(blob.size()) + pre;
     blob.resize(off + v.size() * sizeof(T));
     if (!v.empty()) std::memcpy(blob.data() + off, v.data(), v.size() * sizeof(T));
     return off;
@@ -900,7 +905,7 @@ int ensure_blob(rt_scene *s) {
     std::vector<float> lut(512);
     rtd::fill_decode_lut(lut.data());
     b->o_lut = append(blob, lut);
-    blob.resize(((blob.size() + 255) & ~size_t(255)) + 256);
+    blob.resize(rtp::align_up(blob.size()) + 256);
     s->blob = b;
     return RT_OK;
 }
@@ -909,15 +914,15 @@ void free_device_scene(rt_device_scene *d) {
     if (!d) return;
     DeviceGuard guard(d->device);
     if (guard.ok) {
-        for (hipStream_t q : {d->fr_stream, d->cp_stream})
+        for (hipStream_t q : {d->fr.stream, d->fr.cp_stream})
             if (q) (void)hipStreamSynchronize(q);
         for (void *p : {d->buf, (void *)d->counters, (void *)d->queue, d->wf_buf, (void *)d->wf_count,
-                        (void *)d->wf_fetch, (void *)d->fast_part, d->order_buf, d->fr_buf[0], d->fr_buf[1], d->root_buf})
+                        (void *)d->wf_fetch, (void *)d->fast_part, d->order_buf, d->fr.buf[0], d->fr.buf[1], d->fr.root_buf})
             if (p) (void)hipFree(p);
         if (d->wf_host_count) (void)hipHostFree(d->wf_host_count);
-        for (hipEvent_t e : {d->fr_copied[0], d->fr_copied[1], d->fr_finished, d->fr_last})
+        for (hipEvent_t e : {d->fr.copied[0], d->fr.copied[1], d->fr.finished, d->fr.last})
             if (e) (void)hipEventDestroy(e);
-        for (hipStream_t q : {d->fr_stream, d->cp_stream})
+        for (hipStream_t q : {d->fr.stream, d->fr.cp_stream})
             if (q) (void)hipStreamDestroy(q);
     }
     delete d;
@@ -926,9 +931,9 @@ void free_device_scene(rt_device_scene *d) {
 // rt_render_frame's per-device streams and events (created once per device copy).
 hipError_t ensure_frame_streams(rt_device_scene *d) {
     hipError_t e = hipSuccess;
-    if (!d->fr_stream) e = hipStreamCreateWithFlags(&d->fr_stream, hipStreamNonBlocking);
-    if (e == hipSuccess && !d->cp_stream) e = hipStreamCreateWithFlags(&d->cp_stream, hipStreamNonBlocking);
-    for (hipEvent_t *ev : {&d->fr_copied[0], &d->fr_copied[1], &d->fr_finished, &d->fr_last})
+    if (!d->fr.stream) e = hipStreamCreateWithFlags(&d->fr.stream, hipStreamNonBlocking);
+    if (e == hipSuccess && !d->fr.cp_stream) e = hipStreamCreateWithFlags(&d->fr.cp_stream, hipStreamNonBlocking);
+    for (hipEvent_t *ev : {&d->fr.copied[0], &d->fr.copied[1], &d->fr.finished, &d->fr.last})
         if (e == hipSuccess && !*ev) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
     return e;
 }
@@ -1149,7 +1154,7 @@ struct OrderBuf {
     // the hand-off's names for the arrays it reuses
     unsigned *park_keys, *park_keys_sorted;
     int *resume_map;
-    static size_t array_bytes(long long n) { return (((size_t)n * 4 + 255) / 256) * 256; }
+    static size_t array_bytes(long long n) { return rtp::align_up((size_t)n * 4); }
     static size_t bytes(long long n, size_t tmp_bytes) { return 5 * array_bytes(n) + tmp_bytes; }
     OrderBuf(void *base, long long n_pixels) {
         uint8_t *b = (uint8_t *)base;
@@ -1852,79 +1857,45 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
 
 void rt_accum_free(rt_accum *a) { accum_release(a); }
 
+}  // extern "C"
+
 // The whole frame as shards 0 .. n-1 of a (world n, row_block) split, shard r on device
-// devices[r] (include/rt_hw.h rt_render_frame).  One host thread per distinct device renders
-// that device's shards one after another (one render per (scene, device) in flight), finishes
-// each to 8 bits on the same device (rt_finish_kernel, scene.cpp:54-64) and copies it, 8-bit
-// frame and (if asked) float sums, device-to-device into a staging buffer on the root device
-// devices[0] (hipMemcpyPeerAsync: over xGMI between MI355X) on a copy stream of its own, so
-// the copy of one shard overlaps the render of the device's next one.  The root then places
-// the rows in frame order (rt_rows_scatter_kernel; the reference's canvas, canvas.h:76-89, is
-// row-major) behind an event wait per device, and the frame leaves the devices in one copy per
-// output.  Streams, events and buffers are kept in the scene's device copies between frames.
+// devices[r] (include/rt_hw.h rt_render_frame).  rt_frame_plan.h defines the layout: which
+// device is the root (devices[0]), which shards share a device, where shard r's rows land in
+// the root's staging buffer and how large every buffer is.  rt_render_frame (below) checks its
+// arguments, plans, and then: frame_prepare_devices (scene copies, streams, events; kept in the
+// device copies between frames), frame_setup_root (root buffer, row map, peer access), one
+// FrameRun::work per distinct device (render, finish to 8 bits, copy to the root), on failure
+// a drain of the copy streams, frame_assemble (rows into frame order on the root, one copy to
+// the host per output) and rtp::merge_frame_stats.
 // (On the one-GPU pool this runs with every shard on device 0; the peer copies between two
-// MI355X have not run on hardware.)
-int rt_render_frame(rt_scene *s, const rt_params *p, int32_t n_shards, const int32_t *devices, uint8_t *out_rgb,
-                    float *out_sum, rt_stats *st) {
-    if (!s || !p || (!out_rgb && !out_sum)) return rt_fail(RT_ERR_ARG, "rt_render_frame: NULL argument");
-    if (int rc = check_flags(p, "rt_render_frame")) return rc;
-    // (a devices array needs its length: one entry per shard, so n_shards must be given)
-    if (devices && n_shards <= 0)
-        return rt_fail(RT_ERR_ARG, "rt_render_frame: devices given without n_shards (one device per shard)");
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    const int n = n_shards > 0 ? n_shards : ndev;
-    if (n < 1 || n > (1 << 16)) return rt_fail(RT_ERR_ARG, "rt_render_frame: bad shard count " + std::to_string(n));
-    std::vector<int> dev_of(n);
-    for (int r = 0; r < n; ++r) {
-        dev_of[r] = devices ? devices[r] : r;
-        if (dev_of[r] < 0 || dev_of[r] >= ndev || dev_of[r] >= kRtMaxDevices)
-            return rt_fail(RT_ERR_DEVICE, "rt_render_frame: shard " + std::to_string(r) + " on device " +
-                                              std::to_string(dev_of[r]) + ", " + std::to_string(ndev) + " visible");
-    }
-    const int spp = p->spp > 0 ? p->spp : s->samples;
-    if (spp < 1) return rt_fail(RT_ERR_ARG, "rt_render_frame: samples per pixel must be >= 1");
-    int rc = ensure_blob(s);   // built once here, copied to every device
-    if (rc) return rc;
-    const int rb = norm_row_block(p), W = s->width, H = s->height;
-    const int root = dev_of[0];
-    // staging on the root: shard r's rows at row offset base[r]; frame_row_of[staging row]
-    std::vector<int64_t> rows(n), base(n + 1, 0);
-    std::vector<int32_t> frame_row_of((size_t)std::max(H, 1));
-    for (int r = 0; r < n; ++r) {
-        rows[r] = rt_shard_rows_impl(H, r, n, rb, nullptr);
-        if (rows[r] < 0) return rt_fail(RT_ERR_ARG, "rt_render_frame: bad row partition (height " + std::to_string(H) +
-                                                        ", row_block " + std::to_string(rb) + ")");
-        rt_shard_rows_impl(H, r, n, rb, frame_row_of.data() + base[r]);
-        base[r + 1] = base[r] + rows[r];
-    }
-    const size_t row_u8 = (size_t)W * 3, row_f = row_u8 * sizeof(float);
-    std::vector<int> uniq;
-    for (int d : dev_of)
-        if (std::find(uniq.begin(), uniq.end(), d) == uniq.end()) uniq.push_back(d);
-    for (int d : uniq) {   // every device's scene copy, streams and events (kept between frames)
-        rc = ensure_device_scene(s, d);
-        if (rc) return rc;
+// MI355X have not run on hardware.  tests/test_frame_plan.py covers their host arithmetic.)
+namespace {
+
+static_assert(rtp::kMaxDevices == kRtMaxDevices, "the frame plan refuses the device ids a scene has no slot for");
+
+int frame_prepare_devices(rt_scene *s, const rtp::FramePlan &f) {
+    for (int d : f.uniq) {   // (kept between frames)
+        if (int rc = ensure_device_scene(s, d)) return rc;
         DeviceGuard g(d);
         HIP_TRY(ensure_frame_streams(s->dev[d]));
     }
-    // the root's staging (shard r's rows at row offset base[r]), frame buffers and row map:
-    // [stage u8 | frame u8 | stage f32 | frame f32 | frame_row_of], each 256-B aligned
-    rt_device_scene *rd = s->dev[root];
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t b_u8 = al((size_t)H * row_u8), b_f = out_sum ? al((size_t)H * row_f) : 0,
-                 b_map = al((size_t)std::max(H, 1) * sizeof(int32_t));
+    return RT_OK;
+}
+
+// Grows the root buffer, uploads the row map and lets the root and its peers copy directly
+// (xGMI) where the runtime allows.
+int frame_setup_root(rt_scene *s, const rtp::FramePlan &f) {
+    const int root = f.root();
+    rt_device_scene::Frame &rf = s->dev[root]->fr;
     {
         DeviceGuard g(root);
-        HIP_TRY(grow(&rd->root_buf, &rd->root_bytes, 2 * b_u8 + 2 * b_f + b_map));
-        HIP_TRY(hipStreamSynchronize(rd->fr_stream));   // (the previous frame's map upload is done)
-        HIP_TRY(hipMemcpyAsync((uint8_t *)rd->root_buf + 2 * b_u8 + 2 * b_f, frame_row_of.data(),
-                               (size_t)H * sizeof(int32_t), hipMemcpyHostToDevice, rd->fr_stream));
+        HIP_TRY(grow(&rf.root_buf, &rf.root_bytes, f.root_bytes));
+        HIP_TRY(hipStreamSynchronize(rf.stream));   // (the previous frame's map upload is done)
+        HIP_TRY(hipMemcpyAsync((uint8_t *)rf.root_buf + f.o_row_map, f.frame_row_of.data(),
+                               (size_t)f.height * sizeof(int32_t), hipMemcpyHostToDevice, rf.stream));
     }
-    uint8_t *stage_u8 = (uint8_t *)rd->root_buf, *frame_u8 = stage_u8 + b_u8;
-    uint8_t *stage_f = frame_u8 + b_u8, *frame_f = stage_f + b_f;
-    const int *row_map = (const int *)(frame_f + b_f);
-    for (int d : uniq) {   // direct xGMI copies between the root and its peers where the runtime allows
+    for (int d : f.uniq) {
         if (d == root) continue;
         int can = 0;
         if (hipDeviceCanAccessPeer(&can, d, root) == hipSuccess && can) {
@@ -1938,127 +1909,154 @@ int rt_render_frame(rt_scene *s, const rt_params *p, int32_t n_shards, const int
             (void)hipGetLastError();
         }
     }
-    std::vector<int> rcs(uniq.size(), RT_OK);
-    std::vector<std::string> errs(uniq.size());
-    std::vector<rt_stats> sts(n);
-    // One host thread per device.  Its shards alternate between two buffers: shard r is
-    // rendered (launch waits for it: stats) and finished to 8 bits on the render stream; the
-    // copy stream waits for that finish and copies the shard to the root's staging buffer,
-    // while the render stream goes on with the next shard in the other buffer (it waits for
-    // that buffer's previous copy first).  The device's last copy is marked by fr_last: the
-    // root waits for its own on its stream, and for every peer's on the host (below).
-    auto work = [&](size_t ui) {
-        const int dev = uniq[ui];
-        rt_device_scene *dd = s->dev[dev];
-        auto fail = [&](int code, const std::string &m) {
-            rcs[ui] = rt_fail(code, m);
-            errs[ui] = rt_last_error();
-        };
+    return RT_OK;
+}
+
+// What the frame's workers share; work(ui) is the host thread of device f.uniq[ui].  It renders
+// that device's shards one after another (one render per (scene, device) in flight), alternating
+// between two buffers: shard r is rendered (launch waits for it: stats) and finished to 8 bits
+// (rt_finish_kernel, scene.cpp:54-64) on the render stream; the copy stream waits for that
+// finish and copies the shard, 8-bit rows and (if asked) float sums, to the root's staging
+// buffer (hipMemcpyPeerAsync: over xGMI between MI355X), while the render stream goes on with
+// the next shard in the other buffer (it waits for that buffer's previous copy first).  The
+// device's last copy is marked by fr.last, which frame_assemble waits for.
+struct FrameRun {
+    rt_scene *s;
+    const rt_params *p;
+    const rtp::FramePlan &f;
+    uint8_t *root_buf;               // the root's (staging parts at f.o_stage_u8, f.o_stage_f)
+    std::vector<rt_stats> stats;     // [shard]
+    std::vector<int> rcs;            // [uniq index] the worker's failure, with its text
+    std::vector<std::string> errs;
+
+    void fail(size_t ui, int rc) { rcs[ui] = rc, errs[ui] = rt_last_error(); }
+
+    void work(size_t ui) {
+        const int dev = f.uniq[ui], root = f.root();
+        const rtp::FrameDevice &fd = f.dev[ui];
+        rt_device_scene::Frame &fr = s->dev[dev]->fr;
         DeviceGuard g(dev);
-        if (!g.ok) return fail(RT_ERR_DEVICE, "hipSetDevice failed");
-        int64_t max_rows = 0;
-        for (int r = 0; r < n; ++r)
-            if (dev_of[r] == dev) max_rows = std::max(max_rows, rows[r]);
-        const size_t b_sum = al((size_t)max_rows * row_f);
+        if (!g.ok) return fail(ui, rt_fail(RT_ERR_DEVICE, "hipSetDevice failed"));
         hipError_t e = hipSuccess;
-        for (int b = 0; b < 2 && e == hipSuccess; ++b) e = grow(&dd->fr_buf[b], &dd->fr_bytes[b], b_sum + (size_t)max_rows * row_u8);
+        for (int b = 0; b < 2 && e == hipSuccess; ++b) e = grow(&fr.buf[b], &fr.bytes[b], fd.buf_bytes);
         int nb = 0;   // shards done on this device (buffer = nb % 2)
-        for (int r = 0; r < n && e == hipSuccess && rcs[ui] == RT_OK; ++r) {
-            if (dev_of[r] != dev || rows[r] == 0) continue;
+        for (int r = 0; r < f.n && e == hipSuccess && rcs[ui] == RT_OK; ++r) {
+            if (f.dev_of[r] != dev || f.rows[r] == 0) continue;
             const int b = nb % 2;
-            float *sum = (float *)dd->fr_buf[b];
-            uint8_t *rgb = (uint8_t *)dd->fr_buf[b] + b_sum;
-            if (nb >= 2) e = hipStreamWaitEvent(dd->fr_stream, dd->fr_copied[b], 0);   // buffer b's last copy done
+            float *sum = (float *)fr.buf[b];
+            uint8_t *rgb = (uint8_t *)fr.buf[b] + fd.sum_bytes;
+            if (nb >= 2) e = hipStreamWaitEvent(fr.stream, fr.copied[b], 0);   // buffer b's last copy done
             if (e != hipSuccess) break;
             rt_params q = *p;
             q.rank = r;
-            q.world = n;
-            q.row_block = rb;
+            q.world = f.n;
+            q.row_block = f.row_block;
             q.device = dev;
-            q.spp = spp;
-            int lr = launch(s, &q, sum, dd->fr_stream, &sts[r]);   // waits (stats)
-            if (lr) { rcs[ui] = lr; errs[ui] = rt_last_error(); break; }
-            lr = rt_tonemap_u8_device(sum, W, (int32_t)rows[r], spp, rgb, dd->fr_stream);
-            if (lr) { rcs[ui] = lr; errs[ui] = rt_last_error(); break; }
-            e = hipEventRecord(dd->fr_finished, dd->fr_stream);
-            if (e == hipSuccess) e = hipStreamWaitEvent(dd->cp_stream, dd->fr_finished, 0);
+            q.spp = f.spp;
+            int lr = launch(s, &q, sum, fr.stream, &stats[r]);   // waits (stats)
+            if (!lr) lr = rt_tonemap_u8_device(sum, f.width, (int32_t)f.rows[r], f.spp, rgb, fr.stream);
+            if (lr) { fail(ui, lr); break; }   // (fr.last is still recorded below)
+            e = hipEventRecord(fr.finished, fr.stream);
+            if (e == hipSuccess) e = hipStreamWaitEvent(fr.cp_stream, fr.finished, 0);
             if (e == hipSuccess)
-                e = hipMemcpyPeerAsync(stage_u8 + base[r] * row_u8, root, rgb, dev, rows[r] * row_u8, dd->cp_stream);
-            if (e == hipSuccess && out_sum)
-                e = hipMemcpyPeerAsync(stage_f + base[r] * row_f, root, sum, dev, rows[r] * row_f, dd->cp_stream);
-            if (e == hipSuccess) e = hipEventRecord(dd->fr_copied[b], dd->cp_stream);
+                e = hipMemcpyPeerAsync(root_buf + f.o_stage_u8 + f.base[r] * f.row_u8, root, rgb, dev, f.rows[r] * f.row_u8,
+                                       fr.cp_stream);
+            if (e == hipSuccess && f.want_sums)
+                e = hipMemcpyPeerAsync(root_buf + f.o_stage_f + f.base[r] * f.row_f, root, sum, dev, f.rows[r] * f.row_f,
+                                       fr.cp_stream);
+            if (e == hipSuccess) e = hipEventRecord(fr.copied[b], fr.cp_stream);
             ++nb;
         }
-        if (e == hipSuccess) e = hipEventRecord(dd->fr_last, dd->cp_stream);
-        if (e != hipSuccess && rcs[ui] == RT_OK) fail(RT_ERR_DEVICE, std::string("rt_render_frame: ") + hipGetErrorString(e));
-    };
+        if (e == hipSuccess) e = hipEventRecord(fr.last, fr.cp_stream);
+        if (e != hipSuccess && rcs[ui] == RT_OK)
+            fail(ui, rt_fail(RT_ERR_DEVICE, std::string("rt_render_frame: ") + hipGetErrorString(e)));
+    }
+};
+
+// Assembles the frame on the root behind every device's last copy; one copy to the host per output.
+int frame_assemble(rt_scene *s, const rtp::FramePlan &f, uint8_t *out_rgb, float *out_sum) {
+    const int root = f.root();
+    DeviceGuard g(root);
+    if (!g.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    const rt_device_scene::Frame &rf = s->dev[root]->fr;
+    hipStream_t q = rf.stream;
+    uint8_t *buf = (uint8_t *)rf.root_buf, *frame_u8 = buf + f.o_frame_u8, *frame_f = buf + f.o_frame_f;
+    const int *row_map = (const int *)(buf + f.o_row_map);
+    const long long H = f.height;
+    // The root's own last copy is waited for on its stream.  A peer's copy is waited for on
+    // the host (hipEventSynchronize on the peer's event) before the assembly is queued: a
+    // root-stream wait on an event recorded on another device is the cheaper form, but it
+    // has not run on a multi-GPU box yet, so the host wait stays the
+    // conservative default until it has.
+    for (int d : f.uniq) {
+        if (d == root) {
+            HIP_TRY(hipStreamWaitEvent(q, s->dev[d]->fr.last, 0));
+        } else {
+            DeviceGuard gp(d);
+            if (!gp.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+            HIP_TRY(hipEventSynchronize(s->dev[d]->fr.last));
+        }
+    }
+    hipLaunchKernelGGL(rt_rows_scatter_kernel, dim3(4, (unsigned)H), dim3(256), 0, q, (const uint8_t *)(buf + f.o_stage_u8),
+                       frame_u8, row_map, H, (long long)f.row_u8);
+    HIP_TRY(hipGetLastError());
+    if (out_sum) {
+        hipLaunchKernelGGL(rt_rows_scatter_kernel, dim3(8, (unsigned)H), dim3(256), 0, q,
+                           (const uint8_t *)(buf + f.o_stage_f), frame_f, row_map, H, (long long)f.row_f);
+        HIP_TRY(hipGetLastError());
+    }
+    if (out_rgb) HIP_TRY(hipMemcpyAsync(out_rgb, frame_u8, (size_t)H * f.row_u8, hipMemcpyDeviceToHost, q));
+    if (out_sum) HIP_TRY(hipMemcpyAsync(out_sum, frame_f, (size_t)H * f.row_f, hipMemcpyDeviceToHost, q));
+    HIP_TRY(hipStreamSynchronize(q));
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_frame(rt_scene *s, const rt_params *p, int32_t n_shards, const int32_t *devices, uint8_t *out_rgb,
+                    float *out_sum, rt_stats *st) {
+    // 1. the arguments (the devices check needs no device count and comes before it)
+    if (!s || !p || (!out_rgb && !out_sum)) return rt_fail(RT_ERR_ARG, "rt_render_frame: NULL argument");
+    if (int rc = check_flags(p, "rt_render_frame")) return rc;
+    if (const rtp::Refusal r = rtp::frame_check_devices(n_shards, devices)) return rt_fail(r.code, r.msg);
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    const rtp::FrameIn in{s->width, s->height, n_shards, devices, norm_row_block(p), p->spp > 0 ? p->spp : s->samples,
+                          ndev, out_sum != nullptr};
+    if (const rtp::Refusal r = rtp::frame_check(in)) return rt_fail(r.code, r.msg);
+    if (int rc = ensure_blob(s)) return rc;   // built once here, copied to every device
+    // 2. the plan
+    const rtp::FramePlan f = rtp::plan_frame(in);
+    if (f.refused) return rt_fail(f.refused.code, f.refused.msg);
+    // 3. and 4. the devices and the root
+    if (int rc = frame_prepare_devices(s, f)) return rc;
+    if (int rc = frame_setup_root(s, f)) return rc;
+    // 5. one worker per device (the root's on this thread)
+    const size_t nu = f.uniq.size();
+    FrameRun run{s, p, f, (uint8_t *)s->dev[f.root()]->fr.root_buf, std::vector<rt_stats>(f.n),
+                 std::vector<int>(nu, RT_OK), std::vector<std::string>(nu)};
     std::vector<std::thread> threads;
-    for (size_t ui = 1; ui < uniq.size(); ++ui) threads.emplace_back(work, ui);
-    work(0);
+    for (size_t ui = 1; ui < nu; ++ui) threads.emplace_back(&FrameRun::work, &run, ui);
+    run.work(0);
     for (std::thread &t : threads) t.join();
     // every shard's render has ended here (launch waited for each); from now on the host waits
     // only for the copies still in flight, the assembly and the copy to the host: gather_ms
     const auto t0 = std::chrono::steady_clock::now();
-    for (size_t ui = 0; ui < uniq.size(); ++ui)
-        if (rcs[ui] != RT_OK) {
-            for (int d : uniq) {   // (leave no copy in flight into the root's buffers)
+    // 6. a failed worker: leave no copy in flight into the root's buffers
+    for (size_t ui = 0; ui < nu; ++ui)
+        if (run.rcs[ui] != RT_OK) {
+            for (int d : f.uniq) {
                 DeviceGuard g(d);
-                (void)hipStreamSynchronize(s->dev[d]->cp_stream);
+                (void)hipStreamSynchronize(s->dev[d]->fr.cp_stream);
             }
-            return rt_fail(rcs[ui], "device " + std::to_string(uniq[ui]) + ": " + errs[ui]);
+            return rt_fail(run.rcs[ui], "device " + std::to_string(f.uniq[ui]) + ": " + run.errs[ui]);
         }
-    {   // assemble on the root behind every device's last copy, one copy to the host per output
-        DeviceGuard g(root);
-        if (!g.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
-        hipStream_t q = rd->fr_stream;
-        // The root's own last copy is waited for on its stream.  A peer's copy is waited for on
-        // the host (hipEventSynchronize on the peer's event) before the assembly is queued: a
-        // root-stream wait on an event recorded on another device is the cheaper form, but it
-        // has not run on a multi-GPU box yet, so the host wait stays the
-        // conservative default until it has.
-        for (int d : uniq) {
-            if (d == root) {
-                HIP_TRY(hipStreamWaitEvent(q, s->dev[d]->fr_last, 0));
-            } else {
-                DeviceGuard gp(d);
-                if (!gp.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
-                HIP_TRY(hipEventSynchronize(s->dev[d]->fr_last));
-            }
-        }
-        if (H > 0) {
-            hipLaunchKernelGGL(rt_rows_scatter_kernel, dim3(4, (unsigned)H), dim3(256), 0, q, (const uint8_t *)stage_u8,
-                               frame_u8, row_map, (long long)H, (long long)row_u8);
-            HIP_TRY(hipGetLastError());
-            if (out_sum) {
-                hipLaunchKernelGGL(rt_rows_scatter_kernel, dim3(8, (unsigned)H), dim3(256), 0, q,
-                                   (const uint8_t *)stage_f, frame_f, row_map, (long long)H, (long long)row_f);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-        if (out_rgb) HIP_TRY(hipMemcpyAsync(out_rgb, frame_u8, (size_t)H * row_u8, hipMemcpyDeviceToHost, q));
-        if (out_sum) HIP_TRY(hipMemcpyAsync(out_sum, frame_f, (size_t)H * row_f, hipMemcpyDeviceToHost, q));
-        HIP_TRY(hipStreamSynchronize(q));
-    }
+    // 7. and 8. the frame and its stats
+    if (int rc = frame_assemble(s, f, out_rgb, out_sum)) return rc;
     const double gather_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (st) {
-        std::memset(st, 0, sizeof *st);
-        std::vector<double> dev_ms(uniq.size(), 0.0), dev_order(uniq.size(), 0.0);   // a device's shards run in turn
-        for (int r = 0; r < n; ++r) {
-            const rt_stats &x = sts[r];
-            st->pixels += x.pixels; st->samples += x.samples; st->rays += x.rays;
-            st->aabb_tests += x.aabb_tests; st->tri_tests += x.tri_tests; st->light_queries += x.light_queries;
-            st->light_aabb_tests += x.light_aabb_tests; st->light_tri_tests += x.light_tri_tests;
-            st->shading_hits += x.shading_hits; st->extend_rays += x.extend_rays;
-            st->schedule |= x.schedule;
-            const size_t ui = (size_t)(std::find(uniq.begin(), uniq.end(), dev_of[r]) - uniq.begin());
-            dev_ms[ui] += x.render_ms;
-            dev_order[ui] += x.order_ms;
-        }
-        st->render_ms = *std::max_element(dev_ms.begin(), dev_ms.end());
-        st->order_ms = *std::max_element(dev_order.begin(), dev_order.end());
-        st->gather_ms = gather_ms;
-        st->devices = (uint64_t)uniq.size();
-    }
+    if (st) rtp::merge_frame_stats(f, run.stats.data(), gather_ms, st);
     return RT_OK;
 }
 

@@ -11,6 +11,7 @@
 // are compile-time A/B knobs (make variant VFLAGS=-DRT_…=…).
 #pragma once
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <string>
 
@@ -74,6 +75,9 @@ constexpr int kClaimStride = RT_CLAIM_STRIDE;
 #endif
 constexpr int kCoopRoundMinSpec = RT_SPEC_COOP_ROUND_MIN;   // small scenes
 constexpr int kCoopRoundNodes = 4096;
+
+// Device buffers are laid out in parts that start on 256-byte boundaries.
+inline size_t align_up(size_t bytes) { return (bytes + 255) & ~size_t(255); }
 
 // A refusal (code RT_OK: none) with the text rt_last_error reports.
 struct Refusal {
