@@ -284,17 +284,8 @@ __global__ void __launch_bounds__(256) rt_finish_kernel(const float *sum, long l
 // SPEC (parity renders without counting): a wave whose claim finds the queue empty enters its
 // tail and runs speculative sample runahead (rt_mega.h spec_manage) on its idle lanes.  A
 // separate instantiation, so the kernel without it keeps its own register allocation.
-// `mode` (0 for the default schedules) packs the hand-off's settings (one kernel argument: the
-// kernel is short of SGPRs, which spill into VGPRs):
-//   bits 0-7   park_below > 0 (plain kernel): a wave whose queue is empty and that holds fewer
-//              than park_below pixels parks them, each at its next sample end, in the park list
-//              at its lane slot (rt_mega.h park_pixel; the list's address in the queue block,
-//              read where used: no register held in the loop);
-//   bits 8-15  resume_pct > 0 (SPEC): the items are that park list's slots (st.n of them); wave
-//              w of the grid takes slots [w * per, (w + 1) * per), its lanes below per one each
-//              (per: resume_pct percent of the slots over the grid's waves, at most 64), skips
-//              the empty ones and enters its tail at once; the slots past the grid's share are
-//              claimed in the tail (rt_mega.h SpecClaim) through the resume claim counter.
+// `mode` (0 for the default schedules) packs the hand-off's settings, park_below (plain kernel)
+// and resume_pct (SPEC): rt_launch_plan.h mode_pack has the layout and what each one does.
 // `queue` is the queue block (rt_mega.h QueueWord names its words); the pre-pass gets the
 // address of its own claim counter instead.
 // CHAIN (rt_accum_add; parity renders without counting, plain and runahead kernels only): the
@@ -308,7 +299,7 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
                unsigned long long *queue, const int *order, unsigned *cost, int cs, int mode) {
     constexpr bool kSpec = SPEC && !COUNT && !FAST && !LSPLIT;
     constexpr bool kChain = CHAIN && !COUNT && !FAST && !LSPLIT;
-    const int park_below = mode & 255, resume_pct = (mode >> 8) & 255;
+    const int park_below = rtp::mode_park_below(mode), resume_pct = rtp::mode_resume_pct(mode);
     const uint4 *resume = kSpec && resume_pct > 0 ? (const uint4 *)queue[rtd::kQueueParkList] : nullptr;
     const long long n_items = FAST ? g.n_pixels * (long long)((spp + cs - 1) / cs) : (kSpec && resume) ? st.n : g.n_pixels;
     const int lane = threadIdx.x & 63;
@@ -367,6 +358,7 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
     if constexpr (kSpec) {
         if (resume) {
             const long long waves = (long long)gridDim.x * (blockDim.x >> 6);
+            // (dealt, per: must equal rtp::resume_deal(n_items, resume_pct, waves))
             const long long dealt = (n_items * resume_pct + 99) / 100;
             const int per = (int)std::min<long long>(64, std::max<long long>(1, (dealt + waves - 1) / waves));
             const long long p = (rtd::mega_slot() >> 6) * per + lane;
@@ -486,9 +478,10 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
         }
         // hand-off: a wave whose queue is empty and that holds fewer than park_below pixels parks
         // each of them at its next sample end (rt_mega.h mega_shade)
-        if (!kSpec && park_below > 0 && exhausted && !park) park = __popcll(__ballot(L.pix >= 0)) < park_below;
+        if (!kSpec && park_below > 0 && exhausted && !park) park = rtp::park_rule(__popcll(__ballot(L.pix >= 0)), park_below);
         const int nr = __popcll(__ballot(L.state == rtd::M_READY || (LSPLIT && L.state == rtd::M_LREADY)));
         const int nt = __popcll(__ballot(L.state == rtd::M_TRAV || (LSPLIT && L.state == rtd::M_LTRAV)));
+        // (must equal rtp::shade_rule(nr, nt, shade_min))
         const bool shade_now = nr > 0 && (nr >= (kSpec ? kSpecShadeMin : kShadeMin) || nt == 0);
         // Runahead kernel (the 8-way shards): a traversal iteration issues at priority 1, a
         // shading pass at 0, so waves in their long shading code give issue slots to waves
@@ -1300,7 +1293,7 @@ int launch_handoff(rt_device_scene *d, const ShardGeom &g, const rtp::Grid &gr, 
     w.lanes = gr.blocks2 * 256;
     w.n = slots;   // the park list's slots
     hipLaunchKernelGGL(rk, dim3((unsigned)gr.blocks2), dim3(256), 0, stream, d->ds, g, w, spp, k_out, d->counters, d->queue,
-                       (const int *)nullptr, (unsigned *)nullptr, 0, rtp::kHandoffPct << 8);
+                       (const int *)nullptr, (unsigned *)nullptr, 0, rtp::mode_pack(0, rtp::kHandoffPct));
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
@@ -1425,7 +1418,7 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
         if (cp)
             if (int rc = set_queue_word(d, rtd::kChainWord, cp->chain, stream)) return rc;
         hipLaunchKernelGGL(mk, dim3((unsigned)grid.blocks), dim3(256), 0, stream, d->ds, g, w, in.spp, k_out, d->counters,
-                           d->queue, order, (unsigned *)nullptr, plan.cs, plan.handoff ? rtp::kHandoffBelow : 0);
+                           d->queue, order, (unsigned *)nullptr, plan.cs, rtp::mode_pack(plan.handoff ? rtp::kHandoffBelow : 0, 0));
         HIP_TRY(hipGetLastError());
         if (plan.handoff)
             if (int rc = launch_handoff(d, g, grid, rk, w, in.spp, k_out, stream)) return rc;

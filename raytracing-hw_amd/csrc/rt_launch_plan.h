@@ -8,7 +8,9 @@
 // Two steps because the grid depends on the occupancy of the kernel step one chose.  Resident
 // block counts are inputs, so every rule here runs without a GPU (tests/test_launch_plan.py).
 // The tuning constants the rules use live here with their measurements; the #ifndef RT_… ones
-// are compile-time A/B knobs (make variant VFLAGS=-DRT_…=…).
+// are compile-time A/B knobs (make variant VFLAGS=-DRT_…=…).  The rules the kernel's wave loop
+// shares with the plan and with its host emulation (the `mode` word, the resume deal, the shade
+// and park rules) are constexpr functions below, next to kHandoffBelow and kHandoffPct.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -59,6 +61,42 @@ constexpr long long kSpecPixelsPerLane = RT_SPEC_PIXELS_PER_LANE;
 constexpr int kHandoffBelow = RT_HANDOFF_BELOW;
 constexpr int kHandoffPct = RT_HANDOFF_PCT;
 constexpr bool kHandoffSpread = RT_HANDOFF_SPREAD != 0;
+
+// The schedule rules the host plan, rt_mega_kernel and the host emulation of its wave loop
+// (tests/native/mega_emu.h) share, each written once.  The kernel calls those that leave its
+// device listing as it is (the mode word, the park rule) and keeps the others as literal
+// expressions marked with the rule's name: register allocation of the plain kernel moved
+// throughout when they were calls.
+//
+// rt_mega_kernel's `mode` argument (0 for the default schedules) packs the hand-off's settings
+// into one kernel argument (the kernel is short of SGPRs, which spill into VGPRs):
+//   bits 0-7   park_below > 0 (plain kernel): a wave whose queue is empty and that holds fewer
+//              than park_below pixels parks them, each at its next sample end, in the park list
+//              at its lane slot (rt_mega.h park_pixel; the list's address in the queue block,
+//              read where used: no register held in the loop);
+//   bits 8-15  resume_pct > 0 (SPEC): the items are that park list's slots (st.n of them); wave
+//              w of the grid takes slots [w * per, (w + 1) * per), its lanes below per one each
+//              (resume_deal), skips the empty ones and enters its tail at once; the slots past
+//              the grid's share are claimed in the tail (rt_mega.h SpecClaim) through the resume
+//              claim counter.
+constexpr int mode_pack(int park_below, int resume_pct) { return (park_below & 255) | (resume_pct & 255) << 8; }
+constexpr int mode_park_below(int mode) { return mode & 255; }
+constexpr int mode_resume_pct(int mode) { return (mode >> 8) & 255; }
+// The resume launch's deal: `dealt` = pct percent of the park list's slots, rounded up, go out
+// at its start, `per` of them to each of its waves (one per lane: at most 64; at least 1).
+struct Deal {
+    long long dealt, per;
+};
+constexpr Deal resume_deal(long long slots, int pct, long long waves) {
+    const long long dealt = (slots * pct + 99) / 100;
+    return {dealt, std::min<long long>(64, std::max<long long>(1, (dealt + waves - 1) / waves))};
+}
+// A wave shades its nr READY lanes once there are shade_min of them or none of its nt others
+// still traverses; otherwise it steps the traversing lanes.
+constexpr bool shade_rule(int nr, int nt, int shade_min) { return nr > 0 && (nr >= shade_min || nt == 0); }
+// A plain wave whose queue is empty parks its pixels once it holds fewer than park_below.
+constexpr bool park_rule(int held, int park_below) { return held < park_below; }
+
 // Diagnostics (A/B builds only): only every k-th lane of a wave claims pixels, so a wave
 // holds at most 64 / k pixels and the grid grows k-fold (lockstep study).
 #ifndef RT_CLAIM_STRIDE
@@ -183,8 +221,8 @@ struct Grid {
     // first round (one per wave): `groups` claims of `per` items (rt_order_spread_kernel)
     long long groups = 0, per = 64;
     // the hand-off's relaunch over the runahead kernel's whole resident grid: its blocks and
-    // waves, the park-list slots dealt at its start and how many of them each wave takes.  The
-    // same formula as the kernel's resume site (rt_mega_kernel: waves, dealt, per).
+    // waves, the park-list slots dealt at its start and how many of them each wave takes
+    // (resume_deal, as at the kernel's resume site).
     long long blocks2 = 0, waves2 = 0, dealt = 0, per2 = 0;
     bool spread2 = false;   // the parked pixels are dealt heaviest first (else in slot order)
 };
@@ -204,8 +242,9 @@ inline Grid plan_grid(const Schedule &s, long long variant_blocks) {
     if (s.handoff) {
         g.blocks2 = s.spec_blocks;
         g.waves2 = 4 * g.blocks2;   // (256-thread blocks)
-        g.dealt = (g.slots * kHandoffPct + 99) / 100;
-        g.per2 = std::min<long long>(64, std::max<long long>(1, (g.dealt + g.waves2 - 1) / g.waves2));
+        const Deal deal = resume_deal(g.slots, kHandoffPct, g.waves2);
+        g.dealt = deal.dealt;
+        g.per2 = deal.per;
         // (with the pixel order's estimates at hand; the order buffer holds n_pixels per array)
         g.spread2 = kHandoffSpread && s.ordered && g.slots <= s.n_pixels;
     }

@@ -613,7 +613,7 @@ __device__ __forceinline__ void mega_iterate(ML &L, bool shade_now, const DevSce
 // epoch), 1 (sum xyz, meta), 2 (X_f, lane table low word), 3 (start state of job nxt-1, lane
 // table high word); plane 4 is each lane's job (tag = record | epoch << 6, start state).  A management pass loads them once, works on registers with the wave's
 // shuffles and ballots, and stores them back: one memory round trip per pass.  The same
-// pass runs on the host test harness (tests/native/kernel_host.cpp) over emulated lanes:
+// pass runs on the host test harness (tests/native/mega_emu.h) over emulated lanes:
 // WArr is one register per lane on the GPU and a 64-entry array on the host.
 
 // Diagnostics build (RT_MEGA_PROF): runahead event counts, printed by the launch.

@@ -1,51 +1,11 @@
 // kernel_host.cpp — TEST ONLY: compiles the GPU kernel source (raytracing-hw_amd/csrc/rt_path.h)
 // for the host so tests can check its arithmetic against the goldens without a GPU.  Not
-// part of the product: librt_hw_amd.so has no CPU render path.
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-#include <algorithm>
-#include <type_traits>
-#include "../../raytracing-hw_amd/csrc/rt_mega.h"
-#include "../../raytracing-hw_amd/csrc/rt_bvh_layout.h"
-#include "../../include/rt_hw.h"
+// part of the product: librt_hw_amd.so has no CPU render path.  The emulation of the
+// lane-resident kernel's wave loop is mega_emu.h's; the kh_render_mega* entry points here run
+// it with the harness's default options (kh_options, written by the kh_set_* setters).
+#include "mega_emu.h"
 
-static rtd::DevScene make(const rt_scene_view *v) {
-    rtd::DevScene s{};
-    s.tri = (const float4 *)v->tri;
-    s.tri_attr = (const float4 *)v->tri_attr;
-    s.tri_tan = (const float4 *)v->tri_tan;
-    s.node = (const float4 *)v->node;
-    // the device copy of the triangles is padded (a leaf lane reads 4 x 16 B of its last
-    // triangle: its 3 records and the next one's first)
-    static thread_local std::vector<float> tri;
-    tri.assign(v->tri, v->tri + 12 * (size_t)v->n_tris);
-    tri.resize(tri.size() + 12, 0.f);
-    s.tri = (const float4 *)tri.data();
-    s.light = (const float4 *)v->light;
-    s.light_node = (const float4 *)v->light_node;
-    s.mesh_f = v->mesh_f;
-    s.mesh_tex = v->mesh_tex;
-    s.mesh_nt = v->mesh_normal_transform;
-    s.tex_info = (const uint4 *)v->tex_info;
-    s.texels = (const uint32_t *)v->texels;
-    static float lut[512];
-    static bool lut_ready = false;
-    if (!lut_ready) { rtd::fill_decode_lut(lut); lut_ready = true; }
-    s.lut = lut;
-    s.n_lights = (int)v->n_lights;
-    s.ray_depth = v->ray_depth;
-    s.max_distance = v->max_distance;
-    s.width = v->width;
-    s.height = v->height;
-    s.fwidth = (float)v->width;
-    s.fheight = (float)v->height;
-    std::memcpy(s.cam_pos, v->cam_pos, sizeof s.cam_pos);
-    std::memcpy(s.cam_axes, v->cam_axes, sizeof s.cam_axes);
-    std::memcpy(s.tan_fov, v->tan_half_fov, sizeof s.tan_fov);
-    return s;
-}
+using namespace emu;
 
 // render_pixel (rt_path.h): the reference's recursion order, closest_hit by explicit stack.
 extern "C" void kh_render(const rt_scene_view *v, int spp, int64_t p0, int64_t p1, float *out, uint64_t *cnt) {
@@ -67,14 +27,10 @@ extern "C" void kh_render(const rt_scene_view *v, int spp, int64_t p0, int64_t p
 // the same rt_wavefront.h slot functions and queue records, driven by a host queue.
 extern "C" int kh_render_wf(const rt_scene_view *v, int spp, int rank, int world, int row_block, float *out,
                             uint64_t *cnt_out, int64_t *iterations) {
-    rtd::DevScene sc = make(v);
-    sc.n_tris = (int)v->n_tris;
-    sc.n_nodes = (int)v->n_nodes;
-    int64_t rows = 0;
-    for (int r = 0; r < v->height; ++r)
-        if ((r / row_block) % world == rank) ++rows;
-    const long long n = (long long)rows * v->width;
-    const rtd::ShardGeom g = rtd::shard_geom(v->width, rank, world, row_block, n);
+    const rtd::DevScene sc = make(v);
+    const Shard sh = shard_of(v, rank, world, row_block);
+    const long long n = sh.n;
+    const rtd::ShardGeom g = sh.g;
     const int D = v->ray_depth;
     std::vector<float4> stv((size_t)2 * n), ab((size_t)2 * n * D);
     std::vector<float> cv((size_t)n * D);
@@ -143,25 +99,6 @@ extern "C" void kh_rng(uint32_t seed, int kind, int n, float *out_f, uint32_t *o
     }
 }
 
-// Emulates rt_mega_kernel (kernel 0): `waves` waves of 64 lanes, round-robin one main-loop
-// iteration at a time, sharing the pixel queue, with the kernel's shade_min decision.
-// LSPLIT: the light-split kernel (light-pdf walk as lane states M_LTRAV / M_LREADY).
-// order (may be NULL): queue item p renders shard pixel order[p], as in the ordered render.
-// SPEC: the speculative sample runahead of the waves' tails (rt_mega.h spec_*), driven here
-// by host loops over the wave's lanes where the kernel uses ballots (rt_mega.h spec_manage);
-// a non-counting render, as on the GPU.
-static uint64_t g_spec_passes = 0;   // management passes since the last kh_spec_stats
-static int g_static_per_wave = 0;    // > 0: no queue; wave w takes items [w*P, w*P+P) (study of spare lanes)
-extern "C" void kh_set_static_per_wave(int p) { g_static_per_wave = p; }
-// Hand-off (rt_device.hip RT_HANDOFF): the plain emulation parks (g_park_below > 0) into
-// g_park_list by lane slot; the runahead emulation resumes it (g_resume_pct > 0)
-static int g_park_below = 0, g_resume_pct = 0;
-static std::vector<uint4> g_park_list;
-// RT_HANDOFF_SPREAD (rt_device.hip): the resume launch deals the slots heaviest first (work
-// left; the harness has no pre-pass estimate, so samples left), spread one per wave
-static int g_handoff_spread = 1;
-extern "C" void kh_set_handoff_spread(int on) { g_handoff_spread = on; }
-static std::vector<int> g_ridx;
 // div_magic (rt_wavefront.h) against `/` for divisor d: every n below 2^20, the 2^20 values
 // below 2^31, the multiples of d and their neighbours up to 2^31, and `extra` seeded draws;
 // returns the number of mismatches.
@@ -187,249 +124,44 @@ extern "C" int64_t kh_div_magic_check(uint32_t d, uint32_t extra) {
     return bad;
 }
 
-static uint64_t g_rounds = 0;        // main-loop rounds (one iteration of every live wave) of the last render
-extern "C" uint64_t kh_rounds() { return g_rounds; }
+// The options every emulated render here starts from.  accum_host.cpp, built into the same
+// library, runs its passes with them too, so one setter serves both.
+emu::Options kh_options;
+extern "C" void kh_set_static_per_wave(int p) { kh_options.static_per_wave = p; }
+extern "C" void kh_set_handoff_spread(int on) { kh_options.spread = on != 0; }
+extern "C" uint64_t kh_rounds() { return kh_options.rounds; }   // main-loop rounds of the last render
 extern "C" void kh_spec_prof(uint64_t *out) {   // the 16 runahead counters (rt_mega.h RT_SPEC_STAT), not reset
     std::memcpy(out, rtd::g_spec_prof, sizeof rtd::g_spec_prof);
 }
 extern "C" void kh_spec_stats(uint64_t *out) {   // passes, frontier jobs, runahead jobs, added, invalidations
-    out[0] = g_spec_passes;
+    out[0] = kh_options.passes;
     out[1] = rtd::g_spec_prof[2];
     out[2] = rtd::g_spec_prof[3];
     out[3] = rtd::g_spec_prof[4];
     out[4] = rtd::g_spec_prof[6];
-    g_spec_passes = 0;
+    kh_options.passes = 0;
     std::memset(rtd::g_spec_prof, 0, sizeof rtd::g_spec_prof);
 }
 
-template <bool LSPLIT, bool SPEC = false>
-static int render_mega(const rt_scene_view *v, int spp, int rank, int world, int row_block, int waves, int shade_min,
-                       const int32_t *order, float *out, uint64_t *cnt_out) {
-    rtd::DevScene sc = make(v);
-    sc.n_tris = (int)v->n_tris;
-    sc.n_nodes = (int)v->n_nodes;
-    int64_t rows = 0;
-    for (int r = 0; r < v->height; ++r)
-        if ((r / row_block) % world == rank) ++rows;
-    const long long n = (long long)rows * v->width;
-    const rtd::ShardGeom g = rtd::shard_geom(v->width, rank, world, row_block, n);
-    const int D = v->ray_depth;
-    const long long slots = std::max<long long>(n, (long long)waves * 64);
-    std::vector<float4> ab((size_t)2 * slots * D);
-    std::vector<float> cv((size_t)slots * D);
-    rtd::WfState st{};
-    st.n = n;
-    st.D = D;
-    st.rec_ab = ab.data();
-    st.rec_c = cv.data();
-    st.lanes = (long long)waves * 64;
-    std::vector<float4> mid((size_t)5 * st.lanes);
-    st.mid = mid.data();
-    const rtd::NodeRec root = rtd::load_node(rtd::mega_nodes(sc), 0);
-    const rtd::GlobalNodes nodes{sc.node};
-    // lane state as in rt_device.hip: TravState for the runahead kernel, TravStateU otherwise
-    using Lane = std::conditional_t<SPEC, rtd::MegaLane, rtd::MegaLaneU>;
-    std::vector<Lane> lanes((size_t)waves * 64);
-    std::vector<std::vector<uint2>> stacks((size_t)waves * 64, std::vector<uint2>(rtd::kStack));
-    for (auto &L : lanes) { L.pix = -1; L.state = rtd::M_IDLE; }
-    std::vector<char> exhausted(waves, 0), done(waves, 0), tail(waves, 0), wave_room(waves, 0);
-    rtd::Counters cnt{0, 0, 0, 0, 0, 0, 0};
-    unsigned long long queue = 0;
-    rtd::SpecClaim claim{&queue, 0, 0, nullptr, 0, false};
-    // hand-off: parking (plain) / resuming (runahead) as rt_mega_kernel's `mode`
-    const bool parking = !SPEC && !LSPLIT && g_park_below > 0, resuming = SPEC && g_resume_pct > 0;
-    std::vector<char> park(waves, 0);
-    if (parking) g_park_list.assign((size_t)2 * waves * 64, make_uint4(rtd::kNoPark, rtd::kNoPark, rtd::kNoPark, rtd::kNoPark));
-    int res_per = 0;
-    long long res_n = 0;
-    std::vector<char> xk((size_t)waves * 64, 0);
-    std::vector<rtd::Rng> xs((size_t)waves * 64);
-    if (resuming) {
-        res_n = (long long)g_park_list.size() / 2;
-        const long long dealt = (res_n * g_resume_pct + 99) / 100;
-        res_per = (int)std::min<long long>(64, std::max<long long>(1, (dealt + waves - 1) / waves));
-        claim = rtd::SpecClaim{&queue, (long long)waves * res_per, res_n, g_park_list.data(), res_per,
-                               (long long)waves * res_per < res_n, nullptr};
-        if (g_handoff_spread) {   // rt_park_keys_kernel, the descending sort, rt_order_spread_kernel
-            std::vector<std::pair<unsigned, int>> kv((size_t)res_n);
-            for (long long i = 0; i < res_n; ++i) {
-                const rtd::Parked q = rtd::parked(g_park_list.data(), i);
-                kv[(size_t)i] = {q.pix == rtd::kNoPark ? 0u : (unsigned)(spp - (int)q.s), (int)i};
-            }
-            std::stable_sort(kv.begin(), kv.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
-            const long long per = res_per, m = std::min<long long>(res_n, (long long)waves * per), a = m / per, b = m % per;
-            g_ridx.resize((size_t)res_n);
-            for (long long q = 0; q < res_n; ++q) {
-                long long r = q;
-                if (q < m) {
-                    const long long gi = q / per, j = q % per;
-                    r = j * a + (j < b ? j : b) + gi;
-                }
-                g_ridx[(size_t)q] = kv[(size_t)r].second;
-            }
-            claim.ridx = g_ridx.data();
-        }
-    }
-    int live = waves;
-    g_rounds = 0;
-    while (live > 0) {
-        ++g_rounds;
-        if (g_rounds > 50000000ull) {   // (a schedule that stops draining: report, do not hang the test)
-            std::fprintf(stderr, "render_mega: no progress after %llu rounds, %d waves live\n",
-                         (unsigned long long)g_rounds, live);
-            if constexpr (SPEC) {
-                for (int w = 0; w < waves; ++w) {
-                    const rtd::SpecView V{(uint4 *)st.mid, st.lanes, (long long)w * 64};
-                    for (int l = 0; l < 64; ++l) {
-                        const uint4 a = *V.w(0, l), b = *V.w(1, l), c = *V.w(2, l), d = *V.w(3, l);
-                        if (b.w & rtd::kRecActive)
-                            std::fprintf(stderr, " w%d rec %d: pix %u f %u n %u e %u meta %u tab %08x%08x | lane state %d\n", w, l,
-                                         a.x, a.y, a.z, a.w, b.w, d.w, c.w, lanes[(size_t)w * 64 + l].state);
-                    }
-                }
-            }
-            return -7;
-        }
-        for (int w = 0; w < waves; ++w) {
-            if (done[w]) continue;
-            Lane *W = &lanes[(size_t)w * 64];
-            if (parking && park[w])   // lanes idle with a pixel park it (at their lane slot)
-                for (int l = 0; l < 64; ++l)
-                    if (W[l].state == rtd::M_IDLE && W[l].pix >= 0) {
-                        rtd::g_mega_slot = (long long)w * 64 + l;
-                        rtd::park_pixel(g_park_list.data(), (long long)w * 64 + l, W[l].pix, rtd::lane_ctr(W[l]).s,
-                                        rtd::lane_rng(W[l]), rtd::lane_sum(W[l]));
-                        W[l].pix = -1;
-                    }
-            if (!exhausted[w] && resuming) {   // the park list's slots, res_per per wave
-                for (int l = 0; l < res_per; ++l) {
-                    const long long p = (long long)w * res_per + l;
-                    if (p >= res_n) break;
-                    const rtd::Parked q = rtd::parked_item(g_park_list.data(), claim.ridx, p);
-                    if (q.pix == rtd::kNoPark) continue;
-                    rtd::g_mega_slot = (long long)w * 64 + l;
-                    rtd::mega_resume(W[l], sc, g, q, root);
-                    xk[(size_t)w * 64 + l] = 1;
-                    xs[(size_t)w * 64 + l] = q.x;
-                }
-                exhausted[w] = 1;
-            }
-            if (!exhausted[w] && g_static_per_wave > 0) {   // static allotment: wave w renders items [w*P, w*P+P)
-                for (int l = 0; l < 64 && l < g_static_per_wave; ++l) {
-                    const long long p = (long long)w * g_static_per_wave + l;
-                    if (p < n) rtd::mega_assign<!SPEC>(W[l], sc, g, order ? order[p] : (int)p, root, cnt);
-                }
-                exhausted[w] = 1;
-            }
-            if (!exhausted[w]) {
-                uint64_t m = 0;
-                for (int l = 0; l < 64; ++l) if (W[l].pix < 0) m |= 1ull << l;
-                if (m) {
-                    const long long base = queue;
-                    const int cm = __builtin_popcountll(m);
-                    queue += cm;
-                    for (int l = 0; l < 64; ++l) {
-                        if (!(m >> l & 1)) continue;
-                        const long long p = base + __builtin_popcountll(m & ((1ull << l) - 1ull));
-                        if (p < n) rtd::mega_assign<!SPEC>(W[l], sc, g, order ? order[p] : (int)p, root, cnt);
-                    }
-                    if (base + cm >= n) exhausted[w] = 1;
-                }
-            }
-            if constexpr (SPEC) {
-            if (exhausted[w] && !tail[w]) {
-                const rtd::SpecView V{(uint4 *)st.mid, st.lanes, (long long)w * 64};
-                rtd::g_mega_slot = (long long)w * 64;
-                for (int l = 0; l < 64; ++l) {
-                    rtd::g_mega_slot = (long long)w * 64 + l;
-                    rtd::spec_convert(W[l], sc, g, V, l, xk[(size_t)w * 64 + l] != 0, xs[(size_t)w * 64 + l]);
-                }
-                rtd::g_mega_slot = (long long)w * 64;
-                rtd::spec_hint_take();
-                tail[w] = 1;
-                wave_room[w] = 0;
-            }
-            if (tail[w]) {
-                rtd::g_mega_slot = (long long)w * 64;
-                wave_room[w] |= rtd::spec_hint_take();
-                bool fresh = false, idle = false;
-                for (int l = 0; l < 64; ++l) {
-                    fresh |= W[l].state == rtd::M_DONE_NEW;
-                    idle |= W[l].state == rtd::M_IDLE;
-                }
-                if (fresh || (wave_room[w] && idle)) {
-                    ++g_spec_passes;
-                    wave_room[w] = rtd::spec_manage(rtd::SpecLanes{W}, sc, g,
-                                                    rtd::SpecView{(uint4 *)st.mid, st.lanes, (long long)w * 64}, spp,
-                                                    out, root, claim);
-                }
-            }
-            }
-            bool any = false;
-            int nr = 0, nt = 0;
-            for (int l = 0; l < 64; ++l) {
-                any |= tail[w] ? W[l].state != rtd::M_IDLE : W[l].pix >= 0;
-                nr += W[l].state == rtd::M_READY || W[l].state == rtd::M_LREADY;
-                nt += W[l].state == rtd::M_TRAV || W[l].state == rtd::M_LTRAV;
-            }
-            if (!any) {
-                done[w] = 1;
-                --live;
-                continue;
-            }
-            if (parking && exhausted[w] && !park[w]) {
-                int held = 0;
-                for (int l = 0; l < 64; ++l) held += W[l].pix >= 0;
-                park[w] = held < g_park_below;
-            }
-            const bool shade_now = nr > 0 && (nr >= shade_min || nt == 0);
-            for (int l = 0; l < 64; ++l) {
-                rtd::ArrayStack S{stacks[(size_t)w * 64 + l].data()};
-                rtd::g_mega_slot = (long long)w * 64 + l;
-                if (parking)   // (parking renders do not count, as on the GPU)
-                    rtd::mega_iterate<false, decltype(S), decltype(nodes), false, LSPLIT>(
-                        W[l], shade_now, sc, g, st, spp, out, nullptr, root, S, nodes, cnt, false, (bool)park[w]);
-                else
-                    rtd::mega_iterate<!SPEC, decltype(S), decltype(nodes), false, LSPLIT>(
-                        W[l], shade_now, sc, g, st, spp, out, nullptr, root, S, nodes, cnt, (bool)tail[w]);
-            }
-        }
-    }
-    uint64_t c[7] = {cnt.rays, cnt.aabb, cnt.tri, cnt.lq, cnt.laabb, cnt.ltri, cnt.hits};
-    std::memcpy(cnt_out, c, sizeof c);
-    return 0;
-}
+// rt_mega_kernel on the host (mega_emu.h render_mega): the plain kernel, the runahead kernel (a
+// non-counting render, as on the GPU), the hand-off from one to the other, the light-split kernel.
 extern "C" int kh_render_mega(const rt_scene_view *v, int spp, int rank, int world, int row_block, int waves,
                               int shade_min, const int32_t *order, float *out, uint64_t *cnt_out) {
-    return render_mega<false>(v, spp, rank, world, row_block, waves, shade_min, order, out, cnt_out);
+    return render_mega<false, false, false>(v, spp, rank, world, row_block, waves, shade_min, order, out, cnt_out, kh_options);
 }
 extern "C" int kh_render_mega_spec(const rt_scene_view *v, int spp, int rank, int world, int row_block, int waves,
                                    int shade_min, const int32_t *order, float *out, uint64_t *cnt_out) {
-    return render_mega<false, true>(v, spp, rank, world, row_block, waves, shade_min, order, out, cnt_out);
+    return render_mega<false, true, false>(v, spp, rank, world, row_block, waves, shade_min, order, out, cnt_out, kh_options);
 }
-// Hand-off: the plain emulation over `waves` waves parks its sparse tail waves (fewer than
-// park_below pixels held once the queue is empty), then the runahead emulation over
-// `spec_waves` waves resumes the park list (resume_pct percent dealt at the start).  A
-// non-counting render (cnt_out: the counters of the plain part only).
 extern "C" int kh_render_mega_handoff(const rt_scene_view *v, int spp, int rank, int world, int row_block, int waves,
                                       int spec_waves, int shade_min, int park_below, int resume_pct,
                                       const int32_t *order, float *out, uint64_t *cnt_out, uint64_t *parked_out) {
-    g_park_below = park_below;
-    int rc = render_mega<false>(v, spp, rank, world, row_block, waves, shade_min, order, out, cnt_out);
-    g_park_below = 0;
-    if (rc) return rc;
-    uint64_t parked = 0;
-    for (size_t k = 0; k < g_park_list.size(); k += 2) parked += g_park_list[k].x != rtd::kNoPark;
-    *parked_out = parked;
-    g_resume_pct = resume_pct;
-    uint64_t c2[7];
-    rc = render_mega<false, true>(v, spp, rank, world, row_block, spec_waves, shade_min, nullptr, out, c2);
-    g_resume_pct = 0;
-    return rc;
+    return render_mega_handoff<false>(v, spp, rank, world, row_block, waves, spec_waves, shade_min, park_below, resume_pct,
+                                      order, out, cnt_out, parked_out, kh_options);
 }
 extern "C" int kh_render_mega_lsplit(const rt_scene_view *v, int spp, int rank, int world, int row_block, int waves,
                                      int shade_min, float *out, uint64_t *cnt_out) {
-    return render_mega<true>(v, spp, rank, world, row_block, waves, shade_min, nullptr, out, cnt_out);
+    return render_mega<true, false, false>(v, spp, rank, world, row_block, waves, shade_min, nullptr, out, cnt_out, kh_options);
 }
 
 // rng_skip_sample (rt_path.h, the speculative runahead's state prediction) against the

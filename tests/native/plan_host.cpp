@@ -1,6 +1,7 @@
 // plan_host.cpp — TEST ONLY: rt_launch_plan.h (the render's launch plan) behind a C interface
 // for tests/test_launch_plan.py.  The header is host only, so this builds with plain g++; the
-// resident block counts the device would report are inputs.
+// resident block counts the device would report are inputs.  ph_mode_* and ph_deal are the rules
+// the header names once for the plan, the kernel and the kernel's host emulation.
 #include <cstring>
 
 #include "../../raytracing-hw_amd/csrc/rt_launch_plan.h"
@@ -77,6 +78,17 @@ int ph_plan(const ph_in *i, ph_out *o) {
     o->per2 = g.per2;
     o->spread2 = g.spread2;
     return RT_OK;
+}
+
+int ph_mode_pack(int park_below, int resume_pct) { return rtp::mode_pack(park_below, resume_pct); }
+void ph_mode_unpack(int mode, int *park_below, int *resume_pct) {
+    *park_below = rtp::mode_park_below(mode);
+    *resume_pct = rtp::mode_resume_pct(mode);
+}
+void ph_deal(long long slots, int pct, long long waves, long long *dealt, long long *per) {
+    const rtp::Deal d = rtp::resume_deal(slots, pct, waves);
+    *dealt = d.dealt;
+    *per = d.per;
 }
 
 }  // extern "C"

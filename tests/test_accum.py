@@ -13,7 +13,8 @@ import pytest
 import rtref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "native", "accum_host.cpp")
+# (the accumulator's entry points, and the harness's options and setters they run with)
+SRC = [os.path.join(ROOT, "tests", "native", f) for f in ("accum_host.cpp", "kernel_host.cpp")]
 ACCUM_SYMBOLS = ["rt_accum_create", "rt_accum_add", "rt_accum_samples", "rt_accum_sums", "rt_accum_device_sums",
                  "rt_accum_frame_u8", "rt_accum_state", "rt_accum_save", "rt_accum_load", "rt_accum_free"]
 ERR_ARG, ERR_IO, ERR_FORMAT = -1, -2, -3
@@ -136,13 +137,15 @@ def test_cli_refuses_checkpoints_of_another_scene(rt, scene, tmp_path):
 def ah(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("ah") / "libah.so")
     subprocess.run(["g++", "-O2", "-fno-tree-vectorize", "-fno-tree-slp-vectorize", "-ffp-contract=off", "-fopenmp",
-                    "-std=c++17", "-shared", "-fPIC", SRC, "-o", out], check=True)
+                    "-std=c++17", "-shared", "-fPIC", *SRC, "-o", out], check=True)
     lib = ctypes.CDLL(out)
     V, I = ctypes.c_void_p, ctypes.c_int
     lib.kh_accum_init.argtypes = [V, I, I, I, V]
     lib.kh_accum_init.restype = None
     lib.kh_accum_pass.argtypes = [V, I, I, I, I, I, I, I, I, V, V, V]
     lib.kh_accum_pass.restype = I
+    lib.kh_set_handoff_spread.argtypes = [I]
+    lib.kh_set_handoff_spread.restype = None
     return lib
 
 
@@ -159,6 +162,22 @@ SCHEDULES = [(3, 16, (0, 0, 0)), (4, 8, (1, 1, 1)), (5, 16, (0, 1, 0)), (3, 16, 
 @pytest.mark.parametrize("waves,shade_min,modes", SCHEDULES)
 @pytest.mark.parametrize("name,w,h,s,passes", PASSES)
 def test_host_passes_match_reference(rt, ah, name, w, h, s, passes, waves, shade_min, modes):
+    _check_passes(rt, ah, name, w, h, s, passes, waves, shade_min, modes)
+
+
+@pytest.mark.parametrize("spread", [1, 0])
+@pytest.mark.parametrize("name,w,h,s,passes", PASSES[:2])
+def test_host_handoff_passes_with_and_without_spread(rt, ah, name, w, h, s, passes, spread):
+    """The hand-off schedule with the resume launch's spread map (RT_HANDOFF_SPREAD: the parked
+    records dealt heaviest first, one per wave) and in park-list slot order: the same sums."""
+    ah.kh_set_handoff_spread(spread)
+    try:
+        _check_passes(rt, ah, name, w, h, s, passes, *SCHEDULES[3])
+    finally:
+        ah.kh_set_handoff_spread(1)
+
+
+def _check_passes(rt, ah, name, w, h, s, passes, waves, shade_min, modes):
     want = rtref.golden(f"{name}_sums_{w}x{h}x{s}.rtd")["sums"].reshape(h * w, 3)
     v, keep = rt.make_view(rtref.ref_arrays(rt, name, w, h, s))
     chain = np.zeros((w * h, 8), np.uint32)

@@ -3,8 +3,10 @@ tests/native/plan_host.cpp): which kernel instantiation, schedule, work units, p
 grid launch() chooses, and what it refuses.  Resident block counts are inputs: 1280 for the
 plain kernel and 1024 for the runahead kernel (256 CUs at 5 and 4 blocks)."""
 import ctypes
+import math
 import os
 import subprocess
+from fractions import Fraction
 
 import pytest
 
@@ -53,6 +55,7 @@ def ph(tmp_path_factory):
         rc = lib.ph_plan(ctypes.byref(i), ctypes.byref(o))
         assert rc == o.err
         return o
+    plan.lib = lib
     return plan
 
 
@@ -83,9 +86,52 @@ def test_runahead_up_to_two_pixels_per_lane_then_handoff(ph, n_pixels, spec):
         assert n_pixels == 518400
 
 
+def test_mode_word_round_trips(ph):
+    vals = (0, 1, 56, 100, 255)
+    below, pct = ctypes.c_int(-1), ctypes.c_int(-1)
+    words = set()
+    for b in vals:
+        for p in vals:
+            mode = ph.lib.ph_mode_pack(b, p)
+            ph.lib.ph_mode_unpack(mode, ctypes.byref(below), ctypes.byref(pct))
+            assert (below.value, pct.value) == (b, p)
+            words.add(mode)
+    assert len(words) == len(vals) ** 2 and ph.lib.ph_mode_pack(0, 0) == 0   # (0: the default schedules)
+
+
+# (slots, pct, waves) -> (dealt, per): the resume launch's deal (rt_launch_plan.h resume_deal),
+# worked out by hand, and again below in exact fractions
+DEALS = [
+    ((327680, 100, 4096), (327680, 64)),   # the headline: 80 a wave, capped at one per lane
+    ((25600, 100, 4096), (25600, 7)),      # 6.25 a wave rounds up
+    ((768, 100, 4096), (768, 1)),          # fewer slots than waves: 0.19 a wave rounds up
+    ((0, 100, 4096), (0, 1)),              # nothing parked: per forced up to 1
+    ((100, 0, 4), (0, 1)),                 # nothing dealt: per forced up to 1
+    ((192, 100, 3), (192, 64)),            # exactly 64 a wave
+    ((193, 100, 3), (193, 64)),            # 64.3 a wave: capped at 64
+    ((101, 50, 4), (51, 13)),              # 50.5 rounds up to 51 dealt; 12.75 a wave rounds up
+    ((7, 60, 2), (5, 3)),                  # 4.2 rounds up to 5 dealt; 2.5 a wave rounds up
+    ((10, 50, 5), (5, 1)),                 # exact: no rounding
+    ((1000, 1, 4), (10, 3)),
+]
+
+
+def test_resume_deal_table(ph):
+    ph.lib.ph_deal.argtypes = [ctypes.c_longlong, ctypes.c_int, ctypes.c_longlong,
+                               ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    ph.lib.ph_deal.restype = None
+    dealt, per = ctypes.c_longlong(-1), ctypes.c_longlong(-1)
+    for (slots, pct, waves), want in DEALS:
+        ph.lib.ph_deal(slots, pct, waves, ctypes.byref(dealt), ctypes.byref(per))
+        assert (dealt.value, per.value) == want, (slots, pct, waves)
+        d = math.ceil(Fraction(slots * pct, 100))
+        assert want == (d, min(64, max(1, math.ceil(Fraction(d, waves))))), (slots, pct, waves)
+    assert {1, 64} <= {w[1] for _, w in DEALS}   # both clamps are in the table
+
+
 def test_handoff_relaunch_deal_is_the_kernels_resume_formula(ph):
-    # rt_mega_kernel's resume site: waves of the grid, dealt = ceil(items * pct / 100),
-    # per = min(64, max(1, ceil(dealt / waves))), with RT_HANDOFF_PCT 100
+    # plan_grid deals the main launch's slots over the runahead kernel's resident waves with
+    # RT_HANDOFF_PCT 100 (test_resume_deal_table pins the rule itself)
     for blocks in (PLAIN_BLOCKS, 100, 3):
         o = ph(600000, variant_blocks=blocks)
         slots = blocks * 256
