@@ -52,7 +52,9 @@ typedef struct rt_scene rt_scene; /* opaque: host arrays + lazily uploaded devic
  * Triangles and BVH nodes are in the reference's post-build order (bvh.cpp:166 reorders
  * `objects` in place), so object ids equal the reference's Intersection::object_id. */
 typedef struct {
-    int32_t width, height, samples, ray_depth; /* canvas, spp (scene_parser.cpp:16-22)   */
+    int32_t width, height, samples, ray_depth; /* canvas, spp (scene_parser.cpp:16-22); a render
+                                                  of a ray_depth outside 1..15 is RT_ERR_LIMIT,
+                                                  before any launch                          */
     float max_distance;                        /* camera zfar or 1e9 (scene_parser.cpp:119) */
     float cam_pos[3];                          /* camera.h position_                        */
     float cam_axes[9];                         /* right, up, forward (camera.h axes_)       */

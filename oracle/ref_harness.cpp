@@ -10,9 +10,10 @@
 //  — the per-pixel-reset convention every build component follows.
 //
 // Modes (all print one JSON line on stdout, after the reference's own log lines):
-//   sums    <gltf> W H spp out.rtd [threads [out.ppm]]
+//   sums    <gltf> W H spp out.rtd [threads [out.ppm [ray_depth]]]
 //                                              per-pixel float RGB sums (scene.cpp:20,42) + counters
-//                                              (+ the reference's finished frame of them)
+//                                              (+ the reference's finished frame of them; ray_depth
+//                                              sets Scene::ray_depth, scene.h:24, "-" = no ppm)
 //   time    <gltf> W H spp [rows [stride]]     time Scene::render itself (scene.cpp:17-65)
 //   rays    <gltf> W H n out.rtd               closest-hit known answers (bvh.cpp:239-243) + per-ray test counts
 //   dump    <gltf> W H out.rtd                 post-BVH scene arrays (bvh.cpp:166 reorders objects)
@@ -157,10 +158,15 @@ static void finish_to_ppm(const std::vector<float> &sums, int W, int H, int spp,
 }
 
 static int mode_sums(int argc, char **argv) {
-    if (argc < 7) throw std::runtime_error("sums <gltf> W H spp out.rtd [threads [out.ppm]]");
+    if (argc < 7) throw std::runtime_error("sums <gltf> W H spp out.rtd [threads [out.ppm [ray_depth]]]");
     int W = atoi(argv[3]), H = atoi(argv[4]), spp = atoi(argv[5]);
     int threads = argc > 7 ? atoi(argv[7]) : omp_get_max_threads();
     Scene s = parse_scene_gltf(argv[2], W, H, spp);
+    if (argc > 9) {
+        const int depth = atoi(argv[9]);
+        if (depth < 1) throw std::runtime_error("sums: ray_depth must be positive");
+        s.ray_depth = depth;   // render_pixel starts every sample at r.power = s.ray_depth (scene.cpp:39)
+    }
     std::vector<float> out((size_t)W * H * 3);
     reset_counters();
     double t0 = now_s();
@@ -178,7 +184,8 @@ static int mode_sums(int argc, char **argv) {
     std::vector<uint64_t> cv{c.rays, c.aabb, c.tri, c.lqueries, c.laabb, c.ltri};
     d.put("counters", cv);
     d.close();
-    if (argc > 8) finish_to_ppm(out, W, H, spp, argv[8]);   // the reference's final image of these sums
+    if (argc > 8 && std::strcmp(argv[8], "-") != 0)
+        finish_to_ppm(out, W, H, spp, argv[8]);   // the reference's final image of these sums
     print_counts("sums", c, t1 - t0, threads);
     return 0;
 }

@@ -22,6 +22,10 @@ the reference's accessor budgets:
                          Textures are procedural RGBA8 written as binary PPM (P6), which
                          stb_image (reference) and this build's loader both decode.
 * ``sponza_mini``     — the same generator with budgets /32 and 16x16 textures (parity tests).
+* ``texedge``         — not from the reference's examples: a closed room seen from inside with
+                         textures of odd sizes (1x1 to 13x6) in all four material slots, the
+                         emissive one included, UVs over about [-3, 4], four constant-UV quads
+                         and a camera zfar that cuts the room's far end (edge-case parity tests).
 
 The textures are read by the reference through tinygltf/stb_image with ``req_comp=4``
 (thirdparty/tinygltf/tiny_gltf.h:2609), i.e. RGBA8 with alpha 255 for P6 input.
@@ -656,6 +660,117 @@ def make_sponza(directory: str, tri_scale: float = 1.0, tex_size: int = 1024, na
     return b.write(directory, name)
 
 
+# texedge: the texture and zfar edges no other fixture reaches (tests/test_gpu_edges.py).
+# (width, height, role) of its PPM textures: none is a multiple of 4 on both sides, 1-texel
+# sides take the sampler's two-step wrap, and every one that is sampled is not square.
+TEXEDGE_TEXTURES = [(1, 1, "mr"), (1, 7, "base"), (5, 1, "base"), (5, 3, "normal"), (13, 6, "base"), (7, 9, "base"),
+                    (6, 13, "emissive"), (9, 4, "emissive")]
+# the four quads facing the camera whose three vertices share one UV: p - floor(p) rounding to
+# 1.0, the exact upper edge, the origin, and the largest float below 1 with a negative integer
+TEXEDGE_CONST_UVS = [(-1e-9, -1e-9), (1.0, 1.0), (0.0, 0.0), (0.99999994, -2.0)]
+TEXEDGE_ZFAR = 5.3
+TEXEDGE_CAMERA_Z = 1.2
+
+
+def quad_mesh(origin, eu, ev, nu: int, nv: int, uv0, uv1):
+    """Planar quad origin + s*eu + t*ev (s, t in [0, 1]) as nu x nv cells: normal eu x ev,
+    tangent along eu, UVs from uv0 to uv1 (equal: every vertex gets that one UV)."""
+    origin, eu, ev = (np.asarray(x, np.float64) for x in (origin, eu, ev))
+    s, t = np.meshgrid(np.linspace(0.0, 1.0, nu + 1), np.linspace(0.0, 1.0, nv + 1), indexing="xy")
+    pos = origin + s[..., None] * eu + t[..., None] * ev
+    n = np.cross(eu, ev)
+    n /= np.linalg.norm(n)
+    cnt = (nu + 1) * (nv + 1)
+    uv = np.stack([np.float32(uv0[0]) + s.astype(F32) * (np.float32(uv1[0]) - np.float32(uv0[0])),
+                   np.float32(uv0[1]) + t.astype(F32) * (np.float32(uv1[1]) - np.float32(uv0[1]))], -1)
+    tan = np.concatenate([eu / np.linalg.norm(eu), [1.0]])
+    I = []
+    for j in range(nv):
+        for i in range(nu):
+            v00 = j * (nu + 1) + i
+            v10, v01, v11 = v00 + 1, v00 + nu + 1, v00 + nu + 2
+            I += [v00, v10, v11, v00, v11, v01]
+    return (pos.reshape(-1, 3).astype(F32), np.tile(n, (cnt, 1)).astype(F32), uv.reshape(-1, 2).astype(F32),
+            np.tile(tan, (cnt, 1)).astype(F32), np.array(I, np.uint32))
+
+
+def _texedge_texture(img: int, w: int, h: int, role: str) -> np.ndarray:
+    """Seeded random texels (every texel differs from its neighbours, so one wrong address
+    changes the frame); normal maps stay near +z, roughness stays away from mirrors."""
+    rng = np.random.default_rng(20261019 + img)
+    rgb = rng.integers(0, 256, (h, w, 3))
+    if role == "normal":
+        rgb = np.stack([128 + (rgb[..., 0] - 128) // 3, 128 + (rgb[..., 1] - 128) // 3, 215 + rgb[..., 2] % 40], -1)
+    elif role == "mr":
+        rgb = np.stack([rgb[..., 0] * 0, 90 + rgb[..., 1] % 160, rgb[..., 2] // 2], -1)
+    elif role == "base":
+        rgb = 120 + rgb % 136
+    return rgb.astype(np.uint8)
+
+
+def make_texedge(directory: str) -> str:
+    """A closed room (4 x 3 x 7) seen from inside, lit by an emissive ceiling quad: textures of
+    odd sizes in all four material slots, UVs over about [-3, 4], four constant-UV quads in
+    front of the camera and a camera zfar that cuts the room's far end."""
+    b = GltfBuilder()
+    b.extensions_used.add(_EMISSIVE)
+    os.makedirs(directory, exist_ok=True)
+    for img, (w, h, role) in enumerate(TEXEDGE_TEXTURES):
+        fname = f"texedge_tex{img:02d}.ppm"
+        b.images.append({"name": f"tex{img:02d}", "uri": fname})
+        write_ppm(os.path.join(directory, fname), _texedge_texture(img, w, h, role))
+    b.textures = [{"sampler": 0, "source": s} for s in range(len(TEXEDGE_TEXTURES))]
+    b.cameras = [{"name": "Camera", "type": "perspective", "perspective": {
+        "aspectRatio": 40 / 24, "yfov": 0.9, "zfar": TEXEDGE_ZFAR, "znear": 0.1}}]
+    b.nodes = [{"camera": 0, "name": "Camera", "translation": [0, 0, TEXEDGE_CAMERA_Z]}]
+
+    def material(name, base=None, normal=None, mr=None, emissive=None, factor=(0.9, 0.9, 0.9), metallic=0.0,
+                 roughness=1.0, emission=None, strength=None):
+        pbr = {"baseColorFactor": list(factor) + [1], "metallicFactor": metallic, "roughnessFactor": roughness}
+        if base is not None:
+            pbr["baseColorTexture"] = {"index": base}
+        if mr is not None:
+            pbr["metallicRoughnessTexture"] = {"index": mr}
+        m = {"doubleSided": True, "name": name, "pbrMetallicRoughness": pbr}
+        if normal is not None:
+            m["normalTexture"] = {"index": normal}
+        if emissive is not None:
+            m["emissiveTexture"] = {"index": emissive}
+        if emission is not None:
+            m["emissiveFactor"] = list(emission)
+        if strength is not None:
+            m["extensions"] = {_EMISSIVE: {"emissiveStrength": strength}}
+        b.materials.append(m)
+        return len(b.materials) - 1
+
+    def add(name, mat, mesh):
+        pos, nrm, uv, tan, idx = mesh
+        b.nodes.append({"mesh": b.mesh(name, [b.primitive(pos, nrm, idx, mat, uv=uv, tan=tan)]), "name": name})
+
+    x0, x1, y0, y1, z0, z1 = -2.0, 2.0, -1.5, 1.5, -5.0, 2.0
+    lo, hi = (-3.0, -2.5), (4.0, 3.5)
+    add("Floor", material("Floor", base=4, normal=3, mr=0, metallic=0.6),
+        quad_mesh([x0, y0, z1], [x1 - x0, 0, 0], [0, 0, z0 - z1], 3, 3, lo, hi))
+    add("Ceiling", material("Ceiling", base=5, mr=7, metallic=0.3),
+        quad_mesh([x0, y1, z0], [x1 - x0, 0, 0], [0, 0, z1 - z0], 3, 3, lo, hi))
+    add("Back", material("Back", base=5, normal=3),
+        quad_mesh([x0, y0, z0], [x1 - x0, 0, 0], [0, y1 - y0, 0], 3, 3, lo, hi))
+    add("Left", material("Left", base=1, normal=3, mr=7, metallic=0.5),
+        quad_mesh([x0, y0, z1], [0, 0, z0 - z1], [0, y1 - y0, 0], 3, 3, lo, hi))
+    add("Right", material("Right", base=2, emissive=6, emission=(0.4, 0.4, 0.4)),
+        quad_mesh([x1, y0, z0], [0, 0, z1 - z0], [0, y1 - y0, 0], 3, 3, lo, hi))
+    add("Front", material("Front", base=4),
+        quad_mesh([x1, y0, z1], [x0 - x1, 0, 0], [0, y1 - y0, 0], 3, 3, lo, hi))
+    add("Light", material("Light", emissive=7, factor=(0, 0, 0), emission=(1, 1, 1), strength=6.0),
+        quad_mesh([-0.7, 1.45, -1.4], [1.4, 0, 0], [0, 0, 2.0], 2, 2, lo, hi))
+    quads = [material("QuadA", base=1), material("QuadB", base=2, mr=7, metallic=0.5),
+             material("QuadC", base=4, normal=3), material("QuadD", base=5, emissive=6, emission=(0.5, 0.5, 0.5))]
+    for k, (uv, mat) in enumerate(zip(TEXEDGE_CONST_UVS, quads)):
+        cx, cy = (-0.5, 0.5)[k % 2], (0.42, -0.42)[k // 2]
+        add(f"Quad{k}", mat, quad_mesh([cx - 0.27, cy - 0.27, -1.0], [0.54, 0, 0], [0, 0.54, 0], 1, 1, uv, uv))
+    return b.write(directory, "texedge")
+
+
 SCENES = {
     "cornell": lambda d: make_cornell(d),
     "cornell_blob": lambda d: make_cornell_blob(d),
@@ -666,6 +781,7 @@ SCENES = {
     "sponza_dragon": lambda d: make_sponza(d, dragon=True, name="sponza_dragon"),
     "sponza_dragon_mini": lambda d: make_sponza(d, tri_scale=1.0 / 32, tex_size=16, name="sponza_dragon_mini",
                                                 dragon=True),
+    "texedge": lambda d: make_texedge(d),
 }
 
 

@@ -124,6 +124,36 @@ def ref_arrays(rt, name, width, height, spp, dump=None, path=None):
     return a
 
 
+# Ray-depth variants of the goldens (ref_harness `sums` with Scene::ray_depth set, written by
+# tools/make_goldens.py --edges): (scene, W, H, spp, ray_depth)
+DEPTH_CASES = [("texedge", 40, 24, 6, 1), ("texedge", 40, 24, 6, 2), ("texedge", 40, 24, 6, 15),
+               ("cornell", 33, 17, 8, 15)]
+
+
+def sums_golden(name, w, h, s, depth=None):
+    """The reference's sums golden of a frame; depth: its ray-depth variant."""
+    return golden(f"{name}_sums_{w}x{h}x{s}" + (f"_d{depth}" if depth else "") + ".rtd")
+
+
+def with_depth(arrays, depth):
+    a = dict(arrays)
+    a["ray_depth"] = int(depth)
+    return a
+
+
+def pixel_centre_rays(arrays):
+    """Camera rays through every pixel centre (Camera::cast_in_pixel with zero offsets,
+    camera.cpp:49-62), row-major: (origins, directions)."""
+    w, h = int(arrays["width"]), int(arrays["height"])
+    i, j = np.meshgrid(np.arange(w, dtype=np.float32), np.arange(h, dtype=np.float32))
+    tan = np.asarray(arrays["tan_half_fov"], np.float32)
+    tx = (np.float32(2) * (i + np.float32(0.5)) / np.float32(w) - 1) * tan[0]
+    ty = -(np.float32(2) * (j + np.float32(0.5)) / np.float32(h) - 1) * tan[1]
+    ax = np.asarray(arrays["cam_axes"], np.float32).reshape(3, 3)
+    dirs = (tx[..., None] * ax[0] + ty[..., None] * ax[1] + ax[2]).reshape(-1, 3).astype(np.float32)
+    return np.tile(np.asarray(arrays["cam_pos"], np.float32), (w * h, 1)), dirs
+
+
 class Oracle:
     """ctypes front of oracle/liboracle.so (the CPU restatement)."""
 

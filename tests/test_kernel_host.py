@@ -20,7 +20,7 @@ import rtref
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "kernel_host.cpp")
 CASES = [("cornell", 33, 17, 3), ("cornell", 64, 64, 8), ("cornell_blob", 48, 48, 4),
-         ("practice6_1", 256, 256, 4), ("sponza_mini", 64, 36, 4)]
+         ("practice6_1", 256, 256, 4), ("sponza_mini", 64, 36, 4), ("texedge", 40, 24, 6)]
 
 
 def _build_kh(tmp_path_factory, *defines):
@@ -135,7 +135,7 @@ def test_rng_sequences_match_reference(kh):
 
 
 @pytest.mark.parametrize("name,w,h,s,waves,shade_min", [("cornell_blob", 48, 48, 4, 2, 32), ("sponza_mini", 64, 36, 4, 3, 1),
-                                                        ("cornell", 33, 17, 3, 1, 64)])
+                                                        ("cornell", 33, 17, 3, 1, 64), ("texedge", 40, 24, 6, 2, 48)])
 def test_lane_resident_emulation(rt, kh, name, w, h, s, waves, shade_min):
     """Kernel 4 (rt_mega.h): lanes own whole pixels, traversal steps per iteration, batched
     shading; bit-exact sums and counters."""
@@ -151,7 +151,8 @@ def test_lane_resident_emulation(rt, kh, name, w, h, s, waves, shade_min):
 
 @pytest.mark.parametrize("name,w,h,s,waves,world", [("cornell_blob", 48, 48, 4, 2, 1), ("sponza_mini", 64, 36, 4, 3, 1),
                                                     ("cornell", 33, 17, 3, 1, 1), ("practice6_1", 256, 256, 4, 40, 1),
-                                                    ("sponza_mini", 64, 36, 4, 40, 1), ("sponza_mini", 64, 36, 4, 2, 3)])
+                                                    ("sponza_mini", 64, 36, 4, 40, 1), ("sponza_mini", 64, 36, 4, 2, 3),
+                                                    ("texedge", 40, 24, 6, 2, 1), ("texedge", 40, 24, 6, 20, 3)])
 def test_lane_resident_runahead_emulation(rt, kh, name, w, h, s, waves, world):
     """Speculative sample runahead (rt_mega.h spec_*): once the pixel queue is empty a wave's
     idle lanes run later samples of its unfinished pixels from predicted start states, and
@@ -230,7 +231,7 @@ def test_lane_resident_any_pixel_order(rt, kh, name, w, h, s, waves):
 
 
 @pytest.mark.parametrize("name,w,h,s,waves,shade_min", [("practice6_1", 256, 256, 4, 6, 48), ("sponza_mini", 64, 36, 4, 3, 1),
-                                                        ("cornell", 33, 17, 3, 1, 64)])
+                                                        ("cornell", 33, 17, 3, 1, 64), ("texedge", 40, 24, 6, 2, 48)])
 def test_lane_resident_light_split_emulation(rt, kh, name, w, h, s, waves, shade_min):
     """Light-split kernel (rt_mega.h light_step / mega_shade_split): the
     light pdf's light-BVH walk as a lane state between shade_pre and shade_post; bit-exact
@@ -259,6 +260,60 @@ def test_lane_resident_leaf_triangles(rt, tmp_path_factory, leaf_n):
                                    cnt.ctypes.data) == 0
         assert np.array_equal(rtref.bits(out), rtref.bits(want))
         assert list(cnt[:6]) == list(cnt_want)
+
+
+@pytest.mark.parametrize("name,w,h,s,depth", rtref.DEPTH_CASES)
+def test_depth_variants_match_reference(rt, kh, name, w, h, s, depth):
+    """Ray depths 1, 2 and 15 against the reference's sums and counters with Scene::ray_depth
+    set: the pixel schedule, the wavefront schedule, and the lane-resident emulation plain,
+    with the light split and with runahead (whole frame and 3-way shards)."""
+    g = rtref.sums_golden(name, w, h, s, depth)
+    want, cnt_want = g["sums"].reshape(h * w, 3), list(g["counters"])
+    v, keep = rt.make_view(rtref.with_depth(rtref.ref_arrays(rt, name, w, h, s), depth))
+    A = ctypes.addressof(v)
+
+    def fresh(n=h * w):
+        return np.zeros((n, 3), np.float32), np.zeros(7, np.uint64)
+
+    out, cnt = fresh()
+    kh.kh_render(A, s, 0, w * h, out.ctypes.data, cnt.ctypes.data)
+    assert np.array_equal(rtref.bits(out), rtref.bits(want)) and list(cnt[:6]) == cnt_want
+    out, cnt = fresh()
+    it = np.zeros(1, np.int64)
+    assert kh.kh_render_wf(A, s, 0, 1, 8, out.ctypes.data, cnt.ctypes.data, it.ctypes.data) == 0
+    assert np.array_equal(rtref.bits(out), rtref.bits(want)) and list(cnt[:6]) == cnt_want
+    assert it[0] <= s * depth + 1
+    out, cnt = fresh()
+    assert kh.kh_render_mega(A, s, 0, 1, 8, 2, 48, None, out.ctypes.data, cnt.ctypes.data) == 0
+    assert np.array_equal(rtref.bits(out), rtref.bits(want)) and list(cnt[:6]) == cnt_want
+    out, cnt = fresh()
+    assert kh.kh_render_mega_lsplit(A, s, 0, 1, 8, 2, 48, out.ctypes.data, cnt.ctypes.data) == 0
+    assert np.array_equal(rtref.bits(out), rtref.bits(want)) and list(cnt[:6]) == cnt_want
+    kh.kh_render_mega_spec.argtypes = kh.kh_render_mega.argtypes
+    kh.kh_render_mega_spec.restype = ctypes.c_int
+    for world, waves in ((1, 2), (3, 20)):
+        for rank in range(world):
+            rows = rt.shard_rows(h, rank, world, 8)
+            out, cnt = fresh(len(rows) * w)
+            assert kh.kh_render_mega_spec(A, s, rank, world, 8, waves, 48, None, out.ctypes.data, cnt.ctypes.data) == 0
+            assert np.array_equal(rtref.bits(out), rtref.bits(want.reshape(h, w, 3)[rows].reshape(-1, 3))), (world, rank)
+
+
+@pytest.mark.parametrize("name,w,h,s", [("texedge", 40, 24, 6), ("cornell", 33, 17, 8)])
+def test_depth_15_frames_reach_every_path_length(rt, kh, name, w, h, s):
+    """Precondition of the depth-15 parity tests: in each depth-15 frame every path length
+    1..15 (vertices shaded, kh_v_trace) occurs in at least 8 samples, so every batch shape of
+    the four-at-a-time record folds and the last vertex count the packed counters hold run."""
+    v, keep = rt.make_view(rtref.with_depth(rtref.ref_arrays(rt, name, w, h, s), 15))
+    pix = np.arange(w * h, dtype=np.int64)
+    nv = np.zeros(w * h * s, np.uint8)
+    cost = np.zeros(w * h * s, np.uint32)
+    kh.kh_v_trace.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 3
+    kh.kh_v_trace.restype = None
+    kh.kh_v_trace(ctypes.addressof(v), s, len(pix), pix.ctypes.data, nv.ctypes.data, cost.ctypes.data)
+    hist = np.bincount(nv, minlength=16)
+    print(f"{name}: samples by path length 0..15: {hist.tolist()}")
+    assert len(hist) == 16 and hist[1:].min() >= 8, hist.tolist()
 
 
 def test_box_pair_matches_single_box_test(kh):

@@ -14,7 +14,7 @@ import pytest
 
 import rtref
 
-EXACT = ["cornell", "sponza_mini", "cornell_blob", "practice6_1"]
+EXACT = ["cornell", "sponza_mini", "cornell_blob", "practice6_1", "texedge"]
 ROTATED = ["cornell_blob", "practice6_1"]
 KEYS = ["tri", "tri_attr", "tri_tan", "node", "light", "light_node", "mesh_f", "mesh_tex", "mesh_normal_transform"]
 
@@ -67,20 +67,43 @@ def test_slp_evidence(rt, tmp_path, name):
 
 
 def test_texels_match_reference(rt):
-    name = "sponza_mini"
-    mine = _mine(rt, name)
-    d = rtref.golden(f"{name}_dump.rtd")
-    info = np.asarray(mine["tex_info"])
-    tex = np.asarray(mine["texels"])
-    assert len(info) == len(d["tex_fnv1a"])
-    for (off, w, h, ch), (rw, rh, rch), want in zip(info, d["tex_dim"], d["tex_fnv1a"]):
-        assert (w, h) == (rw, rh)
-        # texels are stored RGBA8 from texel `off`; the reference keeps `channels` bytes per texel
-        px = tex[4 * int(off):4 * (int(off) + int(w) * int(h))].reshape(-1, 4)[:, :int(rch)]
-        hsh = 1469598103934665603
-        for byte in px.reshape(-1).tobytes():
-            hsh = ((hsh ^ byte) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-        assert hsh == int(want)
+    """Decoded texels of every texture, by FNV-1a hash: sponza_mini's 69 16x16 images and
+    texedge's eight odd sizes (1x1 to 13x6)."""
+    for name in ("sponza_mini", "texedge"):
+        mine = _mine(rt, name)
+        d = rtref.golden(f"{name}_dump.rtd")
+        info = np.asarray(mine["tex_info"])
+        tex = np.asarray(mine["texels"])
+        assert len(info) == len(d["tex_fnv1a"])
+        for (off, w, h, ch), (rw, rh, rch), want in zip(info, d["tex_dim"], d["tex_fnv1a"]):
+            assert (w, h) == (rw, rh)
+            # texels are stored RGBA8 from texel `off`; the reference keeps `channels` bytes per texel
+            px = tex[4 * int(off):4 * (int(off) + int(w) * int(h))].reshape(-1, 4)[:, :int(rch)]
+            hsh = 1469598103934665603
+            for byte in px.reshape(-1).tobytes():
+                hsh = ((hsh ^ byte) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+            assert hsh == int(want), name
+
+
+def test_texedge_fixture_covers_its_edges(rt):
+    """The texedge fixture as the reference parsed it: the eight texture sizes (none a
+    multiple of 4 on both sides), every one of the four material slots in use, UVs over about
+    [-3, 4], the four constant-UV quads, and a zfar inside the room."""
+    sc = rtref.scenes_module()
+    d = rtref.golden("texedge_dump.rtd")
+    assert [(int(w), int(h)) for w, h, _ in d["tex_dim"]] == [(w, h) for w, h, _ in sc.TEXEDGE_TEXTURES]
+    assert (d["mesh_tex"] >= 0).any(0).all()
+    used = set(int(t) for t in d["mesh_tex"].reshape(-1) if t >= 0)
+    assert used == set(range(len(sc.TEXEDGE_TEXTURES)))
+    uv = d["obj_texcoord"].reshape(-1, 2)
+    assert uv.min() <= -2.9 and uv.max() >= 3.9
+    const = set()
+    for t in d["obj_texcoord"]:
+        if (t == t[0]).all():
+            const.add((float(t[0, 0]), float(t[0, 1])))
+    assert const == {(float(np.float32(u)), float(np.float32(v))) for u, v in sc.TEXEDGE_CONST_UVS}
+    assert np.any(d["obj_tangent"])
+    assert float(_mine(rt, "texedge")["max_distance"]) == float(np.float32(sc.TEXEDGE_ZFAR))
 
 
 def test_scene_generator_deterministic(tmp_path):
@@ -91,6 +114,12 @@ def test_scene_generator_deterministic(tmp_path):
     import os
     for f in sorted(os.listdir(os.path.dirname(a))):
         assert filecmp.cmp(os.path.join(os.path.dirname(a), f), os.path.join(os.path.dirname(b), f), shallow=False), f
+    # the committed texedge fixture is what the generator writes
+    c = os.path.dirname(sc.SCENES["texedge"](str(tmp_path / "c")))
+    committed = os.path.dirname(rtref.scene_path("texedge"))
+    assert sorted(os.listdir(c)) == sorted(os.listdir(committed))
+    for f in sorted(os.listdir(c)):
+        assert filecmp.cmp(os.path.join(c, f), os.path.join(committed, f), shallow=False), f
 
 
 def test_loader_errors(rt, tmp_path):

@@ -28,6 +28,10 @@ Outputs (tests/golden/):
                                       scenes in this build's layout (pins the loader)
 
     python tools/make_goldens.py --configs   # only the BASELINE-config fixtures
+    python tools/make_goldens.py --edges     # only the texedge scene and the ray-depth variants
+                                             # (EDGE_SUMS; their metadata goes to edges_meta.json,
+                                             # no other file under tests/golden/ is touched)
+    <name>_sums_<W>x<H>x<S>_d<D>.rtd        the same sums with Scene::ray_depth = D
 """
 import hashlib
 import importlib.util
@@ -252,7 +256,41 @@ def shipped_goldens(meta):
                                                    "log": r.stdout.strip().splitlines()[-2:]}
 
 
+# --edges: (scene, W, H, spp, ray_depth or None for the scene's own, keep the finished ppm)
+EDGE_SUMS = [("texedge", 40, 24, 6, None, True), ("texedge", 40, 24, 6, 1, False), ("texedge", 40, 24, 6, 2, False),
+             ("texedge", 40, 24, 6, 15, False), ("cornell", 33, 17, 8, 15, True)]
+EDGE_RAYS = 1500
+
+
+def edge_goldens():
+    """The texedge fixture (scene files, dump, rays, sums) and the ray-depth variants of
+    texedge and cornell.  Writes only files that did not exist before this mode did."""
+    name = "texedge"
+    sdir = os.path.join(GOLD, "scenes", name)
+    if os.path.isdir(sdir):
+        shutil.rmtree(sdir)
+    gltf = scenes.SCENES[name](sdir)
+    raw = os.path.join("/tmp", f"{name}_dump_full.rtd")
+    meta = {name: {"dump": harness("dump", gltf, 64, 64, raw)}}
+    compact_dump(raw, os.path.join(GOLD, f"{name}_dump.rtd"))
+    meta[name]["rays"] = harness("rays", gltf, 64, 64, EDGE_RAYS, os.path.join(GOLD, f"{name}_rays.rtd"))
+    for scene, w, h, s, depth, keep_ppm in EDGE_SUMS:
+        tag = f"{w}x{h}x{s}" + (f"_d{depth}" if depth else "")
+        out = os.path.join(GOLD, f"{scene}_sums_{tag}.rtd")
+        ppm = os.path.join(GOLD, f"{scene}_{tag}.ppm") if keep_ppm else "-"
+        args = ["sums", os.path.join(GOLD, "scenes", scene, scene + ".gltf"), w, h, s, out, 8, ppm]
+        meta.setdefault(scene, {})[f"sums_{tag}"] = harness(*args, *([depth] if depth else []))
+    with open(os.path.join(GOLD, "edges_meta.json"), "w") as f:
+        json.dump(meta, f, indent=1, sort_keys=True)
+    print(json.dumps(meta, indent=1))
+
+
 def main():
+    if "--edges" in sys.argv:
+        if not os.path.exists(HARNESS):
+            sys.exit("build the reference harness first: make -C oracle ref")
+        edge_goldens()
+        return
     if "--shipped" in sys.argv:
         path = os.path.join(GOLD, "golden_meta.json")
         meta = json.load(open(path))
@@ -319,6 +357,7 @@ def main():
     with open(os.path.join(GOLD, "golden_meta.json"), "w") as f:
         json.dump(meta, f, indent=1, sort_keys=True)
     print(json.dumps(meta, indent=1)[:2000])
+    edge_goldens()
 
 
 if __name__ == "__main__":
