@@ -259,6 +259,74 @@ int rt_accum_save(rt_accum *accum, const char *path);
 int rt_accum_load(rt_scene *scene, int32_t device, const char *path, rt_accum **out);
 void rt_accum_free(rt_accum *accum);
 
+/* --- per-pixel sample counts: subset passes and adaptive refinement (additive in ABI 6) --- */
+/* Every pixel's record carries its own next sample, so a pass may render a subset of the shard:
+ * a window, a mask, the pixels below a sample count, the pixels an error estimate still calls
+ * noisy.  The invariant carries over: after any sequence of full and subset passes, a pixel that
+ * has n samples holds exactly the sum rt_render gives that pixel at spp = n.
+ *
+ * The subset is chosen on the device (rt_accum_select) and rendered by the next
+ * rt_accum_add_selected; a caller never hands in a pixel list.  (Liveness: a listed pixel whose
+ * record is at or past the pass's end sample would never finish, and a pixel listed twice would
+ * be raced by two lanes.  The selection's rule includes next < target and emits every pixel at
+ * most once.)  A pending selection is dropped by every pass (rt_accum_add,
+ * rt_accum_add_selected), which change the records it was made from; a new or loaded
+ * accumulator has none.  rt_accum_mark changes no record and leaves it pending, so the
+ * adaptive loop is select, mark, add_selected.
+ *
+ * The rule, per owned pixel (csrc/rt_select.h is its text, shared by the device and the CPU
+ * test; f32 arithmetic in the order written).  n_b = the pixel's sample count, S_b = its sum;
+ * n_a, S_a = both at the last rt_accum_mark (n_a = 0 without one):
+ *   1. outside the window, mask byte 0, or n_b >= target                   -> not selected
+ *   2. threshold <= 0                                                      -> selected
+ *   3. n_b == 0 or n_a == 0 (no estimate yet)                              -> selected
+ *      n_b == n_a (no sample since it was last judged: convergence sticks) -> not selected
+ *   4. per channel ma = S_a / n_a, mn = (S_b - S_a) / (n_b - n_a), mb = S_b / n_b (each as a
+ *      product with the f32 reciprocal of the count), d = |mn - ma|;
+ *      e = ((d_r + d_g) + d_b) / sqrtf(((mb_r + mb_g) + mb_b) + 1e-4f); selected iff
+ *      e > threshold.  A NaN e (non-finite sums) is never selected.
+ * The estimate compares the mean of the samples before the mark with the mean of those since
+ * (normalised like the half-buffer criterion of Dammertz et al.); it is a first estimator: the
+ * 1e-4 floor and the per-pixel form without a spatial filter are choices, not measurements. */
+typedef struct {
+    int32_t target;           /* absolute sample count the selected pixels are raised to */
+    int32_t x0, y0, x1, y1;   /* frame window [x0, x1) x [y0, y1), all 0 = whole frame */
+    const uint8_t *mask;      /* host, n_pixels bytes in the shard's layout, NULL = all */
+    float threshold;          /* <= 0: no error test */
+} rt_select;
+/* Copies the sums and counts as they stand into the accumulator's mark buffers (3 floats and one
+ * int per pixel, made on first use); asynchronous on `stream`.  Marks are not part of a
+ * checkpoint: a loaded accumulator has no mark. */
+int rt_accum_mark(rt_accum *accum, void *stream);
+/* Applies the rule and keeps the selected pixels as the pending list, in ascending shard-pixel
+ * order (deterministic: no atomics order it); waits, and returns the list's length in
+ * *n_selected (may be NULL).  Checked before any launch: target < 1 RT_ERR_ARG; target >= 2^20
+ * RT_ERR_LIMIT; a window with x1 < x0, y1 < y0 or outside the frame RT_ERR_ARG. */
+int rt_accum_select(rt_accum *accum, const rt_select *select, void *stream, int64_t *n_selected);
+/* Test / inspection entry: the pending list (n_selected shard pixels). */
+int rt_accum_selection(rt_accum *accum, int32_t *out_pixels);
+/* Renders every listed pixel from its own next sample up to the selection's target, on the
+ * schedule rt_accum_add's rule gives for that many items (a small list runs on the runahead
+ * kernel throughout, a large one on the plain kernel with the hand-off); the list is the pixel
+ * order, so no order pre-pass runs and RT_FLAG_HEAVY_ORDER is ignored.  Asynchronous unless
+ * stats != NULL (stats->pixels = the list's length, samples = the sum of target - next over it,
+ * order_ms = 0).  Without a pending selection RT_ERR_ARG; an empty selection launches nothing
+ * (RT_OK, stats zero).  Pixels not listed keep their sums and records. */
+int rt_accum_add_selected(rt_accum *accum, void *stream, rt_stats *stats);
+/* The sample-count map: every owned pixel's count, to host memory (waits) or to device memory
+ * on `stream` (asynchronous). */
+int rt_accum_counts(rt_accum *accum, int32_t *out);
+int rt_accum_counts_device(rt_accum *accum, int32_t *d_out, void *stream);
+/* The smallest and the largest count (either pointer may be NULL). */
+int rt_accum_sample_range(rt_accum *accum, int32_t *min_out, int32_t *max_out);
+/* While the counts differ: rt_accum_samples returns the largest; rt_accum_add fails with
+ * RT_ERR_ARG (level first: select with target = the largest count and no threshold, then
+ * rt_accum_add_selected); rt_accum_frame_u8 divides every pixel by its own count
+ * (rt_tonemap_u8_counts_device); rt_accum_save writes header word `i32 0` as 1 and `samples done`
+ * as the largest count, and rt_accum_load then accepts any record whose next sample is at most
+ * that (with 0 there, every record must equal it, as before).  The rule "one render per (scene,
+ * device) in flight" covers rt_accum_mark, rt_accum_select and rt_accum_add_selected. */
+
 /* Closest hit + light pdf for n explicit rays (BVH::intersect bvh.cpp:239-243 and
  * ManyLightsDistribution::pdf random.cpp:179-188; origin/dir as given to Ray::Ray, which
  * normalises dir).  Host arrays: org/dir n x 3; out_f n x 4 (t, u, v, light_pdf);
@@ -273,6 +341,14 @@ int rt_tonemap_u8(const float *sum, int32_t width, int32_t height, int32_t spp, 
  * d_rgb are device pointers; bit-identical to rt_tonemap_u8 (the gamma quantizer is glibc
  * powf's, as exact thresholds). */
 int rt_tonemap_u8_device(const float *d_sum, int32_t width, int32_t height, int32_t spp, uint8_t *d_rgb, void *stream);
+/* The finish of a frame whose pixels hold different sample counts (subset passes): pixel p's sum
+ * is multiplied by 1.f / (float)counts[p] where rt_tonemap_u8 multiplies by 1.f / (float)spp,
+ * then the same ACES, gamma and quantizer (same NaN / inf behaviour); a pixel with 0 samples
+ * gives 0, 0, 0.  With every count equal to spp the bytes are rt_tonemap_u8's.  The device
+ * twin runs on the current HIP device, asynchronous on `stream`, bit-identical to the host's. */
+int rt_tonemap_u8_counts(const float *sum, const int32_t *counts, int32_t width, int32_t height, uint8_t *rgb_out);
+int rt_tonemap_u8_counts_device(const float *d_sum, const int32_t *d_counts, int32_t width, int32_t height, uint8_t *d_rgb,
+                                void *stream);
 /* "P6\n{W} {H}\n255\n" + raw RGB (canvas.h:76-89) */
 int rt_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t height);
 

@@ -63,6 +63,12 @@ class RtParams(ctypes.Structure):
                 ("flags", ctypes.c_int32), ("fast_chunk", ctypes.c_int32), ("device", ctypes.c_int32)]
 
 
+class RtSelect(ctypes.Structure):
+    """include/rt_hw.h rt_select: what rt_accum_select raises to `target`."""
+    _fields_ = [("target", ctypes.c_int32), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("x1", ctypes.c_int32),
+                ("y1", ctypes.c_int32), ("mask", _c_b), ("threshold", ctypes.c_float)]
+
+
 class RtStats(ctypes.Structure):
     _fields_ = [("pixels", ctypes.c_uint64), ("samples", ctypes.c_uint64), ("rays", ctypes.c_uint64),
                 ("aabb_tests", ctypes.c_uint64), ("tri_tests", ctypes.c_uint64), ("light_queries", ctypes.c_uint64),
@@ -114,6 +120,18 @@ ABI = {
     "rt_accum_save": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "rt_accum_load": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]),
     "rt_accum_free": (None, [ctypes.c_void_p]),
+    # per-pixel sample counts: subset passes and adaptive refinement
+    "rt_accum_mark": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "rt_accum_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtSelect), ctypes.c_void_p,
+                                       ctypes.POINTER(ctypes.c_int64)]),
+    "rt_accum_selection": (ctypes.c_int, [ctypes.c_void_p, _c_i]),
+    "rt_accum_add_selected": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(RtStats)]),
+    "rt_accum_counts": (ctypes.c_int, [ctypes.c_void_p, _c_i]),
+    "rt_accum_counts_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rt_accum_sample_range": (ctypes.c_int, [ctypes.c_void_p, _c_i, _c_i]),
+    "rt_tonemap_u8_counts": (ctypes.c_int, [_c_f, _c_i, ctypes.c_int32, ctypes.c_int32, _c_b]),
+    "rt_tonemap_u8_counts_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                                   ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 _lib_handle = None
@@ -350,6 +368,29 @@ class Scene:
         _check(lib().rt_accum_create(self._h, ctypes.byref(p), ctypes.byref(h)))
         return Accumulator(self, h.value, rank, world, row_block)
 
+    def render_adaptive(self, min_spp, max_spp, step, threshold, device=0):
+        """Adaptive sampling of the whole frame on one shard (the loop of the CLI's RT_ADAPT):
+        min_spp samples everywhere in two halves with a mark between them, then rounds of
+        select(target = min(max_spp, largest count + step), threshold), mark, add_selected until
+        nothing is selected or max_spp is reached.  Returns (sums (H, W, 3), counts (H, W),
+        frame (H, W, 3) uint8 finished per pixel by its own count)."""
+        if min_spp < 2 or max_spp < min_spp or step < 1:
+            raise ValueError("render_adaptive: need 2 <= min_spp <= max_spp and step >= 1")
+        acc = self.accumulator(device=device)
+        try:
+            acc.add(min_spp // 2)
+            acc.mark()
+            acc.add(min_spp - min_spp // 2)
+            while acc.samples < max_spp:
+                target = min(max_spp, acc.samples + step)
+                if acc.select(target, threshold=threshold) == 0:
+                    break
+                acc.mark()
+                acc.add_selected()
+            return acc.sums(), acc.counts(), acc.frame()
+        finally:
+            acc.free()
+
     def render(self):
         """Scene::render (scene.cpp:17-65): sample loop on the GPU, then the 8-bit frame finish."""
         sums, _ = self.render_sums(self.samples)
@@ -418,6 +459,58 @@ class Accumulator:
     def save(self, path):
         _check(lib().rt_accum_save(self._h, os.fsencode(path)))
 
+    # --- per-pixel sample counts (include/rt_hw.h rt_accum_select and friends)
+    def mark(self, stream_ptr=None):
+        """rt_accum_mark: remember the sums and counts as they stand (the selection rule's
+        "before" half).  A pending selection stays."""
+        _check(lib().rt_accum_mark(self._h, ctypes.c_void_p(stream_ptr or 0)))
+
+    def select(self, target, window=None, mask=None, threshold=0.0, stream_ptr=None):
+        """rt_accum_select: choose the pixels the next add_selected() raises to `target` samples:
+        those below it, inside window = (x0, y0, x1, y1) (frame coordinates, half-open), with a
+        non-zero byte in mask ((rows, W), the shard's layout) and, with threshold > 0, whose
+        error estimate since the last mark exceeds it.  Returns how many were selected."""
+        x0, y0, x1, y1 = window if window is not None else (0, 0, 0, 0)
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+            if m.size != len(self.rows) * self._scene.width:
+                raise ValueError("mask must have one byte per owned pixel")
+        sel = RtSelect(int(target), int(x0), int(y0), int(x1), int(y1), m.ctypes.data_as(_c_b) if m is not None else None,
+                       float(threshold))
+        n = ctypes.c_int64(0)
+        _check(lib().rt_accum_select(self._h, ctypes.byref(sel), ctypes.c_void_p(stream_ptr or 0), ctypes.byref(n)))
+        self._n_selected = int(n.value)
+        return self._n_selected
+
+    def selection(self):
+        """The pending list: shard pixels, ascending (test / inspection)."""
+        out = np.zeros(max(getattr(self, "_n_selected", 0), 1), np.int32)
+        _check(lib().rt_accum_selection(self._h, out.ctypes.data_as(_c_i)))
+        return out[:self._n_selected]
+
+    def add_selected(self, stats=True, stream_ptr=None):
+        """rt_accum_add_selected: render the pending list's pixels up to its target; returns the
+        pass's stats (waits), or None with stats=False."""
+        st = RtStats() if stats else None
+        _check(lib().rt_accum_add_selected(self._h, ctypes.c_void_p(stream_ptr or 0), ctypes.byref(st) if st else None))
+        self._n_selected = 0
+        _after_render()
+        return st.as_dict() if st else None
+
+    def counts(self):
+        """(rows, W) int32: every owned pixel's sample count."""
+        out = np.zeros((len(self.rows), self._scene.width), np.int32)
+        _check(lib().rt_accum_counts(self._h, out.ctypes.data_as(_c_i)))
+        return out
+
+    @property
+    def sample_range(self):
+        """(smallest, largest) sample count."""
+        lo, hi = ctypes.c_int32(0), ctypes.c_int32(0)
+        _check(lib().rt_accum_sample_range(self._h, ctypes.byref(lo), ctypes.byref(hi)))
+        return int(lo.value), int(hi.value)
+
     def free(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value and _lib_handle is not None:
@@ -470,6 +563,18 @@ def tonemap(sums, spp):
     h, w = sums.shape[0], sums.shape[1]
     rgb = np.zeros((h, w, 3), np.uint8)
     _check(lib().rt_tonemap_u8(sums.ctypes.data_as(_c_f), w, h, spp, rgb.ctypes.data_as(_c_b)))
+    return rgb
+
+
+def tonemap_counts(sums, counts):
+    """rt_tonemap_u8_counts: the frame finish with a per-pixel sample count (0 samples: black)."""
+    sums = np.ascontiguousarray(sums, np.float32)
+    h, w = sums.shape[0], sums.shape[1]
+    counts = np.ascontiguousarray(counts, np.int32)
+    if counts.size != h * w:
+        raise ValueError("counts must have one entry per pixel")
+    rgb = np.zeros((h, w, 3), np.uint8)
+    _check(lib().rt_tonemap_u8_counts(sums.ctypes.data_as(_c_f), counts.ctypes.data_as(_c_i), w, h, rgb.ctypes.data_as(_c_b)))
     return rgb
 
 

@@ -7,6 +7,10 @@
 //                           counting pre-pass that orders pixels heaviest-first
 //   wf_{init,extend,shade}  wavefront schedule of the same arithmetic (kernel 4, rt_wavefront.h)
 //   rt_finish_kernel        mean -> ACES -> gamma -> 8-bit (scene.cpp:54-64)
+//   rt_finish_counts_kernel the same finish with a per-pixel sample count
+//   rt_select_kernel        an accumulator's subset pass: the pixels the rule of rt_select.h
+//                           chooses, as a compacted ascending list (with rt_select_scan_kernel),
+//                           and rt_mark_kernel / rt_counts_kernel beside it
 //   rt_rays_kernel          BVH::intersect + light pdf for explicit rays (test entry)
 // Every schedule writes the per-pixel float RGB sum (sample_canvas, scene.cpp:20,42) of the
 // owned rows; the bits do not depend on the kernel, the launch shape, the pixel order or the
@@ -43,6 +47,7 @@
 #include "rt_scene.h"
 #include "rt_bvh_layout.h"
 #include "rt_launch_plan.h"
+#include "rt_select.h"
 #include "rt_frame_plan.h"
 
 using rtd::Counters;
@@ -268,6 +273,33 @@ __global__ void __launch_bounds__(256) rt_finish_kernel(const float *sum, long l
     }
 }
 
+// The same finish with a per-pixel sample count (rt_tonemap_u8_counts_device): value i belongs to
+// pixel i / 3, whose sum is multiplied by 1.f / (float)count as above by 1.f / (float)spp; a pixel
+// without samples gives 0, 0, 0.  Same thresholds, same NaN / inf behaviour.
+__global__ void __launch_bounds__(256) rt_finish_counts_kernel(const float *sum, const int32_t *counts, long long n,
+                                                                uint8_t *rgb) {
+    __shared__ float thr[256];
+    thr[threadIdx.x] = __uint_as_float(k_quant_thr[threadIdx.x]);
+    __syncthreads();
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int32_t c = counts[i / 3];
+        float x = sum[i];
+        x *= rtsel::count_normalizer(c);
+        const float num = x * (x * 2.51f + 0.03f);
+        const float den = x * (x * 2.43f + 0.59f) + 0.14f;
+        const float v = rtv::smax(rtv::smin(num / den, 1.f), 0.f);
+        int q = 0;
+        if (c > 0 && !isnan(v)) {
+            int lo = 0;
+#pragma unroll
+            for (int step = 128; step > 0; step >>= 1)
+                if (lo + step <= 255 && thr[lo + step] <= v) lo += step;
+            q = lo;
+        }
+        rgb[i] = (uint8_t)q;
+    }
+}
+
 // ------------------------------------------------------------------------ lane-resident (kernel 0)
 // rt_mega.h: every lane runs whole pixels; traversal one unit per iteration, shading batched
 // per wave (READY lanes wait for kShadeMin of them or for no lane left traversing).
@@ -301,7 +333,11 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
     constexpr bool kChain = CHAIN && !COUNT && !FAST && !LSPLIT;
     const int park_below = rtp::mode_park_below(mode), resume_pct = rtp::mode_resume_pct(mode);
     const uint4 *resume = kSpec && resume_pct > 0 ? (const uint4 *)queue[rtd::kQueueParkList] : nullptr;
-    const long long n_items = FAST ? g.n_pixels * (long long)((spp + cs - 1) / cs) : (kSpec && resume) ? st.n : g.n_pixels;
+    // (CHAIN: the pass's item count, the shard's pixels for a full pass or a selection's length
+    // for a subset pass, whose pixels `order` lists; a constant of the instantiation chooses, so
+    // the one-shot kernels read what they read before)
+    const long long n_items = FAST ? g.n_pixels * (long long)((spp + cs - 1) / cs)
+                                   : (kChain || (kSpec && resume)) ? st.n : g.n_pixels;
     const int lane = threadIdx.x & 63;
     // sRGB texel-decode table in LDS: the shading's lane-dependent lookups become ds_reads (the
     // linear decode is computed: rt_path.h texel_decode)
@@ -431,7 +467,7 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
                     if (p < n_items) {
                         if (FAST) rtd::mega_assign_fast<COUNT>(L, sc, g, p, cs, spp, root, cnt);
                         else if constexpr (kChain)
-                            rtd::mega_assign_chain<COUNT>(L, sc, g, order ? order[p] : (int)p, root, cnt, rtd::chain_of(queue));
+                            rtd::mega_assign_chain<COUNT>(L, sc, g, order ? order[p] : (int)p, root, cnt, rtd::chain_of(queue), spp);
                         else rtd::mega_assign<COUNT>(L, sc, g, order ? order[p] : (int)p, root, cnt);
                     }
                 }
@@ -1251,9 +1287,15 @@ int shard_of(const rt_scene *s, const rt_params *p, const char *who, Shard &sh) 
 // An accumulator's pass (rt_accum_add): the chain buffer and the samples the pass adds.  The
 // render's spp is then the absolute sample the pass ends at; the pixel order and the stats go
 // by the pass's own sample count (rt_launch_plan.h PlanIn.pass_spp).
+// A subset pass (rt_accum_add_selected) also names its item list: `n_items` shard pixels in
+// `items` (device memory, made by rt_select_kernel), each raised to the render's spp from its
+// own record; `n` is then only the plan's pass marker and `samples` the pass's sample total.
 struct ChainPass {
     uint4 *chain;
     int n;
+    const int *items = nullptr;
+    long long n_items = 0;
+    unsigned long long samples = 0;
 };
 
 // One word of the queue block, written in stream order.
@@ -1306,7 +1348,7 @@ struct RenderEvents {
 
 // rt_stats of one shard, once its last launch is queued (waits for it).
 int read_stats(rt_device_scene *d, const rtp::Schedule &plan, bool count, RenderEvents &ev, LaunchTimer &timer,
-               hipStream_t stream, rt_stats *st) {
+               hipStream_t stream, rt_stats *st, const ChainPass *cp = nullptr) {
     HIP_TRY(hipEventRecord(ev.end, stream));
     HIP_TRY(hipEventSynchronize(ev.end));
     float ms = 0.f, ms_order = 0.f;
@@ -1315,6 +1357,10 @@ int read_stats(rt_device_scene *d, const rtp::Schedule &plan, bool count, Render
     std::memset(st, 0, sizeof *st);
     st->pixels = (uint64_t)plan.n_pixels;
     st->samples = (uint64_t)plan.n_pixels * (uint64_t)plan.stats_spp;
+    if (cp && cp->items) {   // a subset pass: the list's pixels and what they were raised by
+        st->pixels = (uint64_t)cp->n_items;
+        st->samples = cp->samples;
+    }
     st->render_ms = ms;
     st->order_ms = ms_order;
     st->devices = 1;
@@ -1354,6 +1400,7 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
     in.fast_chunk = p->fast_chunk;
     in.spp = p->spp > 0 ? p->spp : s->samples;
     in.pass_spp = cp ? cp->n : 0;
+    in.subset_items = cp && cp->items ? cp->n_items : 0;
     in.ray_depth = s->ray_depth;
     if (const rtp::Refusal r = rtp::plan_check(in)) return rt_fail(r.code, r.msg);
     Shard sh;
@@ -1395,14 +1442,14 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
     } else if (plan.lane) {   // lane-resident (rt_mega.h), the default
         if (int rc = ensure_wf(d, std::max<long long>(g.n_pixels, grid.slots), s->ray_depth)) return rc;   // vertex records
         rtd::WfState w = d->wf;
-        w.n = g.n_pixels;
+        w.n = cp && cp->items ? cp->n_items : g.n_pixels;   // (the CHAIN kernels' item count)
         w.lanes = grid.slots;   // LaneRec slots (<= the workspace capacity)
         w.round_min = plan.round_min;
         if (plan.handoff) {   // the park list: every slot "nothing parked"; the runahead launch's claim counter
             HIP_TRY(hipMemsetAsync(d->wf_queue[0], 0xff, (size_t)grid.slots * 32, stream));
             HIP_TRY(hipMemsetAsync(d->queue + rtd::kQueueResume, 0, sizeof(unsigned long long), stream));
         }
-        const int *order = nullptr;
+        const int *order = cp ? cp->items : nullptr;   // (a subset pass: the list is the order)
         if (plan.ordered)
             if (int rc = launch_order(d, g, stream, grid.groups, grid.per, &order)) return rc;
         if (st) HIP_TRY(hipEventRecord(ev.ordered, stream));
@@ -1433,7 +1480,7 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
 #endif
     }
     HIP_TRY(hipGetLastError());
-    if (st) return read_stats(d, plan, count, ev, timer, stream, st);
+    if (st) return read_stats(d, plan, count, ev, timer, stream, st, cp);
     return RT_OK;
 }
 
@@ -1500,23 +1547,38 @@ int rt_render_device(rt_scene *s, const rt_params *p, float *d_out, void *stream
     return launch(s, p, d_out, (hipStream_t)stream, st);
 }
 
-int rt_tonemap_u8_device(const float *d_sum, int32_t width, int32_t height, int32_t spp, uint8_t *d_rgb, void *stream) {
-    if (!d_sum || !d_rgb || width <= 0 || height <= 0 || spp <= 0)
-        return rt_fail(RT_ERR_ARG, "rt_tonemap_u8_device: bad argument");
-    // the quantizer thresholds go to each device's constant memory once; threads finishing
-    // on the same device at first use serialise on the mutex
+// The quantizer thresholds go to each device's constant memory once; threads finishing on the
+// same device at first use serialise on the mutex.
+static int quant_thresholds_upload() {
     static std::mutex upload_mu;
     static bool uploaded[kRtMaxDevices] = {false};
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= kRtMaxDevices) return rt_fail(RT_ERR_DEVICE, "rt_tonemap_u8_device: device id");
-    {
-        std::lock_guard<std::mutex> lock(upload_mu);
-        if (!uploaded[dev]) {
-            HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(k_quant_thr), rtm::kQuantThr, sizeof rtm::kQuantThr));
-            uploaded[dev] = true;
-        }
+    std::lock_guard<std::mutex> lock(upload_mu);
+    if (!uploaded[dev]) {
+        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(k_quant_thr), rtm::kQuantThr, sizeof rtm::kQuantThr));
+        uploaded[dev] = true;
     }
+    return RT_OK;
+}
+
+int rt_tonemap_u8_counts_device(const float *d_sum, const int32_t *d_counts, int32_t width, int32_t height, uint8_t *d_rgb,
+                                void *stream) {
+    if (!d_sum || !d_counts || !d_rgb || width <= 0 || height <= 0)
+        return rt_fail(RT_ERR_ARG, "rt_tonemap_u8_counts_device: bad argument");
+    if (int rc = quant_thresholds_upload()) return rc;
+    const long long n = (long long)width * height * 3;
+    const unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(rt_finish_counts_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_sum, d_counts, n, d_rgb);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+int rt_tonemap_u8_device(const float *d_sum, int32_t width, int32_t height, int32_t spp, uint8_t *d_rgb, void *stream) {
+    if (!d_sum || !d_rgb || width <= 0 || height <= 0 || spp <= 0)
+        return rt_fail(RT_ERR_ARG, "rt_tonemap_u8_device: bad argument");
+    if (int rc = quant_thresholds_upload()) return rc;
     const long long n = (long long)width * height * 3;
     const unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 4096);
     hipLaunchKernelGGL(rt_finish_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_sum, n,
@@ -1548,7 +1610,139 @@ struct rt_accum {
     float *sums = nullptr;    // n_pixels x 3
     uint8_t *rgb = nullptr;   // n_pixels x 3, made by the first rt_accum_frame_u8
     hipStream_t stream = nullptr;   // the last pass's stream (host reads wait for it)
+    // Per-pixel sample counts (subset passes): `samples` is the largest count, `min_samples` the
+    // smallest; they are equal until a subset pass leaves some pixels behind.
+    int min_samples = 0;
+    // rt_accum_mark's copy of the sums and counts (made on first use); none after create / load
+    float *mark_sums = nullptr;
+    int32_t *mark_counts = nullptr;
+    bool has_mark = false;
+    // rt_accum_select's pending list (shard pixels, ascending; made on first use) and what the
+    // selection kernel reduced with it; dropped by every pass
+    int *sel_list = nullptr;
+    unsigned *sel_blocks = nullptr;        // per block of rt_select_kernel: selected count, then list offset
+    unsigned long long *sel_out = nullptr; // SelectOut
+    uint8_t *sel_mask = nullptr;           // device copy of rt_select.mask
+    int32_t *counts = nullptr;             // n_pixels, for the count-aware finish
+    bool sel_pending = false;
+    long long sel_n = 0;
+    unsigned long long sel_samples = 0;
+    int sel_target = 0, sel_min = 0, sel_max = 0;
 };
+
+// What rt_select_kernel reduces besides the list (device words, zeroed / set before the launch).
+struct SelectOut {
+    unsigned long long n_selected, samples;   // samples: sum of (target - next) over the selected
+    int next_min, next_max;                   // of `next` as it will be after the pass
+};
+
+// The selection (rt_accum_select, rt_select.h): one thread per shard pixel applies the rule.
+// WRITE = false counts: per wave a ballot, per block the four wave counts, block b's count to
+// blocks[b], and the reductions of SelectOut per wave (shuffles), per block (LDS), one atomic
+// per block and value.  rt_select_scan_kernel then turns the block counts into list offsets,
+// and WRITE = true evaluates the same rule again and writes pixel p to
+// list[blocks[b] + selected in the block's earlier waves + selected lanes below (mbcnt)]: the
+// list is in ascending shard-pixel order, holds each pixel at most once, and no atomic orders it.
+template <bool WRITE>
+__global__ void __launch_bounds__(256) rt_select_kernel(ShardGeom g, rtsel::Rule rule, const uint4 *chain, const float *sums,
+                                                         const float *mark_sums, const int32_t *mark_counts,
+                                                         const uint8_t *mask, unsigned *blocks, int *list, SelectOut *out) {
+    __shared__ unsigned wave_n[4];
+    __shared__ unsigned long long wave_s[4];
+    __shared__ int wave_lo[4], wave_hi[4];
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    bool sel = false;
+    int n_b = 0;
+    if (p < g.n_pixels) {
+        n_b = (int)chain[2 * p].y;   // the record's next sample (rt_mega.h park_pixel)
+        int x, y;
+        rtd::shard_xy(g, p, x, y);
+        const float S_b[3] = {sums[3 * p], sums[3 * p + 1], sums[3 * p + 2]};
+        const int n_a = mark_counts ? mark_counts[p] : 0;
+        float S_a[3] = {0.f, 0.f, 0.f};
+        if (mark_sums) {
+            S_a[0] = mark_sums[3 * p];
+            S_a[1] = mark_sums[3 * p + 1];
+            S_a[2] = mark_sums[3 * p + 2];
+        }
+        sel = rtsel::selected(rule, x, y, mask ? mask[p] : 1u, n_b, S_b, n_a, S_a);
+    }
+    const unsigned long long m = __ballot(sel);
+    if (lane == 0) wave_n[wave] = (unsigned)__popcll(m);
+    if constexpr (!WRITE) {
+        unsigned long long s = sel ? (unsigned long long)(rule.target - n_b) : 0ull;
+        const int after = sel ? rule.target : n_b;
+        int lo = p < g.n_pixels ? after : 0x7fffffff, hi = p < g.n_pixels ? after : 0;
+        for (int k = 32; k > 0; k >>= 1) {
+            s += __shfl_xor(s, k, 64);
+            lo = min(lo, __shfl_xor(lo, k, 64));
+            hi = max(hi, __shfl_xor(hi, k, 64));
+        }
+        if (lane == 0) {
+            wave_s[wave] = s;
+            wave_lo[wave] = lo;
+            wave_hi[wave] = hi;
+        }
+    }
+    __syncthreads();
+    if constexpr (WRITE) {
+        unsigned base = blocks[blockIdx.x];
+        for (int w = 0; w < wave; ++w) base += wave_n[w];
+        const unsigned below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (sel) list[base + below] = (int)p;
+    } else if (threadIdx.x == 0) {
+        const unsigned n = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+        blocks[blockIdx.x] = n;
+        atomicAdd(&out->n_selected, (unsigned long long)n);
+        atomicAdd(&out->samples, wave_s[0] + wave_s[1] + wave_s[2] + wave_s[3]);
+        atomicMin(&out->next_min, min(min(wave_lo[0], wave_lo[1]), min(wave_lo[2], wave_lo[3])));
+        atomicMax(&out->next_max, max(max(wave_hi[0], wave_hi[1]), max(wave_hi[2], wave_hi[3])));
+    }
+}
+
+// Exclusive prefix sum of the selection's block counts, in place, by one block: thread t sums
+// its run of ceil(n / 256) counts, thread 0 scans the 256 run sums, thread t writes its run.
+__global__ void __launch_bounds__(256) rt_select_scan_kernel(unsigned *blocks, long long n) {
+    __shared__ unsigned run[256];
+    const long long per = (n + 255) / 256, b0 = (long long)threadIdx.x * per, b1 = b0 + per < n ? b0 + per : n;
+    unsigned s = 0;
+    for (long long b = b0; b < b1; ++b) s += blocks[b];
+    run[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned acc = 0;
+        for (int t = 0; t < 256; ++t) {
+            const unsigned v = run[t];
+            run[t] = acc;
+            acc += v;
+        }
+    }
+    __syncthreads();
+    unsigned acc = run[threadIdx.x];
+    for (long long b = b0; b < b1; ++b) {
+        const unsigned v = blocks[b];
+        blocks[b] = acc;
+        acc += v;
+    }
+}
+
+// rt_accum_mark: the sums and counts as they stand, for the selection rule's "before" half.
+__global__ void __launch_bounds__(256) rt_mark_kernel(const uint4 *chain, const float *sums, long long n, float *mark_sums,
+                                                       int32_t *mark_counts) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    mark_sums[3 * p + 0] = sums[3 * p + 0];
+    mark_sums[3 * p + 1] = sums[3 * p + 1];
+    mark_sums[3 * p + 2] = sums[3 * p + 2];
+    mark_counts[p] = (int32_t)chain[2 * p].y;
+}
+
+// The sample-count map: every record's next sample.
+__global__ void __launch_bounds__(256) rt_counts_kernel(const uint4 *chain, long long n, int32_t *counts) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) counts[p] = (int32_t)chain[2 * p].y;
+}
 
 __global__ void __launch_bounds__(256) rt_chain_init_kernel(DevScene sc, ShardGeom g, uint4 *chain, float *sums) {
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1612,9 +1806,9 @@ void accum_release(rt_accum *a) {
     if (!a) return;
     if (a->chain || a->sums || a->rgb) {
         DeviceGuard guard(a->p.device);
-        if (a->chain) (void)hipFree(a->chain);
-        if (a->sums) (void)hipFree(a->sums);
-        if (a->rgb) (void)hipFree(a->rgb);
+        for (void *b : {(void *)a->chain, (void *)a->sums, (void *)a->rgb, (void *)a->mark_sums, (void *)a->mark_counts,
+                        (void *)a->sel_list, (void *)a->sel_blocks, (void *)a->sel_out, (void *)a->sel_mask, (void *)a->counts})
+            if (b) (void)hipFree(b);
     }
     delete a;
 }
@@ -1653,6 +1847,24 @@ int accum_wait(rt_accum *a) {
     return RT_OK;
 }
 
+// A device buffer of an accumulator made on first use (the current device is the accumulator's).
+template <class T>
+int accum_buffer(T *&p, size_t count) {
+    if (!p) HIP_TRY(hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T)));
+    return RT_OK;
+}
+
+bool accum_uniform(const rt_accum *a) { return a->min_samples == a->samples; }
+
+// The sample-count map into a->counts, on the accumulator's stream.
+int accum_counts_launch(rt_accum *a, int32_t *d_counts, hipStream_t stream) {
+    if (a->n_pixels == 0) return RT_OK;
+    hipLaunchKernelGGL(rt_counts_kernel, dim3((unsigned)((a->n_pixels + 255) / 256)), dim3(256), 0, stream,
+                       (const uint4 *)a->chain, a->n_pixels, d_counts);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1688,6 +1900,11 @@ int rt_accum_add(rt_accum *a, int32_t n_samples, void *stream, rt_stats *st) {
     if (n_samples < 1) return rt_fail(RT_ERR_ARG, "rt_accum_add: n_samples must be >= 1");
     if ((long long)a->samples + n_samples >= (1 << 20))
         return rt_fail(RT_ERR_LIMIT, "rt_accum_add: total samples per pixel must be < 2^20");
+    if (!accum_uniform(a))
+        return rt_fail(RT_ERR_ARG, "rt_accum_add: the pixels hold between " + std::to_string(a->min_samples) + " and " +
+                                       std::to_string(a->samples) + " samples; level them first: rt_accum_select with target = " +
+                                       std::to_string(a->samples) + " and no threshold, then rt_accum_add_selected");
+    a->sel_pending = false;   // (the pass changes the records the list was made from)
     rt_params p = a->p;
     p.spp = a->samples + n_samples;   // the absolute sample this pass ends at
     const ChainPass cp{a->chain, n_samples};
@@ -1695,6 +1912,140 @@ int rt_accum_add(rt_accum *a, int32_t n_samples, void *stream, rt_stats *st) {
     int rc = launch(a->scene, &p, a->sums, (hipStream_t)stream, st, &cp);
     if (rc) return rc;
     a->samples += n_samples;
+    a->min_samples = a->samples;
+    return RT_OK;
+}
+
+int rt_accum_mark(rt_accum *a, void *stream) {
+    if (!a) return rt_fail(RT_ERR_ARG, "rt_accum_mark: NULL accumulator");
+    DeviceGuard guard(a->p.device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    // (a pending selection stays: the mark changes no record, so the list is as safe as it was)
+    if (int rc = accum_buffer(a->mark_sums, (size_t)a->n_pixels * 3)) return rc;
+    if (int rc = accum_buffer(a->mark_counts, (size_t)a->n_pixels)) return rc;
+    a->stream = (hipStream_t)stream;
+    if (a->n_pixels > 0) {
+        hipLaunchKernelGGL(rt_mark_kernel, dim3((unsigned)((a->n_pixels + 255) / 256)), dim3(256), 0, a->stream,
+                           (const uint4 *)a->chain, (const float *)a->sums, a->n_pixels, a->mark_sums, a->mark_counts);
+        HIP_TRY(hipGetLastError());
+    }
+    a->has_mark = true;
+    return RT_OK;
+}
+
+int rt_accum_select(rt_accum *a, const rt_select *sel, void *stream, int64_t *n_selected) {
+    // every argument check comes before any device call
+    if (!sel) return rt_fail(RT_ERR_ARG, "rt_accum_select: NULL selection");
+    const rtsel::Rule rule{sel->target, sel->x0, sel->y0, sel->x1, sel->y1, sel->threshold};
+    const int bad = rtsel::check_rule(rule, a ? a->scene->width : INT32_MAX, a ? a->scene->height : INT32_MAX);
+    if (bad == 2) return rt_fail(RT_ERR_LIMIT, "rt_accum_select: target must be < 2^20");
+    if (bad == 1)
+        return rt_fail(RT_ERR_ARG, rule.target < 1 ? std::string("rt_accum_select: target must be >= 1")
+                                                   : "rt_accum_select: bad window [" + std::to_string(rule.x0) + ", " +
+                                                         std::to_string(rule.x1) + ") x [" + std::to_string(rule.y0) + ", " +
+                                                         std::to_string(rule.y1) + ")");
+    if (!a) return rt_fail(RT_ERR_ARG, "rt_accum_select: NULL accumulator");
+    a->sel_pending = false;
+    DeviceGuard guard(a->p.device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    const long long n = a->n_pixels, nb = (n + 255) / 256;
+    if (int rc = accum_buffer(a->sel_list, (size_t)n)) return rc;
+    if (int rc = accum_buffer(a->sel_blocks, (size_t)nb)) return rc;
+    if (int rc = accum_buffer(a->sel_out, sizeof(SelectOut) / sizeof(unsigned long long))) return rc;
+    if (sel->mask) {   // (the last launch that read the mask buffer has been waited for: select waits)
+        if (int rc = accum_buffer(a->sel_mask, (size_t)n)) return rc;
+        if (int rc = accum_wait(a)) return rc;
+        if (n) HIP_TRY(hipMemcpy(a->sel_mask, sel->mask, (size_t)n, hipMemcpyHostToDevice));
+    }
+    a->stream = (hipStream_t)stream;
+    SelectOut so{0ull, 0ull, INT32_MAX, 0};
+    if (n > 0) {
+        HIP_TRY(hipMemcpyAsync(a->sel_out, &so, sizeof so, hipMemcpyHostToDevice, a->stream));
+        const uint8_t *mask = sel->mask ? a->sel_mask : nullptr;
+        const float *ms = a->has_mark ? a->mark_sums : nullptr;
+        const int32_t *mc = a->has_mark ? a->mark_counts : nullptr;
+        hipLaunchKernelGGL(rt_select_kernel<false>, dim3((unsigned)nb), dim3(256), 0, a->stream, a->geom, rule,
+                           (const uint4 *)a->chain, (const float *)a->sums, ms, mc, mask, a->sel_blocks, a->sel_list,
+                           (SelectOut *)a->sel_out);
+        hipLaunchKernelGGL(rt_select_scan_kernel, dim3(1), dim3(256), 0, a->stream, a->sel_blocks, nb);
+        hipLaunchKernelGGL(rt_select_kernel<true>, dim3((unsigned)nb), dim3(256), 0, a->stream, a->geom, rule,
+                           (const uint4 *)a->chain, (const float *)a->sums, ms, mc, mask, a->sel_blocks, a->sel_list,
+                           (SelectOut *)a->sel_out);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&so, a->sel_out, sizeof so, hipMemcpyDeviceToHost, a->stream));
+        if (int rc = accum_wait(a)) return rc;
+    } else {
+        so.next_min = so.next_max = a->samples;
+    }
+    a->sel_n = (long long)so.n_selected;
+    a->sel_samples = so.samples;
+    a->sel_target = rule.target;
+    a->sel_min = so.next_min;
+    a->sel_max = so.next_max;
+    a->sel_pending = true;
+    if (n_selected) *n_selected = a->sel_n;
+    return RT_OK;
+}
+
+int rt_accum_selection(rt_accum *a, int32_t *out_pixels) {
+    if (!a || !out_pixels) return rt_fail(RT_ERR_ARG, "rt_accum_selection: NULL argument");
+    if (!a->sel_pending) return rt_fail(RT_ERR_ARG, "rt_accum_selection: no pending selection (rt_accum_select first)");
+    DeviceGuard guard(a->p.device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = accum_wait(a)) return rc;
+    if (a->sel_n) HIP_TRY(hipMemcpy(out_pixels, a->sel_list, (size_t)a->sel_n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_accum_add_selected(rt_accum *a, void *stream, rt_stats *st) {
+    if (!a) return rt_fail(RT_ERR_ARG, "rt_accum_add_selected: NULL accumulator");
+    if (!a->sel_pending)
+        return rt_fail(RT_ERR_ARG, "rt_accum_add_selected: no pending selection (rt_accum_select first; every pass "
+                                   "drops it)");
+    a->sel_pending = false;
+    if (a->sel_n == 0) {   // nothing to raise: no launch
+        if (st) {
+            std::memset(st, 0, sizeof *st);
+            st->devices = 1;
+        }
+        return RT_OK;
+    }
+    rt_params p = a->p;
+    p.spp = a->sel_target;   // the absolute sample every listed pixel ends at
+    ChainPass cp{a->chain, 1};
+    cp.items = a->sel_list;
+    cp.n_items = a->sel_n;
+    cp.samples = a->sel_samples;
+    a->stream = (hipStream_t)stream;
+    int rc = launch(a->scene, &p, a->sums, (hipStream_t)stream, st, &cp);
+    if (rc) return rc;
+    a->samples = a->sel_max;
+    a->min_samples = a->sel_min;
+    return RT_OK;
+}
+
+int rt_accum_counts(rt_accum *a, int32_t *out) {
+    if (!a || !out) return rt_fail(RT_ERR_ARG, "rt_accum_counts: NULL argument");
+    DeviceGuard guard(a->p.device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = accum_buffer(a->counts, (size_t)a->n_pixels)) return rc;
+    if (int rc = accum_counts_launch(a, a->counts, a->stream)) return rc;
+    if (int rc = accum_wait(a)) return rc;
+    if (a->n_pixels) HIP_TRY(hipMemcpy(out, a->counts, (size_t)a->n_pixels * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_accum_counts_device(rt_accum *a, int32_t *d_out, void *stream) {
+    if (!a || !d_out) return rt_fail(RT_ERR_ARG, "rt_accum_counts_device: NULL argument");
+    DeviceGuard guard(a->p.device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    return accum_counts_launch(a, d_out, (hipStream_t)stream);
+}
+
+int rt_accum_sample_range(rt_accum *a, int32_t *min_out, int32_t *max_out) {
+    if (!a) return rt_fail(RT_ERR_ARG, "rt_accum_sample_range: NULL accumulator");
+    if (min_out) *min_out = a->min_samples;
+    if (max_out) *max_out = a->samples;
     return RT_OK;
 }
 
@@ -1718,7 +2069,13 @@ int rt_accum_frame_u8(rt_accum *a, uint8_t *out_rgb) {
     DeviceGuard guard(a->p.device);
     if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
     if (!a->rgb) HIP_TRY(hipMalloc((void **)&a->rgb, (size_t)a->n_pixels * 3));
-    if (int rc = rt_tonemap_u8_device(a->sums, a->scene->width, a->rows, a->samples, a->rgb, a->stream)) return rc;
+    if (accum_uniform(a)) {
+        if (int rc = rt_tonemap_u8_device(a->sums, a->scene->width, a->rows, a->samples, a->rgb, a->stream)) return rc;
+    } else {   // every pixel divided by its own count
+        if (int rc = accum_buffer(a->counts, (size_t)a->n_pixels)) return rc;
+        if (int rc = accum_counts_launch(a, a->counts, a->stream)) return rc;
+        if (int rc = rt_tonemap_u8_counts_device(a->sums, a->counts, a->scene->width, a->rows, a->rgb, a->stream)) return rc;
+    }
     if (int rc = accum_wait(a)) return rc;
     HIP_TRY(hipMemcpy(out_rgb, a->rgb, (size_t)a->n_pixels * 3, hipMemcpyDeviceToHost));
     return RT_OK;
@@ -1758,6 +2115,7 @@ int rt_accum_save(rt_accum *a, const char *path) {
     h.row_block = a->p.row_block;
     h.n_pixels = a->n_pixels;
     h.samples = a->samples;
+    h.reserved = accum_uniform(a) ? 0 : 1;   // 1: per-pixel counts, `samples` is the largest
     std::FILE *f = std::fopen(path, "wb");
     if (!f) return rt_fail(RT_ERR_IO, std::string("rt_accum_save: cannot write ") + path);
     bool ok = std::fwrite(&h, sizeof h, 1, f) == 1;
@@ -1783,6 +2141,8 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
         rc = rt_fail(RT_ERR_FORMAT, who + ": version " + std::to_string(h.version) + ", this library reads " + std::to_string(kAccumVersion));
     else if (h.n_pixels < 0 || h.n_pixels > INT32_MAX || h.samples < 0 || h.samples >= (1 << 20))
         rc = rt_fail(RT_ERR_FORMAT, who + ": bad pixel or sample count");
+    else if (h.reserved != 0 && h.reserved != 1)
+        rc = rt_fail(RT_ERR_FORMAT, who + ": bad count form " + std::to_string(h.reserved) + " (0 uniform, 1 per pixel)");
     else {
         std::fseek(f, 0, SEEK_END);
         const long long len = (long long)std::ftell(f);
@@ -1824,11 +2184,17 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
         return rt_fail(RT_ERR_ARG, who + ": " + std::to_string(h.n_pixels) + " pixels, the shard (rank " + std::to_string(h.rank) +
                                        ", world " + std::to_string(h.world) + ") of this scene has " + std::to_string(have));
     }
-    for (long long k = 0; k < h.n_pixels; ++k)
-        if (rec[8 * k] != (uint32_t)k || rec[8 * k + 1] != (uint32_t)h.samples) {
+    // (per-pixel counts, reserved = 1: any next sample up to the header's; else all equal to it)
+    uint32_t lo = (uint32_t)h.samples, hi = h.reserved && h.n_pixels ? 0u : (uint32_t)h.samples;
+    for (long long k = 0; k < h.n_pixels; ++k) {
+        const uint32_t nx = rec[8 * k + 1];
+        if (rec[8 * k] != (uint32_t)k || (h.reserved ? nx > (uint32_t)h.samples : nx != (uint32_t)h.samples)) {
             accum_release(a);
             return rt_fail(RT_ERR_FORMAT, who + ": record " + std::to_string(k) + " does not belong to this file");
         }
+        lo = std::min(lo, nx);
+        hi = std::max(hi, nx);
+    }
     rc = ensure_device_scene(s, device);   // (the file fits the scene: first device call)
     if (rc == RT_OK) rc = accum_alloc(a);
     if (rc == RT_OK && a->n_pixels > 0) {
@@ -1843,7 +2209,8 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
         accum_release(a);
         return rc;
     }
-    a->samples = h.samples;
+    a->samples = (int)hi;   // (no mark, no pending selection)
+    a->min_samples = (int)lo;
     *out = a;
     return RT_OK;
 }

@@ -19,6 +19,7 @@
 
 #include "rt_json.h"
 #include "rt_scene.h"
+#include "rt_select.h"
 #include "rt_vec.h"
 
 using rtv::V2;
@@ -828,23 +829,33 @@ int64_t rt_shard_rows(int32_t height, int32_t rank, int32_t world, int32_t row_b
 
 // Scene::render frame finish (scene.cpp:54-64): c * (1/spp) -> ACES (vector.h:400-407)
 // -> powf(c, 1/2.2f) -> (uint8_t)roundf(clamp(c * 255, 0, 255)) (vector.h:222-233).
+static uint8_t finish_channel(float x, float normalizer) {
+    const float gamma = 1.f / 2.2f;
+    const float a = 2.51f, b = 0.03f, c = 2.43f, d = 0.59f, e = 0.14f;
+    x *= normalizer;
+    float num = x * (x * a + b);
+    float den = x * (x * c + d) + e;
+    float v = rtv::smax(rtv::smin(num / den, 1.f), 0.f);
+    v = std::pow(v, gamma);
+    float s = rtv::smax(rtv::smin(v * 255, 255.f), 0.f);
+    float r = std::round(s);
+    return std::isnan(r) ? (uint8_t)0 : (uint8_t)(int)r;
+}
+
 int rt_tonemap_u8(const float *sum, int32_t width, int32_t height, int32_t spp, uint8_t *rgb) {
     if (!sum || !rgb || width <= 0 || height <= 0 || spp <= 0) return rt_fail(RT_ERR_ARG, "rt_tonemap_u8: bad argument");
     const float normalizer = 1.f / (float)spp;
-    const float gamma = 1.f / 2.2f;
-    const float a = 2.51f, b = 0.03f, c = 2.43f, d = 0.59f, e = 0.14f;
+    for (int64_t p = 0; p < (int64_t)width * height; ++p)
+        for (int k = 0; k < 3; ++k) rgb[3 * p + k] = finish_channel(sum[3 * p + k], normalizer);
+    return RT_OK;
+}
+
+// The same finish with a per-pixel sample count (rt_select.h count_normalizer); 0 samples: 0, 0, 0.
+int rt_tonemap_u8_counts(const float *sum, const int32_t *counts, int32_t width, int32_t height, uint8_t *rgb) {
+    if (!sum || !counts || !rgb || width <= 0 || height <= 0) return rt_fail(RT_ERR_ARG, "rt_tonemap_u8_counts: bad argument");
     for (int64_t p = 0; p < (int64_t)width * height; ++p) {
-        for (int k = 0; k < 3; ++k) {
-            float x = sum[3 * p + k];
-            x *= normalizer;
-            float num = x * (x * a + b);
-            float den = x * (x * c + d) + e;
-            float v = rtv::smax(rtv::smin(num / den, 1.f), 0.f);
-            v = std::pow(v, gamma);
-            float s = rtv::smax(rtv::smin(v * 255, 255.f), 0.f);
-            float r = std::round(s);
-            rgb[3 * p + k] = std::isnan(r) ? (uint8_t)0 : (uint8_t)(int)r;
-        }
+        const float normalizer = rtsel::count_normalizer(counts[p]);
+        for (int k = 0; k < 3; ++k) rgb[3 * p + k] = counts[p] > 0 ? finish_channel(sum[3 * p + k], normalizer) : (uint8_t)0;
     }
     return RT_OK;
 }

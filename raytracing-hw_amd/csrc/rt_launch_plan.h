@@ -131,6 +131,10 @@ struct PlanIn {
     long long n_pixels = 0;   // the shard's
     int ray_depth = 0, n_nodes = 0;   // the scene's
     long long spec_blocks = 0;        // resident blocks of the runahead kernel (the pass's CHAIN form for a pass)
+    // A subset pass (rt_accum_add_selected): the items of its list, each one pixel raised to
+    // `spp` from wherever its record stands; 0 = a full pass.  The list is the order: no
+    // pre-pass runs and RT_FLAG_HEAVY_ORDER is ignored.
+    long long subset_items = 0;
 };
 
 // The two order flags exclude each other (shared with the accumulator's parameter check).
@@ -197,18 +201,20 @@ inline Schedule plan_schedule(const PlanIn &in) {
         s.cs = std::min(in.spp, std::max(in.fast_chunk > 0 ? in.fast_chunk : 2, (in.spp + kFastMaxChunks - 1) / kFastMaxChunks));
         s.chunks = (in.spp + s.cs - 1) / s.cs;
     }
-    s.n_items = in.n_pixels * s.chunks;
+    const bool subset = v.chain && in.subset_items > 0;
+    s.n_items = subset ? in.subset_items : in.n_pixels * s.chunks;
     // Speculative sample runahead (rt_mega.h) where the frame is mostly tail: a shard of at most
     // kSpecPixelsPerLane pixels per resident lane (the 8-way split of the headline: 342 -> 304
     // ms in round 2; at 4-way, 2 pixels per lane, 359 -> 348 ms in round 3).  A larger shard
     // runs the plain kernel and hands its tail off to the runahead kernel.
     const bool parity = !v.fast && !v.lsplit && !v.count && !(in.flags & RT_FLAG_NO_RUNAHEAD);
-    v.spec = parity && in.n_pixels * kClaimStride <= kSpecPixelsPerLane * in.spec_blocks * 256;
+    // (decided on the items: a small subset of a large shard is all tail)
+    v.spec = parity && s.n_items * kClaimStride <= kSpecPixelsPerLane * in.spec_blocks * 256;
     s.handoff = parity && !v.spec && kClaimStride == 1;
     s.sched = v.fast ? RT_SCHED_FAST : v.lsplit ? RT_SCHED_LIGHT_SPLIT : v.spec ? RT_SCHED_RUNAHEAD : RT_SCHED_LANE;
     if (s.handoff) s.sched |= RT_SCHED_RUNAHEAD;
     // (a pass is ordered by the rule on its own samples)
-    s.ordered = !v.fast && !(in.flags & RT_FLAG_NATURAL_ORDER) &&
+    s.ordered = !v.fast && !subset && !(in.flags & RT_FLAG_NATURAL_ORDER) &&
                 (s.stats_spp >= kOrderMinSpp || (in.flags & RT_FLAG_HEAVY_ORDER));
     s.round_min = in.n_nodes < kCoopRoundNodes ? kCoopRoundMinSpec : 65;
     return s;

@@ -12,6 +12,16 @@
 //   RT_CHECKPOINT=pfx   after every pass shard r of n is saved to pfx.<r>of<n>; if those files
 //                       exist at the start the run resumes from them (and fails with the
 //                       library's message when they do not fit the scene).
+// Adaptive rendering (per-pixel sample counts, rt_accum_select / rt_accum_add_selected):
+//   RT_ADAPT=t          the samples argument is the maximum per pixel and RT_PASS_SPP=k the step
+//                       (default 16).  Every shard renders k samples, marks, renders k more; then
+//                       rounds of: select the pixels below min(maximum, largest count + k) whose
+//                       error estimate exceeds t (t <= 0: all of them), stop when no shard
+//                       selects any or the maximum is reached, else mark and render the selected.
+//                       Prints "Progress: refined <pixels> pixels to <target> samples" per round
+//                       and writes the frame with every pixel divided by its own count.
+//   RT_COUNTS_OUT=path  (with RT_ADAPT) the sample-count map as a binary 16-bit PGM: "P5", maxval
+//                       65535, big-endian, counts clamped to it.
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
@@ -29,8 +39,10 @@ static void check(int rc) {
 }
 
 // The frame in passes: device d renders shard (rank d, world n) through its own accumulator.
+// `adapt` (RT_ADAPT): its threshold; the passes are then those of adaptive rendering (above).
 static void render_passes(rt_scene *scene, int width, int height, int samples, int n_gpus, int pass_spp,
-                          const char *ckpt, const std::string &output) {
+                          const char *ckpt, const std::string &output, const float *adapt = nullptr,
+                          const char *counts_out = nullptr) {
     const int n = n_gpus > 0 ? n_gpus : rt_device_count();
     if (n < 1) throw std::runtime_error("no HIP device");
     if (samples < 1) throw std::runtime_error("samples per pixel must be >= 1");
@@ -61,8 +73,11 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
         }
     }
     int done = rt_accum_samples(acc[0]);
-    for (int r = 1; r < n; ++r)
-        if (rt_accum_samples(acc[(size_t)r]) != done) throw std::runtime_error("checkpoint shards are at different sample counts");
+    for (int r = 1; r < n; ++r) {   // (adaptive shards may differ: `done` is then the largest count)
+        const int dr = rt_accum_samples(acc[(size_t)r]);
+        if (dr != done && !adapt) throw std::runtime_error("checkpoint shards are at different sample counts");
+        done = std::max(done, dr);
+    }
     if (done > samples)
         throw std::runtime_error("checkpoint holds " + std::to_string(done) + " samples, more than the " +
                                  std::to_string(samples) + " asked for");
@@ -81,6 +96,67 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
         }
         check(rt_write_ppm(output.c_str(), rgb.data(), width, height));
     };
+    auto save_all = [&]() {
+        if (ckpt)
+            for (int r = 0; r < n; ++r) check(rt_accum_save(acc[(size_t)r], file_of(r).c_str()));
+    };
+    if (adapt) {
+        const int k = pass_spp > 0 ? pass_spp : 16;
+        auto add_all = [&](int m) {
+            for (int r = 0; r < n; ++r) check(rt_accum_add(acc[(size_t)r], m, nullptr, nullptr));
+            done += m;
+        };
+        if (done == 0) {   // (a resumed run goes on with the rounds below; it has no mark: its first round selects by count alone)
+            add_all(std::min(k, samples));
+            for (int r = 0; r < n; ++r) check(rt_accum_mark(acc[(size_t)r], nullptr));
+            if (done < samples) add_all(std::min(k, samples - done));
+            std::cout << "Progress: " << done << " / " << samples << " samples" << std::endl;
+        }
+        while (done < samples) {
+            rt_select sel{};
+            sel.target = std::min(samples, done + k);
+            sel.threshold = *adapt;
+            int64_t total = 0;
+            for (int r = 0; r < n; ++r) {
+                int64_t m = 0;
+                check(rt_accum_select(acc[(size_t)r], &sel, nullptr, &m));
+                total += m;
+            }
+            if (total == 0) break;
+            for (int r = 0; r < n; ++r) {
+                check(rt_accum_mark(acc[(size_t)r], nullptr));
+                check(rt_accum_add_selected(acc[(size_t)r], nullptr, nullptr));
+            }
+            done = sel.target;
+            std::cout << "Progress: refined " << total << " pixels to " << sel.target << " samples" << std::endl;
+            save_all();
+        }
+        write_frame();
+        save_all();
+        if (counts_out) {
+            std::vector<int32_t> cpart;
+            std::vector<uint8_t> pgm((size_t)width * height * 2);
+            for (int r = 0; r < n; ++r) {
+                const int64_t kr = rt_shard_rows(height, r, n, 8, rows.data());
+                if (kr < 0) check((int)kr);
+                cpart.resize((size_t)kr * width);
+                check(rt_accum_counts(acc[(size_t)r], cpart.data()));
+                for (int64_t i = 0; i < kr; ++i)
+                    for (int x = 0; x < width; ++x) {
+                        const int32_t c = std::min<int32_t>(std::max<int32_t>(cpart[(size_t)i * width + x], 0), 65535);
+                        uint8_t *o = &pgm[((size_t)rows[(size_t)i] * width + x) * 2];
+                        o[0] = (uint8_t)(c >> 8);
+                        o[1] = (uint8_t)(c & 255);
+                    }
+            }
+            std::FILE *f = std::fopen(counts_out, "wb");
+            if (!f) throw std::runtime_error(std::string("RT_COUNTS_OUT: cannot write ") + counts_out);
+            std::fprintf(f, "P5\n%d %d\n65535\n", width, height);
+            const bool ok = std::fwrite(pgm.data(), 1, pgm.size(), f) == pgm.size();
+            if (std::fclose(f) != 0 || !ok) throw std::runtime_error(std::string("RT_COUNTS_OUT: short write to ") + counts_out);
+        }
+        return;
+    }
     if (done == samples && done > 0) write_frame();
     while (done < samples) {
         const int k = pass_spp > 0 ? std::min(pass_spp, samples - done) : samples - done;
@@ -113,11 +189,15 @@ int main(int argc, char *argv[]) {
     const char *g = std::getenv("RT_GPUS");
     const int n_gpus = g ? std::atoi(g) : 0;   // 0: every visible device
     const char *pass_env = std::getenv("RT_PASS_SPP"), *ckpt = std::getenv("RT_CHECKPOINT");
-    if ((pass_env && *pass_env) || (ckpt && *ckpt)) {
+    const char *adapt_env = std::getenv("RT_ADAPT"), *counts_out = std::getenv("RT_COUNTS_OUT");
+    const bool adaptive = adapt_env && *adapt_env;
+    const float adapt = adaptive ? std::strtof(adapt_env, nullptr) : 0.f;
+    if ((pass_env && *pass_env) || (ckpt && *ckpt) || adaptive) {
         const int pass_spp = pass_env && *pass_env ? std::atoi(pass_env) : 0;
         if (pass_env && *pass_env && pass_spp < 1) throw std::runtime_error("RT_PASS_SPP must be >= 1");
         try {
-            render_passes(scene, width, height, samples, n_gpus, pass_spp, ckpt && *ckpt ? ckpt : nullptr, output);
+            render_passes(scene, width, height, samples, n_gpus, pass_spp, ckpt && *ckpt ? ckpt : nullptr, output,
+                          adaptive ? &adapt : nullptr, adaptive && counts_out && *counts_out ? counts_out : nullptr);
         } catch (const std::exception &e) {   // (a checkpoint that does not fit, a failed pass: the message, status 1)
             std::cerr << "rt_solution: " << e.what() << std::endl;
             rt_scene_free(scene);

@@ -321,8 +321,12 @@ __device__ __forceinline__ void chain_init(uint4 *chain, const DevScene &sc, con
 // A pixel claimed from the queue: its next sample from its record, onto its record's sum.
 template <bool COUNT, class ML>
 __device__ __forceinline__ void mega_assign_chain(ML &L, const DevScene &sc, const ShardGeom &g, int p,
-                                                  const NodeRec &root, Counters &cnt, const uint4 *chain) {
+                                                  const NodeRec &root, Counters &cnt, const uint4 *chain,
+                                                  int spp = 0x7fffffff) {
     const Parked q = parked(chain, p);
+    // liveness: an item at or past the pass's end sample would never reach it (item lists come
+    // from rt_select_kernel only, whose rule includes next < target)
+    RT_CHECK((int)q.s < spp, 16, p, (void)0);
     L.pix = p;
     lane_ctr_set(L, LaneCtr{(int)q.s, 0, 0});
     lane_sum_set(L, q.sum);
