@@ -364,8 +364,10 @@ int rt_device_synchronize(void);
  * (float)b / 255.f for every byte, and the packed LDS RNG word round trip over every minstd
  * state and both normal-cache flags; which 2: the cooperative leaf step (rt_wavefront.h
  * trav_step_coop) against the per-lane in-order strict-< loop over 2^16 synthetic leaves rich
- * in equal-t ties, NaN and infinite vertices (four launches); *mismatches = values (cases)
- * that differ (0 = exact). */
+ * in equal-t ties, NaN and infinite vertices (four launches); which 3: the traversal's
+ * root-free cull (rt_wavefront.h far_gt and kFarMax2) against the device's sqrtf(x) > acc over
+ * 2^24 generated pairs around the rounding boundary, the special values and the floats
+ * around the 1e9 constant; *mismatches = values (cases) that differ (0 = exact). */
 int rt_device_selfcheck(int32_t which, uint64_t *mismatches);
 
 #ifdef __cplusplus

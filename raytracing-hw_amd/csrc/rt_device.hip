@@ -122,6 +122,23 @@ constexpr int kCoopLeavesSpec = RT_SPEC_COOP_LEAVES;   // the runahead kernel's 
 #define RT_SPEC_MASK_LOAD 1
 #endif
 constexpr bool kSpecMaskLoad = RT_SPEC_MASK_LOAD != 0;
+// Far frames carry the squared entry distance and the cull compares without a root
+// (rt_wavefront.h RT_FAR_DIST2); per kernel, because the two measured differently.  One call,
+// three interleaved runs each, new form against the sqrt form (profiles/dist2_ab.jsonl):
+//   plain kernel, 1-GPU frame      1006.9-1009.1 ms against 1020.8-1022.0 (-13.2 ms, spread 2.2);
+//   runahead kernel, 8-way shards  mean 171.0-171.2 against 173.2-173.5 ms, slowest
+//                                  172.3-173.2 against 175.1-175.2 (-2.4 ms, spread 0.9).
+// The rule was a mean gain of three times the larger spread: the plain kernel (and the other
+// non-runahead instantiations, which share its traversal loop) takes the new form; the
+// runahead kernel's slowest shard misses it (2.4 < 2.7 ms), so it keeps the sqrt form until a
+// measurement with more runs per shard settles it.
+#ifndef RT_PLAIN_FAR_DIST2
+#define RT_PLAIN_FAR_DIST2 RT_FAR_DIST2
+#endif
+#ifndef RT_SPEC_FAR_DIST2
+#define RT_SPEC_FAR_DIST2 0
+#endif
+constexpr bool kPlainFarDist2 = RT_PLAIN_FAR_DIST2 != 0, kSpecFarDist2 = RT_SPEC_FAR_DIST2 != 0;
 // Leaf rounds per coop step (rt_wavefront.h trav_step_coop round_min): a further round
 // while at least this many leaf lanes are unserved.  Plain kernel: 8 (sponza 1080p 1292 ->
 // 1278 ms against one round per step).  The runahead kernel's depends on the scene
@@ -551,7 +568,8 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
             int leaf_defer = 0;   // (the runahead kernel's leaf steps deferred in a row: rt_wavefront.h RT_LEAF_DEFER)
             do {
                 if (rtd::trav_step_coop<COUNT, kSpec ? kCoopLeavesSpec : kCoopLeavesPlain, kSpec && kSpecMaskLoad,
-                                        kSpec ? rtd::kLeafDefer : (COUNT ? 0 : rtd::kLeafDeferPlain)>(
+                                        kSpec ? rtd::kLeafDefer : (COUNT ? 0 : rtd::kLeafDeferPlain),
+                                        kSpec ? kSpecFarDist2 : kPlainFarDist2>(
                         sc, L.r, L.T, S, nodes, cnt, L.state == rtd::M_TRAV, kSpec ? st.round_min : kCoopRoundMinPlain,
                         rtd::NoHook{}, &leaf_defer))
                     L.state = rtd::M_READY;
@@ -2520,6 +2538,35 @@ __global__ void __launch_bounds__(256) decode_check_kernel(unsigned long long *b
     if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
 }
 
+// rt_device_selfcheck 3: the root-free cull (rt_wavefront.h far_gt, kFarMax2) against the
+// device's own sqrtf(x) > acc: 2^24 of the host test's generated pairs (far_case_acc /
+// far_case_x: every exponent of acc, x around acc * acc and around the exact boundary), the
+// special values (zeros, denormals, perfect squares, inf, NaN) and the floats within 64 ulps
+// of kFarMax2 against sqrtf(x) > 1e9f.
+__global__ void __launch_bounds__(256) far_check_kernel(unsigned long long *bad) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;   // (2^24 threads)
+    unsigned long long local = 0;
+    {
+        const uint32_t j = i / (uint32_t)rtd::kFarCaseXs, v = i % (uint32_t)rtd::kFarCaseXs;
+        const float acc = rtd::far_case_acc(j % (uint32_t)rtd::kFarCaseExps, j / (uint32_t)rtd::kFarCaseExps);
+        const float x = rtd::far_case_x(acc, (int)v);
+        local += rtd::far_gt(x, acc) != (sqrtf(x) > acc);
+    }
+    if (i < 54u) {
+        const float accs[6] = {0.f, -0.f, 1e-45f, 0x1p-126f, 1.f, 1e9f};
+        const float xs[9] = {0.f, 1e-45f, 0x1p-126f, 1.f, 4.f, 9.f, 1e18f, __builtin_inff(), __builtin_nanf("")};
+        const float acc = accs[i / 9u], x = xs[i % 9u];
+        local += rtd::far_gt(x, acc) != (sqrtf(x) > acc);
+    }
+    if (i < 132u) {
+        const float x = i < 129u ? rtd::far_case_step(rtd::kFarMax2, (int)i - 64)
+                                 : (i == 129u ? 0.f : (i == 130u ? __builtin_inff() : __builtin_nanf("")));
+        local += (x > rtd::kFarMax2) != (sqrtf(x) > 1e9f);
+    }
+    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
+    if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
+}
+
 }  // extern "C"
 
 // rt_device_selfcheck 2: the cooperative leaf step (rt_wavefront.h trav_step_coop: four
@@ -2641,7 +2688,7 @@ extern "C" {
 
 int rt_device_selfcheck(int32_t which, uint64_t *mismatches) {
     if (!mismatches) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck: null output");
-    if (which < 0 || which > 2) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck: unknown check " + std::to_string(which));
+    if (which < 0 || which > 3) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck: unknown check " + std::to_string(which));
     unsigned long long *d = nullptr;
     HIP_TRY(hipMalloc((void **)&d, sizeof *d));
     hipError_t e = hipMemset(d, 0, sizeof *d);
@@ -2651,6 +2698,8 @@ int rt_device_selfcheck(int32_t which, uint64_t *mismatches) {
             hipLaunchKernelGGL(rcp_check_kernel, dim3(4096), dim3(256), 0, nullptr, d);
         } else if (which == 1) {
             hipLaunchKernelGGL(decode_check_kernel, dim3(4096), dim3(256), 0, nullptr, d);
+        } else if (which == 3) {
+            hipLaunchKernelGGL(far_check_kernel, dim3((1u << 24) / 256u), dim3(256), 0, nullptr, d);
         } else {
             const int n_cases = 1 << 16;
             std::vector<float> tri, rays;

@@ -122,7 +122,8 @@ __device__ __forceinline__ void counters_flush(const Counters &c, unsigned long 
 //     has to wait for the near subtree;
 //   * frames are 8 bytes and carry the far child itself (its a/b fields and entry distance),
 //     so resuming a node never re-reads it:
-//       far frame  (a << 10 | b, entry distance)  pushed when both children are hit;
+//       far frame  (a << 10 | b, entry distance)  pushed when both children are hit
+//                                                  (the distance squared: RT_FAR_DIST2 below);
 //       best frame (kFrameAcc,  node's near best)  pushed when the far child is entered
 //                                                  after a near subtree.
 //     No frame is needed when a node has only one child to visit: its local best starts at
@@ -184,6 +185,74 @@ __device__ __forceinline__ float box_dist(const float coord[3], bool inside, con
     const float l = rtv::length(rtv::sub(V3{coord[0], coord[1], coord[2]}, r.o));
     return inside ? 0.f : l;
 }
+// The square of that distance before the root is rounded: rtv::sub and rtv::length's sum of
+// squares (from 0.f, x y z, no FMA), so box_dist = sqrtf(box_dist2) bit for bit.
+__device__ __forceinline__ float box_dist2(const float coord[3], bool inside, const Ray &r) {
+    const V3 v = rtv::sub(V3{coord[0], coord[1], coord[2]}, r.o);
+    float m = 0.f;
+    m += v.x * v.x;
+    m += v.y * v.y;
+    m += v.z * v.z;
+    return inside ? 0.f : m;
+}
+
+// Traversal only ever compares a far child's entry distance (at a pop against the near
+// subtree's best, in node_step against 1e9), so frames can carry box_dist2 and the root is
+// never taken (RT_FAR_DIST2): sqrtf is correctly rounded, hence
+//   sqrtf(x) > acc  <=>  sqrt(x) > m  <=>  x > m * m,
+// where m is the midpoint of |acc| and the next float up.  m has 25 significant bits, so
+// m * m is exact in double and is no float: no tie exists.  far_thr makes m from (double)|acc|
+// by setting the bit half a float ulp down (bit 28 of the 52); a denormal or zero acc gets an
+// m between 0 and 2^-126 that way (m * m may underflow to 0), which is as good as the true
+// midpoint: every float x > 0 has sqrtf(x) >= 2^-75 > acc, and x <= 0 has not.  A NaN x
+// compares false, as sqrtf(NaN) > acc does.  acc is never NaN and at most 1e9f.  Checked
+// against sqrtf on the host (tests/test_far_dist.py) and on the device (rt_device_selfcheck 3).
+// 0 restores the sqrt form in every kernel (A/B); the kernels take it as a template flag.
+#ifndef RT_FAR_DIST2
+#define RT_FAR_DIST2 1
+#endif
+constexpr bool kFarDist2 = RT_FAR_DIST2 != 0;
+__device__ __forceinline__ double far_thr(float acc) {
+    const double a = (double)__builtin_fabsf(acc);
+    unsigned long long u;
+    __builtin_memcpy(&u, &a, 8);
+    u |= 1ull << 28;
+    double m;
+    __builtin_memcpy(&m, &u, 8);
+    return m * m;
+}
+__device__ __forceinline__ bool far_gt_thr(float x, double thr) { return (double)x > thr; }
+__device__ __forceinline__ bool far_gt(float x, float acc) { return far_gt_thr(x, far_thr(acc)); }
+// The largest float x with sqrtf(x) <= 1e9f, for node_step's `entry distance > 1e9f`: 1e9f
+// is 1000000000, the next float up 1000000064, their midpoint m = 1000000032 and
+// m * m = 1000000064000001024 = 0x1.bc16d851c2d08p59 (exact in double); floats there are
+// 2^36 apart, so the last one below m * m is 0x1.bc16d8p59.
+constexpr float kFarMax2 = 0x1.bc16d8p59f;
+static_assert((double)kFarMax2 < 1000000032.0 * 1000000032.0 &&
+                  (double)kFarMax2 + 0x1p36 > 1000000032.0 * 1000000032.0,
+              "kFarMax2 is the last float below the midpoint's square");
+// The cases far_gt is checked on, by the host test and by rt_device_selfcheck 3.  acc: biased
+// exponent e (0: denormal .. 157: 2^30) and the n-th mantissa (0, all ones, then a
+// multiplicative hash), clamped to 1e9f.  x, for v = 0 .. 13: the floats within 4 ulps of
+// (float)(acc * acc), then within 2 ulps of the exact boundary m * m rounded to float.
+constexpr int kFarCaseExps = 158, kFarCaseXs = 14;
+__device__ __forceinline__ float far_case_step(float f, int d) {   // d floats up (down) from f
+    int32_t k = (int32_t)__float_as_uint(f);
+    if (k < 0) k = (int32_t)(0x80000000u - (uint32_t)k);   // (ordered: -0 and +0 are both 0)
+    k += d;
+    return __uint_as_float(k < 0 ? 0x80000000u - (uint32_t)k : (uint32_t)k);
+}
+__device__ __forceinline__ float far_case_acc(uint32_t e, uint32_t n) {
+    const uint32_t mant = n == 0 ? 0u : (n == 1 ? 0x7fffffu : (n * 2654435761u) >> 9);
+    const float a = __uint_as_float(e << 23 | mant);
+    return a > 1e9f ? 1e9f : a;
+}
+__device__ __forceinline__ float far_case_x(float acc, int v) {
+    if (v < 9) return far_case_step(acc * acc, v - 4);
+    const double m = 0.5 * ((double)acc + (double)far_case_step(acc, 1));
+    return far_case_step((float)(m * m), v - 11);
+}
+
 template <bool DIST>
 __device__ __forceinline__ bool box_hit(const float mn[3], const float mx[3], const Ray &r, float &dist) {
     float coord[3];
@@ -422,10 +491,14 @@ constexpr int kMaxPops = RT_MAX_POPS;
 // The return of trav_step: merge subtree bests upwards until a far child is to be visited
 // (enter it: false), the stack is empty (T.best is final: true) or kMaxPops frames are
 // popped (false, still TP_POP).
-template <class Stack, class TS>
+// DIST2: far frames hold the squared entry distance (node_step); the cull compares it with
+// far_thr(acc), made once here and again only where a best frame changes acc, so a far frame
+// costs one conversion and one f64 compare in place of the f32 compare.
+template <bool DIST2 = kFarDist2, class Stack, class TS>
 __device__ __forceinline__ bool trav_pop(TS &T, Stack &stk) {
     float acc = T.acc;
     int sp = T.sp;
+    double thr = DIST2 ? far_thr(acc) : 0.0;
     for (int n = 0;; ++n) {
         if (sp == 0) {
             T.sp = 0;
@@ -441,9 +514,11 @@ __device__ __forceinline__ bool trav_pop(TS &T, Stack &stk) {
         if (f.x == kFrameAcc) {
             const float p = __uint_as_float(f.y);
             acc = acc < p ? acc : p;
+            if (DIST2) thr = far_thr(acc);
             continue;
         }
-        if (!(__uint_as_float(f.y) > acc)) {   // far child survives the near subtree's best
+        const float e = __uint_as_float(f.y);
+        if (!(DIST2 ? far_gt_thr(e, thr) : e > acc)) {   // far child survives the near subtree's best
             stk.put(sp++, make_uint2(kFrameAcc, __float_as_uint(acc)));
 #ifdef RT_STACK_PROBE
             RT_STACK_PROBE(sp);
@@ -459,7 +534,7 @@ __device__ __forceinline__ bool trav_pop(TS &T, Stack &stk) {
 // The node part of a traversal step: the child pair q[0..3] (two 32-B node records) of the
 // internal node T is entering; pushes the far child when both are hit, enters the near one
 // (or the far one alone, or returns: T.phase = TP_POP).
-template <bool COUNT, class Stack, class TS>
+template <bool COUNT, bool DIST2 = kFarDist2, class Stack, class TS>
 __device__ __forceinline__ void node_step(const float4 q[4], const Ray &r, TS &T, Stack &stk, Counters &cnt) {
     NodeRec L, R;
     L.mn[0] = q[0].x; L.mn[1] = q[0].y; L.mn[2] = q[0].z; L.mx[0] = q[0].w; L.mx[1] = q[1].x; L.mx[2] = q[1].y;
@@ -474,7 +549,8 @@ __device__ __forceinline__ void node_step(const float4 q[4], const Ray &r, TS &T
     float cF[3];
     bool hL, hR, inF;
     box_pair_hit(L, R, r, lf, hL, hR, cF, inF);
-    const float ef = box_dist(cF, inF, r);   // the far child's entry distance
+    // the far child's entry distance (DIST2: its square, far_gt's operand)
+    const float ef = DIST2 ? box_dist2(cF, inF, r) : box_dist(cF, inF, r);
     const bool hn = lf ? hL : hR, hf = lf ? hR : hL;
     const uint32_t na = lf ? L.a : R.a, nb = lf ? L.b : R.b, fa = lf ? R.a : L.a, fb = lf ? R.b : L.b;
     if (hn && hf) {
@@ -486,7 +562,7 @@ __device__ __forceinline__ void node_step(const float4 q[4], const Ray &r, TS &T
     }
     // near child; or, the near box missed, the far child unless its entry distance
     // exceeds the node's local best (still 1e9); or return
-    const bool far_only = !hn && hf && !(ef > 1e9f);
+    const bool far_only = !hn && hf && !(DIST2 ? ef > kFarMax2 : ef > 1e9f);
     if (hn || far_only) trav_enter(T, hn ? na : fa, hn ? nb : fb);
     else T.phase = TP_POP;
 }
@@ -500,7 +576,7 @@ __device__ __forceinline__ void node_step(const float4 q[4], const Ray &r, TS &T
 // Both memory reads of the step issue before either test (node lanes and leaf lanes load
 // through the same registers), so a wave split between node and leaf steps waits for one
 // round trip per iteration, not two.
-template <bool COUNT, class Stack, class Nodes, class TS>
+template <bool COUNT, bool DIST2 = kFarDist2, class Stack, class Nodes, class TS>
 __device__ __forceinline__ bool trav_step(const DevScene &sc, const Ray &r, TS &T, Stack &stk,
                                           const Nodes &nodes, Counters &cnt) {
     constexpr int N = RT_LEAF_N;
@@ -526,7 +602,7 @@ __device__ __forceinline__ bool trav_step(const DevScene &sc, const Ray &r, TS &
 #endif
     }
     if (at_node) {
-        node_step<COUNT>(q, r, T, stk, cnt);
+        node_step<COUNT, DIST2>(q, r, T, stk, cnt);
     } else if (at_leaf) {
 #pragma unroll
         for (int j = 0; j < N; ++j) {
@@ -544,7 +620,7 @@ __device__ __forceinline__ bool trav_step(const DevScene &sc, const Ray &r, TS &
         T.k = k + N;
         if (T.k >= T.kend) T.phase = TP_POP;
     }
-    if (T.phase == TP_POP) return trav_pop(T, stk);
+    if (T.phase == TP_POP) return trav_pop<DIST2>(T, stk);
     return false;
 }
 
@@ -697,8 +773,8 @@ constexpr int kLeafDefer = RT_LEAF_DEFER, kLeafDeferMax = RT_LEAF_DEFER_MAX;
 #define RT_PLAIN_LEAF_DEFER 6
 #endif
 constexpr int kLeafDeferPlain = RT_PLAIN_LEAF_DEFER;
-template <bool COUNT, int kCoopLeaves, bool MASK_LOAD, int DEFER = kLeafDefer, class Stack, class Nodes, class TS,
-          class Hook = NoHook>
+template <bool COUNT, int kCoopLeaves, bool MASK_LOAD, int DEFER = kLeafDefer, bool DIST2 = kFarDist2, class Stack,
+          class Nodes, class TS, class Hook = NoHook>
 __device__ __forceinline__ bool trav_step_coop(const DevScene &sc, const Ray &r, TS &T, Stack &stk,
                                                const Nodes &nodes, Counters &cnt, bool active, int round_min,
                                                const Hook &hook = Hook{}, int *leaf_defer = nullptr) {
@@ -799,8 +875,8 @@ __device__ __forceinline__ bool trav_step_coop(const DevScene &sc, const Ray &r,
     }
     hook();
     // node lanes: the pair test
-    if (at_node) node_step<COUNT>(q, r, T, stk, cnt);
-    if (active && T.phase == TP_POP) return trav_pop(T, stk);
+    if (at_node) node_step<COUNT, DIST2>(q, r, T, stk, cnt);
+    if (active && T.phase == TP_POP) return trav_pop<DIST2>(T, stk);
     return false;
 }
 
