@@ -218,7 +218,8 @@ int rt_render_frame(rt_scene *scene, const rt_params *params, int32_t n_shards, 
  * sum.  This is the seam for the reference's Scene::render(ProgressFunc): previews, progress,
  * early stop, more samples on a finished frame, checkpoint and resume.
  *
- * Parity mode on the lane-resident kernel only: RT_FLAG_NATURAL_ORDER, RT_FLAG_HEAVY_ORDER and
+ * (Fast mode has accumulators of its own kind, with their own invariant: rt_accum_create_fast
+ * below.)  Parity mode on the lane-resident kernel only: RT_FLAG_NATURAL_ORDER, RT_FLAG_HEAVY_ORDER and
  * RT_FLAG_NO_RUNAHEAD are honoured; RT_FLAG_FAST, RT_FLAG_LIGHT_SPLIT, RT_FLAG_KERNEL_TIMES,
  * count != 0 and kernel != RT_KERNEL_LANE fail with RT_ERR_ARG.  The pixel order is chosen per
  * pass by rt_render's rule on the pass's own sample count (pre-pass at >= 128 samples or with
@@ -326,6 +327,50 @@ int rt_accum_sample_range(rt_accum *accum, int32_t *min_out, int32_t *max_out);
  * as the largest count, and rt_accum_load then accepts any record whose next sample is at most
  * that (with 0 there, every record must equal it, as before).  The rule "one render per (scene,
  * device) in flight" covers rt_accum_mark, rt_accum_select and rt_accum_add_selected. */
+
+/* --- fast-mode accumulators: progressive and adaptive passes on Philox units (additive in ABI 6) --- */
+/* A fast accumulator is an rt_accum whose passes render fast-mode work units (RT_FLAG_FAST): sample
+ * s of a pixel draws from its own Philox stream keyed by (pixel, s), so its record needs no RNG
+ * state and a pixel's samples have no chain: a subset pass is as parallel as a full one.  A one-shot
+ * fast sum is defined by where its chunk boundaries fall, and rt_render moves them with spp; here
+ * they never move.  The accumulator has a chunk size c >= 1, fixed at creation from
+ * params->fast_chunk (0 = 2) and never raised: chunk j of a pixel is its samples [j c, (j + 1) c).
+ *
+ * Invariant: after any sequence of full and subset passes of any sizes, a pixel that has n samples
+ * holds, bit for bit, the fast sum of n samples in chunks of c: the partials of chunks 0, 1, ...
+ * (each the sum of its samples in sample order, from +0.f) added in chunk order from +0.f, the
+ * last one ragged when c does not divide n (the CPU oracle's rt_oracle_render_fast(spp = n,
+ * chunk = c)).  For n <= 128 c that is also rt_render with RT_FLAG_FAST at spp = n, fast_chunk = c.
+ *
+ * Per pixel the 32-byte record holds (pixel, next sample, total x, y, z, open x, y, z):
+ *   total  the fold, from +0.f, of the partials of all complete chunks, in chunk order;
+ *   open   the running partial of the chunk that contains `next` when next % c != 0, zero words
+ *          otherwise;
+ * and the reported sum (rt_accum_sums, rt_accum_device_sums, what rt_accum_mark copies and the
+ * selection rule and the frame finish read) is total when next % c == 0, else total + open (always
+ * added; open is never reported alone).  So a pass may stop and resume anywhere, in or between
+ * chunks.  csrc/rt_fast_units.h is the text of the unit arithmetic and the fold, shared by the
+ * device and the CPU test.
+ *
+ * Every rt_accum_* entry works on a fast accumulator as on a parity one, with these differences:
+ *   rt_accum_add / rt_accum_add_selected  any n >= 1 and any target, multiples of c or not; stats
+ *       schedule = RT_SCHED_FAST, order_ms = 0, pixels and samples as for parity passes.  A launch
+ *       carries at most 128 units per item; a pass that needs more runs as successive complete
+ *       passes to chunk boundaries on the way (same bits).  Items are never ordered.
+ *   rt_accum_state   n_pixels x 4 words: next sample, then the three words of `open`.
+ *   rt_accum_save    magic "RTFACCUM", u32 version 1, the same 128-byte header with c (i32) in the
+ *       first four of its eight trailing bytes, then the records verbatim.  Marks are not saved.
+ *   rt_accum_load    reads both kinds (the magic says which) and returns that kind; for a fast
+ *       file, besides the parity checks (the record / samples-done rule included): c < 1 and
+ *       non-zero `open` words where next % c == 0 are RT_ERR_FORMAT.  All before any device call.
+ * rt_accum_create_fast uses rank, world, row_block, device and fast_chunk of params; the scene must
+ * be uploaded to that device.  RT_FLAG_FAST may be set or not; RT_FLAG_NATURAL_ORDER,
+ * RT_FLAG_HEAVY_ORDER and RT_FLAG_NO_RUNAHEAD are accepted and ignored.  count != 0, a kernel other
+ * than RT_KERNEL_LANE, RT_FLAG_LIGHT_SPLIT, RT_FLAG_KERNEL_TIMES and fast_chunk < 0 fail with
+ * RT_ERR_ARG.  (rt_accum_create goes on refusing RT_FLAG_FAST: its accumulators are parity ones.) */
+int rt_accum_create_fast(rt_scene *scene, const rt_params *params, rt_accum **out);
+/* The accumulator's chunk size c; 0 for a parity accumulator (or NULL). */
+int32_t rt_accum_fast_chunk(const rt_accum *accum);
 
 /* Closest hit + light pdf for n explicit rays (BVH::intersect bvh.cpp:239-243 and
  * ManyLightsDistribution::pdf random.cpp:179-188; origin/dir as given to Ray::Ray, which

@@ -132,6 +132,9 @@ ABI = {
     "rt_tonemap_u8_counts": (ctypes.c_int, [_c_f, _c_i, ctypes.c_int32, ctypes.c_int32, _c_b]),
     "rt_tonemap_u8_counts_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.c_void_p, ctypes.c_void_p]),
+    # fast-mode accumulators: progressive and adaptive passes on Philox units
+    "rt_accum_create_fast": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtParams), ctypes.POINTER(ctypes.c_void_p)]),
+    "rt_accum_fast_chunk": (ctypes.c_int32, [ctypes.c_void_p]),
 }
 
 _lib_handle = None
@@ -356,27 +359,30 @@ class Scene:
         return st.as_dict() if st else None
 
     def accumulator(self, rank=0, world=1, row_block=8, device=0, natural_order=False, heavy_order=False,
-                    runahead=True):
+                    runahead=True, fast=False, fast_chunk=0):
         """Progressive rendering (rt_accum_create): the shard's per-pixel chain state on
         `device` (uploaded here if need be), rendered further in passes of any size; after
         passes of n1 + ... + nk samples the sums are those of render_sums(n1 + ... + nk), bit
-        for bit."""
+        for bit.  fast=True (rt_accum_create_fast): a fast-mode accumulator with chunks of
+        fast_chunk samples (0 = 2), fixed for its life; a pixel with n samples then holds the
+        fast sum of n samples in chunks of that size, whatever the passes were."""
         self.upload(device)
         p = self._params(0, rank, world, row_block, False, KERNEL_LANE, device=device, natural_order=natural_order,
-                         runahead=runahead, heavy_order=heavy_order)
+                         runahead=runahead, heavy_order=heavy_order, fast=fast, fast_chunk=fast_chunk if fast else 0)
         h = ctypes.c_void_p()
-        _check(lib().rt_accum_create(self._h, ctypes.byref(p), ctypes.byref(h)))
+        _check((lib().rt_accum_create_fast if fast else lib().rt_accum_create)(self._h, ctypes.byref(p), ctypes.byref(h)))
         return Accumulator(self, h.value, rank, world, row_block)
 
-    def render_adaptive(self, min_spp, max_spp, step, threshold, device=0):
+    def render_adaptive(self, min_spp, max_spp, step, threshold, device=0, fast=False, fast_chunk=0):
         """Adaptive sampling of the whole frame on one shard (the loop of the CLI's RT_ADAPT):
         min_spp samples everywhere in two halves with a mark between them, then rounds of
         select(target = min(max_spp, largest count + step), threshold), mark, add_selected until
         nothing is selected or max_spp is reached.  Returns (sums (H, W, 3), counts (H, W),
-        frame (H, W, 3) uint8 finished per pixel by its own count)."""
+        frame (H, W, 3) uint8 finished per pixel by its own count).  fast / fast_chunk: on a
+        fast-mode accumulator (see accumulator)."""
         if min_spp < 2 or max_spp < min_spp or step < 1:
             raise ValueError("render_adaptive: need 2 <= min_spp <= max_spp and step >= 1")
-        acc = self.accumulator(device=device)
+        acc = self.accumulator(device=device, fast=fast, fast_chunk=fast_chunk)
         try:
             acc.add(min_spp // 2)
             acc.mark()
@@ -415,7 +421,8 @@ class Accumulator:
 
     @classmethod
     def load(cls, scene, path, device=0):
-        """rt_accum_load: the accumulator rt_accum_save wrote, checked against `scene`."""
+        """rt_accum_load: the accumulator rt_accum_save wrote (of either kind: see fast_chunk),
+        checked against `scene`."""
         h = ctypes.c_void_p()
         _check(lib().rt_accum_load(scene.handle, device, os.fsencode(path), ctypes.byref(h)))
         with open(path, "rb") as f:   # rank, world, row_block: int32 words 6-8 of the header
@@ -434,6 +441,11 @@ class Accumulator:
     def samples(self):
         return int(lib().rt_accum_samples(self._h))
 
+    @property
+    def fast_chunk(self):
+        """The chunk size of a fast-mode accumulator (rt_accum_fast_chunk); 0 for a parity one."""
+        return int(lib().rt_accum_fast_chunk(self._h))
+
     def sums(self):
         """(rows, W, 3) float sums so far, as render_sums returns them."""
         out = np.zeros((len(self.rows), self._scene.width, 3), np.float32)
@@ -451,7 +463,8 @@ class Accumulator:
         return out
 
     def state(self):
-        """(pixels, 4) uint32 per shard pixel: next sample, engine state, cache flag, cached value bits."""
+        """(pixels, 4) uint32 per shard pixel: next sample, engine state, cache flag, cached value bits
+        (a fast-mode accumulator: next sample and the three words of the open chunk's partial)."""
         out = np.zeros((len(self.rows) * self._scene.width, 4), np.uint32)
         _check(lib().rt_accum_state(self._h, out.ctypes.data_as(_c_u)))
         return out

@@ -342,19 +342,28 @@ __global__ void __launch_bounds__(256) rt_finish_counts_kernel(const float *sum,
 // record in the chain buffer and the lane that adds its last sample stores the record back
 // (rt_mega.h, chain buffer; the buffer's address in the queue block, read where used).  Separate
 // instantiations again: the one-shot kernels are the code they were.
+// FAST + CHAIN (rt_accum_create_fast): the pass of a fast accumulator.  `cs` is the accumulator's
+// chunk size, `mode` the units per item K and st.n the items; queue item q = k * st.n + i is unit k
+// of item i (pixel `order ? order[i] : i`), its samples cut from the pixel's record and the pass's
+// end `spp` (rt_mega.h mega_assign_fast_chain).  The kernel only reads records; its partials go to
+// the unit-major partial buffer and rt_fast_fold_chain_kernel folds them.  A unit past its pixel's
+// own starts nothing (the lane claims again), so a wave may leave only once the queue is empty.
 template <bool COUNT, bool FAST = false, bool LSPLIT = false, bool SPEC = false, bool CHAIN = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SPEC ? kMegaWpeSpec : kMegaWpe, 8)))
 rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out, unsigned long long *counters,
                unsigned long long *queue, const int *order, unsigned *cost, int cs, int mode) {
     constexpr bool kSpec = SPEC && !COUNT && !FAST && !LSPLIT;
     constexpr bool kChain = CHAIN && !COUNT && !FAST && !LSPLIT;
-    const int park_below = rtp::mode_park_below(mode), resume_pct = rtp::mode_resume_pct(mode);
+    // (a pass of a fast accumulator: `cs` is its chunk size, `mode` the units per item)
+    constexpr bool kFastChain = CHAIN && FAST && !COUNT && !LSPLIT && !SPEC;
+    const int park_below = kFastChain ? 0 : rtp::mode_park_below(mode), resume_pct = kFastChain ? 0 : rtp::mode_resume_pct(mode);
     const uint4 *resume = kSpec && resume_pct > 0 ? (const uint4 *)queue[rtd::kQueueParkList] : nullptr;
     // (CHAIN: the pass's item count, the shard's pixels for a full pass or a selection's length
     // for a subset pass, whose pixels `order` lists; a constant of the instantiation chooses, so
     // the one-shot kernels read what they read before)
-    const long long n_items = FAST ? g.n_pixels * (long long)((spp + cs - 1) / cs)
-                                   : (kChain || (kSpec && resume)) ? st.n : g.n_pixels;
+    const long long n_items = kFastChain ? st.n * (long long)mode
+                              : FAST     ? g.n_pixels * (long long)((spp + cs - 1) / cs)
+                                         : (kChain || (kSpec && resume)) ? st.n : g.n_pixels;
     const int lane = threadIdx.x & 63;
     // sRGB texel-decode table in LDS: the shading's lane-dependent lookups become ds_reads (the
     // linear decode is computed: rt_path.h texel_decode)
@@ -482,7 +491,9 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
                 if (need) {
                     const long long p = (long long)base + below;
                     if (p < n_items) {
-                        if (FAST) rtd::mega_assign_fast<COUNT>(L, sc, g, p, cs, spp, root, cnt);
+                        if constexpr (kFastChain)
+                            rtd::mega_assign_fast_chain<COUNT>(L, sc, g, p, st.n, order, cs, spp, root, cnt, rtd::chain_of(queue));
+                        else if (FAST) rtd::mega_assign_fast<COUNT>(L, sc, g, p, cs, spp, root, cnt);
                         else if constexpr (kChain)
                             rtd::mega_assign_chain<COUNT>(L, sc, g, order ? order[p] : (int)p, root, cnt, rtd::chain_of(queue), spp);
                         else rtd::mega_assign<COUNT>(L, sc, g, order ? order[p] : (int)p, root, cnt);
@@ -525,6 +536,13 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
                 if (!__any(L.state != rtd::M_IDLE)) break;
             } else if (!__any(L.pix >= 0)) {
                 break;
+            }
+        } else if constexpr (kFastChain) {
+            // (a claim may leave every lane without a pixel, all its units being past their
+            // pixels' own: the wave leaves only once the queue is empty too, else claims again)
+            if (!__any(L.pix >= 0)) {
+                if (exhausted) break;
+                continue;
             }
         } else if (!__any(L.pix >= 0)) {
             break;
@@ -653,6 +671,35 @@ __global__ void __launch_bounds__(256) rt_fast_reduce_kernel(const float *__rest
     float s = 0.f;
     for (int c = 0; c < chunks; ++c) s += part[(long long)c * n3 + i];
     out[i] = s;
+}
+
+// A fast accumulator's pass, after its render launch: one thread per item of the pass (`items`
+// lists their shard pixels, null = every pixel) folds the item's partials (unit-major: unit k of
+// item i at k * n_list + i) into its record and writes the record and the pixel's reported sum
+// (rt_fast_units.h fold, reported).  The only writer of fast records besides their init; pixels
+// not listed, and items already at `target`, are not touched.  `units`: the launch's units per
+// item (at least every item's own).
+struct FastPartials {
+    const float *part;
+    long long n_list, i;
+    RT_HD float operator()(int k, int ch) const { return part[3 * ((long long)k * n_list + i) + ch]; }
+};
+__global__ void __launch_bounds__(256) rt_fast_fold_chain_kernel(uint4 *chain, const int *items, long long n_list, int units,
+                                                                  int c, int target, const float *__restrict__ part,
+                                                                  float *sums) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_list) return;
+    const long long p = items ? (long long)items[i] : i;
+    rtd::FastRec q = rtd::fast_rec(chain, p);
+    const int own = rtfu::units_of(q.r.next, target, c);
+    if (own < 1 || own > units) return;   // (nothing rendered for it / never: the launch has the largest count)
+    rtfu::fold(q.r, target, c, FastPartials{part, n_list, i});
+    rtd::fast_rec_store(chain, p, q.r);
+    float s[3];
+    rtfu::reported(q.r, c, s);
+    sums[3 * p + 0] = s[0];
+    sums[3 * p + 1] = s[1];
+    sums[3 * p + 2] = s[2];
 }
 
 // Pixel order, step 1: the sort's values (shard pixel ids) and keys (pre-pass costs).
@@ -1267,10 +1314,12 @@ int launch_order(rt_device_scene *d, const ShardGeom &g, hipStream_t stream, lon
 MegaKernel mega_kernel_of(const rtp::Variant &v) {
     if (v.count && v.fast) return rt_mega_kernel<true, true>;
     if (v.spec) return v.chain ? rt_mega_kernel<false, false, false, true, true> : rt_mega_kernel<false, false, false, true>;
-    if (v.fast) return rt_mega_kernel<false, true>;
+    if (v.fast && !v.chain) return rt_mega_kernel<false, true>;
     if (v.lsplit) return v.count ? rt_mega_kernel<true, false, true> : rt_mega_kernel<false, false, true>;
     if (!v.count && !v.chain) return rt_mega_kernel<false>;   // the plain kernel
-    return v.count ? rt_mega_kernel<true> : rt_mega_kernel<false, false, false, false, true>;
+    if (v.count) return rt_mega_kernel<true>;
+    if (!v.fast) return rt_mega_kernel<false, false, false, false, true>;
+    return rt_mega_kernel<false, true, false, false, true>;   // a fast accumulator's pass (named last: the listing's order)
 }
 
 // Flag bits outside RT_FLAG_ALL (e.g. ABI 5's RT_FLAG_POOL) are an error, not ignored.
@@ -1314,6 +1363,9 @@ struct ChainPass {
     const int *items = nullptr;
     long long n_items = 0;
     unsigned long long samples = 0;
+    // A fast accumulator's pass (rt_accum_create_fast): its chunk size and the work units every
+    // item of this launch gets (rt_launch_plan.h PlanIn.fast_units); 0, 0 for a parity pass.
+    int fast_c = 0, fast_units = 0;
 };
 
 // One word of the queue block, written in stream order.
@@ -1419,6 +1471,11 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
     in.spp = p->spp > 0 ? p->spp : s->samples;
     in.pass_spp = cp ? cp->n : 0;
     in.subset_items = cp && cp->items ? cp->n_items : 0;
+    if (cp && cp->fast_c > 0) {   // (the accumulator's chunk size, not the call's)
+        in.fast_accum = true;
+        in.fast_chunk = cp->fast_c;
+        in.fast_units = cp->fast_units;
+    }
     in.ray_depth = s->ray_depth;
     if (const rtp::Refusal r = rtp::plan_check(in)) return rt_fail(r.code, r.msg);
     Shard sh;
@@ -1482,12 +1539,18 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
         // the chain buffer's address, where the chain kernels read it
         if (cp)
             if (int rc = set_queue_word(d, rtd::kChainWord, cp->chain, stream)) return rc;
+        const bool fast_pass = plan.v.fast && plan.v.chain;   // (its `mode` argument: the units per item)
         hipLaunchKernelGGL(mk, dim3((unsigned)grid.blocks), dim3(256), 0, stream, d->ds, g, w, in.spp, k_out, d->counters,
-                           d->queue, order, (unsigned *)nullptr, plan.cs, rtp::mode_pack(plan.handoff ? rtp::kHandoffBelow : 0, 0));
+                           d->queue, order, (unsigned *)nullptr, plan.cs,
+                           fast_pass ? plan.chunks : rtp::mode_pack(plan.handoff ? rtp::kHandoffBelow : 0, 0));
         HIP_TRY(hipGetLastError());
         if (plan.handoff)
             if (int rc = launch_handoff(d, g, grid, rk, w, in.spp, k_out, stream)) return rc;
-        if (plan.v.fast) {
+        if (fast_pass) {   // the items' partials into their records and reported sums (d_out: the accumulator's sums)
+            hipLaunchKernelGGL(rt_fast_fold_chain_kernel, dim3((unsigned)((w.n + 255) / 256)), dim3(256), 0, stream, cp->chain,
+                               order, w.n, plan.chunks, plan.cs, in.spp, (const float *)d->fast_part, d_out);
+            HIP_TRY(hipGetLastError());
+        } else if (plan.v.fast) {
             const long long n3 = g.n_pixels * 3;
             hipLaunchKernelGGL(rt_fast_reduce_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, stream,
                                (const float *)d->fast_part, d_out, n3, plan.chunks);
@@ -1645,13 +1708,18 @@ struct rt_accum {
     bool sel_pending = false;
     long long sel_n = 0;
     unsigned long long sel_samples = 0;
-    int sel_target = 0, sel_min = 0, sel_max = 0;
+    int sel_target = 0, sel_min = 0, sel_max = 0, sel_from = 0;
+    // A fast accumulator (rt_accum_create_fast): its chunk size, fixed for its life; 0 = parity.
+    // Its chain buffer then holds fast records (rt_mega.h FastRec).
+    int fast_c = 0;
 };
 
 // What rt_select_kernel reduces besides the list (device words, zeroed / set before the launch).
 struct SelectOut {
     unsigned long long n_selected, samples;   // samples: sum of (target - next) over the selected
     int next_min, next_max;                   // of `next` as it will be after the pass
+    int from_min, reserved;                   // the smallest `next` among the selected, as it stands (a fast
+                                              // pass's units per item come from it); INT32_MAX for an empty list
 };
 
 // The selection (rt_accum_select, rt_select.h): one thread per shard pixel applies the rule.
@@ -1667,7 +1735,7 @@ __global__ void __launch_bounds__(256) rt_select_kernel(ShardGeom g, rtsel::Rule
                                                          const uint8_t *mask, unsigned *blocks, int *list, SelectOut *out) {
     __shared__ unsigned wave_n[4];
     __shared__ unsigned long long wave_s[4];
-    __shared__ int wave_lo[4], wave_hi[4];
+    __shared__ int wave_lo[4], wave_hi[4], wave_from[4];
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     bool sel = false;
@@ -1692,15 +1760,18 @@ __global__ void __launch_bounds__(256) rt_select_kernel(ShardGeom g, rtsel::Rule
         unsigned long long s = sel ? (unsigned long long)(rule.target - n_b) : 0ull;
         const int after = sel ? rule.target : n_b;
         int lo = p < g.n_pixels ? after : 0x7fffffff, hi = p < g.n_pixels ? after : 0;
+        int from = sel ? n_b : 0x7fffffff;
         for (int k = 32; k > 0; k >>= 1) {
             s += __shfl_xor(s, k, 64);
             lo = min(lo, __shfl_xor(lo, k, 64));
             hi = max(hi, __shfl_xor(hi, k, 64));
+            from = min(from, __shfl_xor(from, k, 64));
         }
         if (lane == 0) {
             wave_s[wave] = s;
             wave_lo[wave] = lo;
             wave_hi[wave] = hi;
+            wave_from[wave] = from;
         }
     }
     __syncthreads();
@@ -1716,6 +1787,7 @@ __global__ void __launch_bounds__(256) rt_select_kernel(ShardGeom g, rtsel::Rule
         atomicAdd(&out->samples, wave_s[0] + wave_s[1] + wave_s[2] + wave_s[3]);
         atomicMin(&out->next_min, min(min(wave_lo[0], wave_lo[1]), min(wave_lo[2], wave_lo[3])));
         atomicMax(&out->next_max, max(max(wave_hi[0], wave_hi[1]), max(wave_hi[2], wave_hi[3])));
+        atomicMin(&out->from_min, min(min(wave_from[0], wave_from[1]), min(wave_from[2], wave_from[3])));
     }
 }
 
@@ -1771,6 +1843,16 @@ __global__ void __launch_bounds__(256) rt_chain_init_kernel(DevScene sc, ShardGe
     sums[3 * p + 2] = 0.f;
 }
 
+// A fresh fast record: no samples, total and open +0.
+__global__ void __launch_bounds__(256) rt_fast_chain_init_kernel(long long n, uint4 *chain, float *sums) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    rtd::fast_rec_store(chain, p, rtfu::Rec{0, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}});
+    sums[3 * p + 0] = 0.f;
+    sums[3 * p + 1] = 0.f;
+    sums[3 * p + 2] = 0.f;
+}
+
 namespace {
 
 // The checkpoint file (rt_accum_save): this header, then n_pixels records of 8 words in the
@@ -1778,6 +1860,10 @@ namespace {
 // sum x, y, z, 0).  Little-endian, as the devices and their hosts are.
 constexpr char kAccumMagic[8] = {'R', 'T', 'A', 'C', 'C', 'U', 'M', '\0'};
 constexpr uint32_t kAccumVersion = 1;
+// A fast accumulator's file: its own magic (version 1), the same header with the chunk size in
+// pad[0], and fast records (pixel, next sample, total x, y | total z, open x, y, z) verbatim.
+constexpr char kFastAccumMagic[8] = {'R', 'T', 'F', 'A', 'C', 'C', 'U', 'M'};
+constexpr uint32_t kFastAccumVersion = 1;
 struct AccumHeader {
     char magic[8];
     uint32_t version;
@@ -1810,13 +1896,29 @@ void accum_header_fill(const rt_scene *s, AccumHeader &h) {
 int accum_check_params(const rt_params *p, const char *who) {
     if (int rc = check_flags(p, who)) return rc;
     const std::string w = who;
-    if (p->flags & RT_FLAG_FAST) return rt_fail(RT_ERR_ARG, w + ": fast mode has no accumulator (its sum is defined per (spp, fast_chunk))");
+    if (p->flags & RT_FLAG_FAST)
+        return rt_fail(RT_ERR_ARG, w + ": fast mode has no accumulator here (a one-shot fast sum is defined per (spp, fast_chunk)); "
+                                       "use rt_accum_create_fast");
     if (p->flags & RT_FLAG_LIGHT_SPLIT) return rt_fail(RT_ERR_ARG, w + ": the light-split kernel has no accumulator");
     if (p->flags & RT_FLAG_KERNEL_TIMES) return rt_fail(RT_ERR_ARG, w + ": RT_FLAG_KERNEL_TIMES is a wavefront option; accumulators run on kernel 0");
     if (p->count != 0) return rt_fail(RT_ERR_ARG, w + ": counting renders have no accumulator (count must be 0)");
     if (p->kernel != RT_KERNEL_LANE) return rt_fail(RT_ERR_ARG, w + ": accumulators run on the lane-resident kernel only (kernel 0)");
     if (rtp::order_flags_conflict(p->flags))
         return rt_fail(RT_ERR_ARG, w + ": RT_FLAG_NATURAL_ORDER and RT_FLAG_HEAVY_ORDER exclude each other");
+    return RT_OK;
+}
+
+// What a fast accumulator renders with: fast units on the lane-resident kernel.  The order flags
+// and RT_FLAG_NO_RUNAHEAD are accepted and ignored (fast units are never ordered and have no
+// chain to run ahead of); RT_FLAG_FAST may be set or not.
+int accum_check_params_fast(const rt_params *p, const char *who) {
+    if (int rc = check_flags(p, who)) return rc;
+    const std::string w = who;
+    if (p->count != 0) return rt_fail(RT_ERR_ARG, w + ": counting renders have no accumulator (count must be 0)");
+    if (p->kernel != RT_KERNEL_LANE) return rt_fail(RT_ERR_ARG, w + ": accumulators run on the lane-resident kernel only (kernel 0)");
+    if (p->flags & RT_FLAG_LIGHT_SPLIT) return rt_fail(RT_ERR_ARG, w + ": the light-split kernel has no accumulator");
+    if (p->flags & RT_FLAG_KERNEL_TIMES) return rt_fail(RT_ERR_ARG, w + ": RT_FLAG_KERNEL_TIMES is a wavefront option; accumulators run on kernel 0");
+    if (p->fast_chunk < 0) return rt_fail(RT_ERR_ARG, w + ": fast_chunk must be >= 0");
     return RT_OK;
 }
 
@@ -1832,8 +1934,9 @@ void accum_release(rt_accum *a) {
 }
 
 // Host-side part of create / load: parameters and shard, no device call.
-int accum_new(rt_scene *s, const rt_params *p, const char *who, rt_accum **out) {
-    if (int rc = accum_check_params(p, who)) return rc;
+// `fast`: a fast accumulator (p->fast_chunk its chunk size, 0 = 2).
+int accum_new(rt_scene *s, const rt_params *p, const char *who, rt_accum **out, bool fast = false) {
+    if (int rc = fast ? accum_check_params_fast(p, who) : accum_check_params(p, who)) return rc;
     if (p->device < 0 || p->device >= kRtMaxDevices) return rt_fail(RT_ERR_ARG, std::string(who) + ": bad device " + std::to_string(p->device));
     Shard sh;
     if (int rc = shard_of(s, p, who, sh)) return rc;
@@ -1846,6 +1949,11 @@ int accum_new(rt_scene *s, const rt_params *p, const char *who, rt_accum **out) 
     a->rows = sh.rows;
     a->n_pixels = sh.n_pixels;
     a->geom = sh.g;
+    if (fast) {   // (what its passes render with: fast units, no order, the chunk size as it is)
+        a->fast_c = p->fast_chunk > 0 ? p->fast_chunk : 2;
+        a->p.flags = RT_FLAG_FAST;
+        a->p.fast_chunk = a->fast_c;
+    }
     *out = a;
     return RT_OK;
 }
@@ -1883,27 +1991,28 @@ int accum_counts_launch(rt_accum *a, int32_t *d_counts, hipStream_t stream) {
     return RT_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rt_accum_create(rt_scene *s, const rt_params *p, rt_accum **out) {
-    if (!s || !p || !out) return rt_fail(RT_ERR_ARG, "rt_accum_create: NULL argument");
+// rt_accum_create and rt_accum_create_fast (`who` names the entry in messages).
+int accum_create(rt_scene *s, const rt_params *p, rt_accum **out, const std::string &who, bool fast) {
+    if (!s || !p || !out) return rt_fail(RT_ERR_ARG, who + ": NULL argument");
     *out = nullptr;
     rt_accum *a = nullptr;
-    if (int rc = accum_new(s, p, "rt_accum_create", &a)) return rc;
+    if (int rc = accum_new(s, p, who.c_str(), &a, fast)) return rc;
     if (!s->dev[a->p.device]) {
         accum_release(a);
-        return rt_fail(RT_ERR_ARG, "rt_accum_create: scene not uploaded to device " + std::to_string(p->device));
+        return rt_fail(RT_ERR_ARG, who + ": scene not uploaded to device " + std::to_string(p->device));
     }
     int rc = accum_alloc(a);
     if (rc == RT_OK && a->n_pixels > 0) {
         DeviceGuard guard(a->p.device);
-        hipLaunchKernelGGL(rt_chain_init_kernel, dim3((unsigned)((a->n_pixels + 255) / 256)), dim3(256), 0, nullptr,
-                           s->dev[a->p.device]->ds, a->geom, a->chain, a->sums);
+        const dim3 blocks((unsigned)((a->n_pixels + 255) / 256));
+        if (fast)
+            hipLaunchKernelGGL(rt_fast_chain_init_kernel, blocks, dim3(256), 0, nullptr, a->n_pixels, a->chain, a->sums);
+        else
+            hipLaunchKernelGGL(rt_chain_init_kernel, blocks, dim3(256), 0, nullptr, s->dev[a->p.device]->ds, a->geom, a->chain,
+                               a->sums);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        if (e != hipSuccess) rc = rt_fail(RT_ERR_DEVICE, std::string("rt_accum_create: ") + hipGetErrorString(e));
+        if (e != hipSuccess) rc = rt_fail(RT_ERR_DEVICE, who + ": " + hipGetErrorString(e));
     }
     if (rc) {
         accum_release(a);
@@ -1912,6 +2021,56 @@ int rt_accum_create(rt_scene *s, const rt_params *p, rt_accum **out) {
     *out = a;
     return RT_OK;
 }
+
+// One launch of a fast accumulator's pass: the items (null: every pixel) raised to `target`, the
+// one furthest behind standing at `from` (its units are the launch's units per item).
+int fast_launch(rt_accum *a, int from, int target, const int *items, long long n_items, hipStream_t stream, rt_stats *st) {
+    rt_params p = a->p;
+    p.spp = target;
+    ChainPass cp{a->chain, target - from};
+    cp.items = items;
+    cp.n_items = n_items;
+    cp.fast_c = a->fast_c;
+    cp.fast_units = rtfu::units_of(from, target, a->fast_c);
+    return launch(a->scene, &p, a->sums, stream, st, &cp);
+}
+
+// A fast accumulator's pass from `from` (the smallest count among its items) to `target`: one
+// launch carries at most kFastMaxChunks units per item, so a longer pass runs as successive
+// complete passes (render + fold) to chunk boundaries on the way; same bits, the records carry
+// everything.  `st` sums the launches' times.
+int fast_pass(rt_accum *a, int from, int target, const int *items, long long n_items, hipStream_t stream, rt_stats *st) {
+    rt_stats total{};
+    const int c = a->fast_c;
+    while (from < target) {
+        int to = target;
+        if (rtfu::units_of(from, target, c) > rtp::kFastMaxChunks)
+            to = (int)(((long long)(from / c) + rtp::kFastMaxChunks) * c);   // the end of the launch's last whole chunk
+        rt_stats one{};
+        if (int rc = fast_launch(a, from, to, items, n_items, stream, st ? &one : nullptr)) return rc;
+        total.render_ms += one.render_ms;
+        total.schedule |= one.schedule;
+        total.pixels = one.pixels;
+        total.devices = one.devices;
+        from = to;   // (items that stood at or past `to` were not touched and stay ahead of it)
+    }
+    if (st) *st = total;
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_accum_create(rt_scene *s, const rt_params *p, rt_accum **out) {
+    return accum_create(s, p, out, "rt_accum_create", false);
+}
+
+int rt_accum_create_fast(rt_scene *s, const rt_params *p, rt_accum **out) {
+    return accum_create(s, p, out, "rt_accum_create_fast", true);
+}
+
+int32_t rt_accum_fast_chunk(const rt_accum *a) { return a ? a->fast_c : 0; }
 
 int rt_accum_add(rt_accum *a, int32_t n_samples, void *stream, rt_stats *st) {
     if (!a) return rt_fail(RT_ERR_ARG, "rt_accum_add: NULL accumulator");
@@ -1923,6 +2082,14 @@ int rt_accum_add(rt_accum *a, int32_t n_samples, void *stream, rt_stats *st) {
                                        std::to_string(a->samples) + " samples; level them first: rt_accum_select with target = " +
                                        std::to_string(a->samples) + " and no threshold, then rt_accum_add_selected");
     a->sel_pending = false;   // (the pass changes the records the list was made from)
+    if (a->fast_c) {
+        a->stream = (hipStream_t)stream;
+        if (int rc = fast_pass(a, a->samples, a->samples + n_samples, nullptr, 0, (hipStream_t)stream, st)) return rc;
+        if (st) st->samples = (uint64_t)a->n_pixels * (uint64_t)n_samples;
+        a->samples += n_samples;
+        a->min_samples = a->samples;
+        return RT_OK;
+    }
     rt_params p = a->p;
     p.spp = a->samples + n_samples;   // the absolute sample this pass ends at
     const ChainPass cp{a->chain, n_samples};
@@ -1976,7 +2143,7 @@ int rt_accum_select(rt_accum *a, const rt_select *sel, void *stream, int64_t *n_
         if (n) HIP_TRY(hipMemcpy(a->sel_mask, sel->mask, (size_t)n, hipMemcpyHostToDevice));
     }
     a->stream = (hipStream_t)stream;
-    SelectOut so{0ull, 0ull, INT32_MAX, 0};
+    SelectOut so{0ull, 0ull, INT32_MAX, 0, INT32_MAX, 0};
     if (n > 0) {
         HIP_TRY(hipMemcpyAsync(a->sel_out, &so, sizeof so, hipMemcpyHostToDevice, a->stream));
         const uint8_t *mask = sel->mask ? a->sel_mask : nullptr;
@@ -2000,6 +2167,7 @@ int rt_accum_select(rt_accum *a, const rt_select *sel, void *stream, int64_t *n_
     a->sel_target = rule.target;
     a->sel_min = so.next_min;
     a->sel_max = so.next_max;
+    a->sel_from = so.from_min;
     a->sel_pending = true;
     if (n_selected) *n_selected = a->sel_n;
     return RT_OK;
@@ -2026,6 +2194,17 @@ int rt_accum_add_selected(rt_accum *a, void *stream, rt_stats *st) {
             std::memset(st, 0, sizeof *st);
             st->devices = 1;
         }
+        return RT_OK;
+    }
+    if (a->fast_c) {   // (sel_from: the listed pixel furthest behind; below the target by the rule)
+        a->stream = (hipStream_t)stream;
+        if (int rc = fast_pass(a, a->sel_from, a->sel_target, a->sel_list, a->sel_n, (hipStream_t)stream, st)) return rc;
+        if (st) {
+            st->pixels = (uint64_t)a->sel_n;
+            st->samples = a->sel_samples;
+        }
+        a->samples = a->sel_max;
+        a->min_samples = a->sel_min;
         return RT_OK;
     }
     rt_params p = a->p;
@@ -2114,6 +2293,11 @@ int rt_accum_state(rt_accum *a, uint32_t *out) {
     std::vector<uint32_t> rec;
     if (int rc = accum_records(a, rec)) return rc;
     for (long long k = 0; k < a->n_pixels; ++k) {
+        if (a->fast_c) {   // (rt_mega.h FastRec: next sample, the open partial's three words)
+            out[4 * k + 0] = rec[8 * k + 1];
+            std::memcpy(out + 4 * k + 1, &rec[8 * k + 5], 12);
+            continue;
+        }
         out[4 * k + 0] = rec[8 * k + 1];
         out[4 * k + 1] = rec[8 * k + 2] & 0x7fffffffu;   // (rt_mega.h rng_word_pack)
         out[4 * k + 2] = rec[8 * k + 2] >> 31;
@@ -2134,6 +2318,11 @@ int rt_accum_save(rt_accum *a, const char *path) {
     h.n_pixels = a->n_pixels;
     h.samples = a->samples;
     h.reserved = accum_uniform(a) ? 0 : 1;   // 1: per-pixel counts, `samples` is the largest
+    if (a->fast_c) {
+        std::memcpy(h.magic, kFastAccumMagic, 8);
+        h.version = kFastAccumVersion;
+        h.pad[0] = (uint32_t)a->fast_c;
+    }
     std::FILE *f = std::fopen(path, "wb");
     if (!f) return rt_fail(RT_ERR_IO, std::string("rt_accum_save: cannot write ") + path);
     bool ok = std::fwrite(&h, sizeof h, 1, f) == 1;
@@ -2153,10 +2342,15 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
     AccumHeader h;
     std::vector<uint32_t> rec;
     int rc = RT_OK;
+    bool fast = false;   // (the magic says which kind the file holds)
     if (std::fread(&h, sizeof h, 1, f) != 1) rc = rt_fail(RT_ERR_FORMAT, who + ": shorter than its header");
-    else if (std::memcmp(h.magic, kAccumMagic, 8) != 0) rc = rt_fail(RT_ERR_FORMAT, who + ": not an accumulator file (magic)");
-    else if (h.version != kAccumVersion)
-        rc = rt_fail(RT_ERR_FORMAT, who + ": version " + std::to_string(h.version) + ", this library reads " + std::to_string(kAccumVersion));
+    else if (!(fast = std::memcmp(h.magic, kFastAccumMagic, 8) == 0) && std::memcmp(h.magic, kAccumMagic, 8) != 0)
+        rc = rt_fail(RT_ERR_FORMAT, who + ": not an accumulator file (magic)");
+    else if (h.version != (fast ? kFastAccumVersion : kAccumVersion))
+        rc = rt_fail(RT_ERR_FORMAT, who + ": version " + std::to_string(h.version) + ", this library reads " +
+                                        std::to_string(fast ? kFastAccumVersion : kAccumVersion));
+    else if (fast && (h.pad[0] < 1u || h.pad[0] > (uint32_t)INT32_MAX))
+        rc = rt_fail(RT_ERR_FORMAT, who + ": bad chunk size " + std::to_string(h.pad[0]));
     else if (h.n_pixels < 0 || h.n_pixels > INT32_MAX || h.samples < 0 || h.samples >= (1 << 20))
         rc = rt_fail(RT_ERR_FORMAT, who + ": bad pixel or sample count");
     else if (h.reserved != 0 && h.reserved != 1)
@@ -2195,7 +2389,8 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
     p.row_block = h.row_block;
     p.device = device;
     rt_accum *a = nullptr;
-    if (int rc2 = accum_new(s, &p, "rt_accum_load", &a)) return rc2;
+    if (fast) p.fast_chunk = (int)h.pad[0];
+    if (int rc2 = accum_new(s, &p, "rt_accum_load", &a, fast)) return rc2;
     if (a->n_pixels != h.n_pixels) {
         const long long have = a->n_pixels;
         accum_release(a);
@@ -2210,6 +2405,10 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
             accum_release(a);
             return rt_fail(RT_ERR_FORMAT, who + ": record " + std::to_string(k) + " does not belong to this file");
         }
+        if (fast && !rtfu::open_words_fit(nx, a->fast_c, &rec[8 * k + 5])) {
+            accum_release(a);
+            return rt_fail(RT_ERR_FORMAT, who + ": record " + std::to_string(k) + " holds an open partial at a chunk boundary");
+        }
         lo = std::min(lo, nx);
         hi = std::max(hi, nx);
     }
@@ -2218,7 +2417,17 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
     if (rc == RT_OK && a->n_pixels > 0) {
         DeviceGuard guard(device);
         std::vector<float> sums((size_t)h.n_pixels * 3);
-        for (long long k = 0; k < h.n_pixels; ++k) std::memcpy(&sums[3 * k], &rec[8 * k + 4], 12);
+        for (long long k = 0; k < h.n_pixels; ++k) {
+            if (fast) {   // the reported sum of the record (rt_fast_units.h), as the fold kernel writes it
+                rtfu::Rec r;
+                r.next = (int)rec[8 * k + 1];
+                std::memcpy(r.total, &rec[8 * k + 2], 12);
+                std::memcpy(r.open, &rec[8 * k + 5], 12);
+                rtfu::reported(r, a->fast_c, &sums[3 * k]);
+            } else {
+                std::memcpy(&sums[3 * k], &rec[8 * k + 4], 12);
+            }
+        }
         hipError_t e = hipMemcpy(a->chain, rec.data(), rec.size() * 4, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(a->sums, sums.data(), sums.size() * 4, hipMemcpyHostToDevice);
         if (e != hipSuccess) rc = rt_fail(RT_ERR_DEVICE, std::string("rt_accum_load: ") + hipGetErrorString(e));

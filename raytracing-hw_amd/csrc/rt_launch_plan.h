@@ -135,6 +135,12 @@ struct PlanIn {
     // `spp` from wherever its record stands; 0 = a full pass.  The list is the order: no
     // pre-pass runs and RT_FLAG_HEAVY_ORDER is ignored.
     long long subset_items = 0;
+    // A pass of a fast accumulator (rt_accum_create_fast; with pass_spp > 0): fast_chunk is the
+    // accumulator's chunk size, used as it is, and fast_units the work units every item of the
+    // launch gets (the chunks the pass of the item furthest behind overlaps: rt_fast_units.h
+    // units_of; the host keeps it at or below kFastMaxChunks by splitting the pass).
+    bool fast_accum = false;
+    int fast_units = 0;
 };
 
 // The two order flags exclude each other (shared with the accumulator's parameter check).
@@ -154,7 +160,8 @@ inline Refusal plan_check(const PlanIn &in) {
 }
 
 // The rt_mega_kernel instantiation (rt_device.hip mega_kernel_of).  `chain`: a pass of an
-// accumulator, on the plain or the runahead kernel only (rt_accum_* refuse the other modes).
+// accumulator, on the plain or the runahead kernel (parity), or with `fast` the pass of a fast
+// accumulator (PlanIn.fast_accum); rt_accum_* refuse the other modes.
 struct Variant {
     bool count = false, fast = false, lsplit = false, spec = false, chain = false;
 };
@@ -192,17 +199,29 @@ inline Schedule plan_schedule(const PlanIn &in) {
     s.lane = true;
     Variant &v = s.v;
     v.count = in.count != 0;
-    v.fast = (in.flags & RT_FLAG_FAST) != 0;
+    const bool fast_pass = in.fast_accum && in.pass_spp > 0;
+    v.fast = fast_pass || (in.flags & RT_FLAG_FAST) != 0;
     v.lsplit = !v.fast && (in.flags & RT_FLAG_LIGHT_SPLIT) != 0;
     v.chain = in.pass_spp > 0;
     // fast mode (RT_FLAG_FAST): work units of `cs` samples, Philox seed per sample, at most
     // kFastMaxChunks units per pixel (partials: pixels x chunks x 12 B)
-    if (v.fast) {
+    if (fast_pass) {
+        // (the accumulator's chunk size is fixed for its life: a boundary that moved with the
+        // pass would change the sum; the FAST + CHAIN kernel, never ordered, no runahead)
+        if (in.fast_chunk < 1 || in.fast_units < 1 || in.fast_units > kFastMaxChunks) {
+            s.refused = {RT_ERR_ARG, "rt_accum_add: a fast pass needs a chunk size >= 1 and 1 .. " +
+                                         std::to_string(kFastMaxChunks) + " units per item"};
+            s.lane = false;
+            return s;
+        }
+        s.cs = in.fast_chunk;
+        s.chunks = in.fast_units;
+    } else if (v.fast) {
         s.cs = std::min(in.spp, std::max(in.fast_chunk > 0 ? in.fast_chunk : 2, (in.spp + kFastMaxChunks - 1) / kFastMaxChunks));
         s.chunks = (in.spp + s.cs - 1) / s.cs;
     }
     const bool subset = v.chain && in.subset_items > 0;
-    s.n_items = subset ? in.subset_items : in.n_pixels * s.chunks;
+    s.n_items = subset ? in.subset_items * (fast_pass ? s.chunks : 1) : in.n_pixels * s.chunks;
     // Speculative sample runahead (rt_mega.h) where the frame is mostly tail: a shard of at most
     // kSpecPixelsPerLane pixels per resident lane (the 8-way split of the headline: 342 -> 304
     // ms in round 2; at 4-way, 2 pixels per lane, 359 -> 348 ms in round 3).  A larger shard

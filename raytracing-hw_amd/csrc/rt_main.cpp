@@ -22,6 +22,11 @@
 //                       and writes the frame with every pixel divided by its own count.
 //   RT_COUNTS_OUT=path  (with RT_ADAPT) the sample-count map as a binary 16-bit PGM: "P5", maxval
 //                       65535, big-endian, counts clamped to it.
+// Fast mode (RT_FLAG_FAST: per-sample Philox streams, not the reference's RNG convention):
+//   RT_FAST=c           chunks of c samples (c >= 1).  Alone: the one-shot frame in fast mode with
+//                       fast_chunk = c.  With RT_PASS_SPP and / or RT_ADAPT: the passes run on fast
+//                       accumulators (rt_accum_create_fast) with chunk size c; a checkpoint resumes
+//                       only into the kind and chunk size that wrote it.
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
@@ -42,7 +47,7 @@ static void check(int rc) {
 // `adapt` (RT_ADAPT): its threshold; the passes are then those of adaptive rendering (above).
 static void render_passes(rt_scene *scene, int width, int height, int samples, int n_gpus, int pass_spp,
                           const char *ckpt, const std::string &output, const float *adapt = nullptr,
-                          const char *counts_out = nullptr) {
+                          const char *counts_out = nullptr, int fast_chunk = 0) {
     const int n = n_gpus > 0 ? n_gpus : rt_device_count();
     if (n < 1) throw std::runtime_error("no HIP device");
     if (samples < 1) throw std::runtime_error("samples per pixel must be >= 1");
@@ -62,6 +67,12 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
     for (int r = 0; r < n; ++r) {
         if (resume) {
             check(rt_accum_load(scene, r, file_of(r).c_str(), &acc[(size_t)r]));
+            const int have = rt_accum_fast_chunk(acc[(size_t)r]);
+            if (have != fast_chunk)
+                throw std::runtime_error("checkpoint " + file_of(r) + " holds " +
+                                         (have ? "a fast accumulator with chunks of " + std::to_string(have) : std::string("a parity accumulator")) +
+                                         ", the run asks for " +
+                                         (fast_chunk ? "RT_FAST=" + std::to_string(fast_chunk) : std::string("parity passes (RT_FAST unset)")));
         } else {
             check(rt_scene_upload(scene, r));
             rt_params p{};
@@ -69,7 +80,8 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
             p.world = n;
             p.row_block = 8;
             p.device = r;
-            check(rt_accum_create(scene, &p, &acc[(size_t)r]));
+            p.fast_chunk = fast_chunk;
+            check(fast_chunk ? rt_accum_create_fast(scene, &p, &acc[(size_t)r]) : rt_accum_create(scene, &p, &acc[(size_t)r]));
         }
     }
     int done = rt_accum_samples(acc[0]);
@@ -192,12 +204,16 @@ int main(int argc, char *argv[]) {
     const char *adapt_env = std::getenv("RT_ADAPT"), *counts_out = std::getenv("RT_COUNTS_OUT");
     const bool adaptive = adapt_env && *adapt_env;
     const float adapt = adaptive ? std::strtof(adapt_env, nullptr) : 0.f;
+    const char *fast_env = std::getenv("RT_FAST");
+    const int fast_chunk = fast_env && *fast_env ? std::atoi(fast_env) : 0;
+    if (fast_env && *fast_env && fast_chunk < 1) throw std::runtime_error("RT_FAST must be >= 1");
     if ((pass_env && *pass_env) || (ckpt && *ckpt) || adaptive) {
         const int pass_spp = pass_env && *pass_env ? std::atoi(pass_env) : 0;
         if (pass_env && *pass_env && pass_spp < 1) throw std::runtime_error("RT_PASS_SPP must be >= 1");
         try {
             render_passes(scene, width, height, samples, n_gpus, pass_spp, ckpt && *ckpt ? ckpt : nullptr, output,
-                          adaptive ? &adapt : nullptr, adaptive && counts_out && *counts_out ? counts_out : nullptr);
+                          adaptive ? &adapt : nullptr, adaptive && counts_out && *counts_out ? counts_out : nullptr,
+                          fast_chunk);
         } catch (const std::exception &e) {   // (a checkpoint that does not fit, a failed pass: the message, status 1)
             std::cerr << "rt_solution: " << e.what() << std::endl;
             rt_scene_free(scene);
@@ -212,6 +228,10 @@ int main(int argc, char *argv[]) {
     rt_params p{};
     p.spp = samples;
     p.row_block = 8;
+    if (fast_chunk) {
+        p.flags = RT_FLAG_FAST;
+        p.fast_chunk = fast_chunk;
+    }
     rt_stats st{};
     // every shard finished to 8 bits on its GPU and gathered device-to-device onto GPU 0
     std::vector<uint8_t> rgb((size_t)width * height * 3);

@@ -16,6 +16,7 @@
 // RNG, pixel sum, sample counter and depth budget live in registers; the vertex records go
 // to memory (LaneRec, indexed by lane slot).  Same per-pixel arithmetic, so bit-identical output.
 #pragma once
+#include "rt_fast_units.h"
 #include "rt_wavefront.h"
 #if !defined(__HIPCC__)
 #include <algorithm>   // (host emulation of wave_order)
@@ -334,6 +335,69 @@ __device__ __forceinline__ void mega_assign_chain(ML &L, const DevScene &sc, con
     lane_rng_set(L, q.x);
     mega_sample<COUNT>(L, sc, g, root, cnt);
 }
+// ---------------------------------------------------------------- fast accumulator
+// rt_accum_create_fast (include/rt_hw.h, rt_fast_units.h): the chain buffer's 32-byte record of
+// a fast accumulator holds (pixel, next sample, total x, y | total z, open x, y, z): no RNG
+// state, sample s of a pixel draws from its own Philox stream.  Word 1 is the next sample as in
+// a parity record, so the selection, mark and counts kernels read both kinds.  The render
+// kernel only reads records; rt_fast_fold_chain_kernel (rt_device.hip) writes them.
+struct FastRec {
+    uint32_t pix;
+    rtfu::Rec r;
+};
+__device__ __forceinline__ FastRec fast_rec(const uint4 *chain, long long p) {
+    const uint4 a = chain[2 * p], b = chain[2 * p + 1];
+    FastRec q;
+    q.pix = a.x;
+    q.r.next = (int)a.y;
+    q.r.total[0] = __uint_as_float(a.z);
+    q.r.total[1] = __uint_as_float(a.w);
+    q.r.total[2] = __uint_as_float(b.x);
+    q.r.open[0] = __uint_as_float(b.y);
+    q.r.open[1] = __uint_as_float(b.z);
+    q.r.open[2] = __uint_as_float(b.w);
+    return q;
+}
+__device__ __forceinline__ void fast_rec_store(uint4 *chain, long long p, const rtfu::Rec &r) {
+    chain[2 * p] = make_uint4((uint32_t)p, (uint32_t)r.next, __float_as_uint(r.total[0]), __float_as_uint(r.total[1]));
+    chain[2 * p + 1] = make_uint4(__float_as_uint(r.total[2]), __float_as_uint(r.open[0]), __float_as_uint(r.open[1]),
+                                  __float_as_uint(r.open[2]));
+}
+// A pass of a fast accumulator: queue item q = k * n_list + i is unit k of the list's item i
+// (unit-major, like mega_assign_fast: neighbouring lanes take neighbouring pixels), the pixel
+// `order ? order[i] : i` raised from its record's next sample to `spp`.  The unit's samples come
+// from rt_fast_units.h; one that starts inside a chunk starts from the record's open partial.
+// Returns false, the lane left without a pixel, for a unit past the pixel's own (the launch has
+// the units of the pixel furthest behind): starting a sample there would never reach L.send.
+template <bool COUNT, class ML>
+__device__ __forceinline__ bool mega_assign_fast_chain(ML &L, const DevScene &sc, const ShardGeom &g, long long q,
+                                                       long long n_list, const int *order, int cs, int spp,
+                                                       const NodeRec &root, Counters &cnt, const uint4 *chain) {
+    const int k = (int)(q / n_list);
+    const long long i = q - (long long)k * n_list;
+    const int p = order ? order[i] : (int)i;
+    // check 17 (index-checked build): the item names a pixel of the shard, and a sample starts
+    // only on s0 < s1, which holds exactly for the pixel's own units (liveness, as
+    // mega_assign_chain's check 16)
+    RT_CHECK(p >= 0 && p < g.n_pixels, 17, p, return false);
+    const FastRec rec = fast_rec(chain, p);
+    const rtfu::Range u = rtfu::unit_range(rec.r.next, spp, cs, k);
+    RT_CHECK((u.s0 < u.s1) == (k < rtfu::units_of(rec.r.next, spp, cs)), 17, q, return false);
+    if (u.s0 >= u.s1) return false;
+    L.pix = p;
+    L.dst = q;
+    lane_ctr_set(L, LaneCtr{u.s0, 0, 0});
+    L.send = u.s1;
+    const bool cont = rtfu::unit_continues(rec.r.next, cs, k);
+    lane_sum_set(L, cont ? V3{rec.r.open[0], rec.r.open[1], rec.r.open[2]} : V3{0.f, 0.f, 0.f});
+    L.work0 = cnt.aabb + cnt.tri + cnt.laabb + cnt.ltri;
+    int px, py;
+    shard_xy(g, p, px, py);
+    L.gpix = (uint32_t)(py * sc.width + px);
+    mega_sample<COUNT, true>(L, sc, g, root, cnt);
+    return true;
+}
+
 // Shade the lane's closest hit (one vertex of scene.cpp:85-154); bounce, or end the path:
 // fold, accumulate, next sample or pixel done.
 // Set when a lane of the wave added its sample itself (spec_job_end): its pixel may take
