@@ -16,6 +16,8 @@
  *   rt_tonemap_u8        <- Scene::render frame finish  src/core/scene.cpp:54-64
  *   rt_tonemap_u8_device <- the same finish on the GPU   src/core/scene.cpp:54-64
  *   rt_write_ppm         <- Canvas::write_to            src/render/canvas.h:76-89
+ *   rt_gbuffer, rt_denoise*  (no reference counterpart: the first hit's features and a filter
+ *                           for low-sample previews in front of the finish)
  *   rt_last_error        <- the reference's std::runtime_error messages (23 throw sites);
  *                           the host wrappers re-throw them (drop-in failure behaviour).
  *
@@ -396,6 +398,116 @@ int rt_tonemap_u8_counts_device(const float *d_sum, const int32_t *d_counts, int
                                 void *stream);
 /* "P6\n{W} {H}\n255\n" + raw RGB (canvas.h:76-89) */
 int rt_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t height);
+
+/* --- first-hit feature buffer and frame denoiser (additive in ABI 6) ------------------- */
+/* The first-hit feature buffer (G-buffer).  Every owned pixel gets one record from the ray through
+ * its centre, Camera::cast_in_pixel with zero offsets (camera.cpp:49-62): no random number is
+ * drawn, so the record depends on neither spp nor an accumulator.  A record is RT_GBUFFER_WORDS
+ * 32-bit words (64 B), four groups of four:
+ *   words  0..3   shading normal N.xyz, hit distance t
+ *   words  4..7   base colour (albedo).xyz, triangle id (int32 bits)
+ *   words  8..11  emission.xyz, mesh id (int32 bits)
+ *   words 12..15  hit position P = o + d * t (each component one multiply, one add, f32), 0
+ * A hit is the scene's closest hit with t < max_distance (the sample loop's own test); a miss is
+ * all-zero words with both ids -1.  N is Primitive::get_shading_normal (primitive.cpp:86-105:
+ * interpolated vertex normals, the normal map, negated where the ray is inside), before the
+ * sample loop's fall-back to the geometric normal; albedo is the mesh's base colour factor times
+ * the sRGB base-colour texture sample where the mesh has one; emission is Primitive::get_emission
+ * (primitive.cpp:121-129).  csrc/rt_gbuffer.h is the text, shared by the device kernel and the CPU
+ * test; the render kernels are not touched by it.
+ *
+ * Both entries use rank, world, row_block and device of params (the other fields are ignored) and
+ * write the records in rt_render's shard layout: record k * W + i for column i of the k-th owned
+ * row.  rt_gbuffer writes host memory and uploads the scene to the device if need be;
+ * rt_gbuffer_device writes device memory on `stream`, asynchronously, and needs the scene on the
+ * device (rt_scene_upload).  A NULL argument, a bad partition and (rt_gbuffer_device) a scene that
+ * is not on the device are RT_ERR_ARG; no such device or a HIP error RT_ERR_DEVICE.
+ * Both only read the device copy of the scene and use none of its workspace, so they do not fall
+ * under "one render per (scene, device) in flight": they may run beside a render or a pass of the
+ * same scene on the same device (rt_gbuffer works on the default stream and waits for its copy). */
+#define RT_GBUFFER_WORDS 16
+int rt_gbuffer(rt_scene *scene, const rt_params *params, float *out);
+int rt_gbuffer_device(rt_scene *scene, const rt_params *params, float *d_out, void *stream);
+
+/* The denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a WHOLE frame
+ * on one device, guided by the frame's G-buffer (five levels reach 62 pixels, so it cannot run per
+ * row-block shard).  A pure function of its inputs.  csrc/rt_denoise.h is its text, shared by the
+ * device kernels and the host function.  Only f32 +, -, *, /, comparisons and selects in the order
+ * written below; the falloffs are rational, so the host function, the device kernels and a
+ * restatement in any IEEE f32 arithmetic without contraction give the same bits.
+ *
+ * Parameters.  A NULL params is all defaults.  iterations: 0 is a value (no filtering), a negative
+ * one takes the default 5, more than 6 is RT_ERR_ARG.  sigma_color, sigma_plane: <= 0 takes the
+ * default (2 and 0.02); NaN or infinite is RT_ERR_ARG.  normal_power_log2: <= 0 takes the default
+ * 6, more than 16 is RT_ERR_ARG.  The 5 levels and the exponent 2^6 are the filter's usual
+ * choices; the two sigmas are picked, not tuned: no measurement stands behind them.
+ *
+ * Inputs: sums (W * H * 3 floats, row-major), then either counts (W * H sample counts) or, with
+ * counts NULL, one spp >= 1 for every pixel; the G-buffer (W * H records).  Output: the W * H * 3
+ * float MEAN frame; rt_tonemap_u8 with spp = 1 turns it into bytes (1.f / 1.f is exact).
+ *
+ * Prepare, per pixel with n samples (a negative count is 0), sums S, record (N, t, albedo, E, P):
+ *   m  = S * (n > 0 ? 1.f / (float)n : 0.f)                       per channel, as the finish does
+ *   a' = albedo > 1e-3f ? albedo : 1e-3f                          per channel
+ *   L  = (m - E) / a'                                             per channel
+ *   kind: pass   a miss (triangle id < 0), or a hit with n > 0 whose m or L has a non-finite channel
+ *         fill   a hit with n <= 0
+ *         valid  every other hit; only a valid pixel keeps its L (the others hold 0, 0, 0)
+ * One level k = 0 .. iterations - 1, stride s = 2^k, reading one buffer of (L, kind) and writing
+ * the other (all pixels read level k's input).  For a centre p of kind pass: copied.  Otherwise,
+ * over the 25 taps q = p + (dx * s, dy * s), dy = -2 .. 2 outer, dx = -2 .. 2 inner, skipping a tap
+ * outside the frame or not of kind valid:
+ *   h  = b(dx) * b(dy),  b(0) = 3/8, b(+-1) = 1/4, b(+-2) = 1/16
+ *   nd = (Np.x * Nq.x + Np.y * Nq.y) + Np.z * Nq.z;  nd = nd > 0 ? nd : 0;  nd = nd * nd,
+ *        normal_power_log2 times
+ *   e  = Pq - Pp;  pd = (Np.x * e.x + Np.y * e.y) + Np.z * e.z;  pr = pd / (sigma_plane * tp);
+ *   wp = 1 / (1 + pr * pr)
+ *   wc = 1 for a centre of kind fill, else with d = Lq - Lp:
+ *        1 / (1 + ((d.x * d.x + d.y * d.y) + d.z * d.z) / c_k),  c_k = (sigma_color * 2^-k)^2
+ *   w  = ((h * nd) * wp) * wc;  a tap whose w is not > 0 (zero or NaN) is skipped
+ *   sw = sw + w;  sL = sL + w * Lq                                per channel, all from +0
+ * and the centre becomes (sL / sw, valid) when sw > 0 and the three quotients are finite (so a
+ * filled pixel contributes from the next level on), (0, 0, 0, its kind) when sw is not > 0, and
+ * stays as it was when a quotient overflowed.
+ * Resolve: a pixel of kind pass gives its own m; every other gives L' * a' + E per channel (a fill
+ * pixel no level could fill has L' = 0).  With iterations = 0 every pixel gives m, bit for bit.
+ *
+ * So: a hit without samples is filled from its neighbours; a miss keeps its mean; a hit with a NaN
+ * or infinite mean keeps it, so the finish treats it as before, and it never reaches another
+ * pixel; across perpendicular faces nd is exactly 0.
+ *
+ * rt_denoise runs on the host.  rt_denoise_device runs on the current HIP device, asynchronously
+ * on `stream`, every pointer but params a device pointer; its bits are rt_denoise's.  Its scratch
+ * (64 B per pixel) is kept per device from the first call on and only grows, so one
+ * rt_denoise_device per device may be in flight.  NULL sums, G-buffer or output, a width or height
+ * < 1, counts NULL with spp < 1 and the parameter refusals above are RT_ERR_ARG; a frame of 2^31
+ * pixels or more RT_ERR_LIMIT; a HIP error or no device RT_ERR_DEVICE. */
+typedef struct {
+    int32_t iterations;          /* 0..6; < 0: 5                      */
+    float sigma_color;           /* <= 0: 2 (demodulated radiance, at level 0) */
+    float sigma_plane;           /* <= 0: 0.02 (fraction of the centre's hit distance) */
+    int32_t normal_power_log2;   /* 1..16; <= 0: 6                    */
+} rt_denoise_params;
+int rt_denoise(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
+               const float *gbuffer, const rt_denoise_params *params, float *out_mean);
+int rt_denoise_device(const float *d_sums, const int32_t *d_counts, int32_t spp, int32_t width, int32_t height,
+                      const float *d_gbuffer, const rt_denoise_params *params, float *d_out_mean, void *stream);
+/* The same filter and the 8-bit finish for a caller that holds host arrays and no HIP (the CLI's
+ * several-GPU frames): sums, counts (or NULL and spp) and G-buffer are copied to `device`, denoised
+ * there (rt_denoise_device), finished at spp = 1 (rt_tonemap_u8_device) and the W * H * 3 bytes
+ * copied back; it waits.  The bytes are rt_tonemap_u8(rt_denoise(...), spp = 1)'s.  Refusals as
+ * rt_denoise_device's; a device that does not exist RT_ERR_DEVICE. */
+int rt_denoise_frame_u8(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
+                        const float *gbuffer, const rt_denoise_params *params, int32_t device, uint8_t *out_rgb);
+/* rt_accum_frame_u8 with the denoiser in front of the finish, for an accumulator that owns the
+ * whole frame (world = 1), parity or fast, with uniform or per-pixel counts: the reported sums are
+ * denoised with the accumulator's counts and its G-buffer (rendered on first use, kept until
+ * rt_accum_free, like the filter's scratch), and the mean frame is finished at spp = 1.  Nothing
+ * is written into the accumulator: sums, records, marks and a pending selection are untouched.
+ * Falls under "one render per (scene, device) in flight".  With world > 1 RT_ERR_ARG (gather the
+ * shards' sums and G-buffers and use the frame-level entry, rt_denoise_device); before the first
+ * sample RT_ERR_ARG, like rt_accum_frame_u8. */
+int rt_accum_frame_u8_denoised(rt_accum *accum, const rt_denoise_params *params, uint8_t *out_rgb);
 
 /* --- misc --------------------------------------------------------------------------- */
 const char *rt_last_error(void);

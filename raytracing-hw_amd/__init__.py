@@ -69,6 +69,19 @@ class RtSelect(ctypes.Structure):
                 ("y1", ctypes.c_int32), ("mask", _c_b), ("threshold", ctypes.c_float)]
 
 
+class RtDenoiseParams(ctypes.Structure):
+    """include/rt_hw.h rt_denoise_params; iterations < 0 and the other fields <= 0 take the defaults."""
+    _fields_ = [("iterations", ctypes.c_int32), ("sigma_color", ctypes.c_float), ("sigma_plane", ctypes.c_float),
+                ("normal_power_log2", ctypes.c_int32)]
+
+
+GBUFFER_WORDS = 16       # RT_GBUFFER_WORDS: 32-bit words of a first-hit record
+
+
+def denoise_params(iterations=-1, sigma_color=0.0, sigma_plane=0.0, normal_power_log2=0):
+    return RtDenoiseParams(int(iterations), float(sigma_color), float(sigma_plane), int(normal_power_log2))
+
+
 class RtStats(ctypes.Structure):
     _fields_ = [("pixels", ctypes.c_uint64), ("samples", ctypes.c_uint64), ("rays", ctypes.c_uint64),
                 ("aabb_tests", ctypes.c_uint64), ("tri_tests", ctypes.c_uint64), ("light_queries", ctypes.c_uint64),
@@ -135,6 +148,16 @@ ABI = {
     # fast-mode accumulators: progressive and adaptive passes on Philox units
     "rt_accum_create_fast": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtParams), ctypes.POINTER(ctypes.c_void_p)]),
     "rt_accum_fast_chunk": (ctypes.c_int32, [ctypes.c_void_p]),
+    # first-hit feature buffer and frame denoiser
+    "rt_gbuffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtParams), _c_f]),
+    "rt_gbuffer_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtParams), ctypes.c_void_p, ctypes.c_void_p]),
+    "rt_denoise": (ctypes.c_int, [_c_f, _c_i, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_f,
+                                  ctypes.POINTER(RtDenoiseParams), _c_f]),
+    "rt_denoise_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.c_void_p, ctypes.POINTER(RtDenoiseParams), ctypes.c_void_p, ctypes.c_void_p]),
+    "rt_denoise_frame_u8": (ctypes.c_int, [_c_f, _c_i, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_f,
+                                           ctypes.POINTER(RtDenoiseParams), ctypes.c_int32, _c_b]),
+    "rt_accum_frame_u8_denoised": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtDenoiseParams), _c_b]),
 }
 
 _lib_handle = None
@@ -358,6 +381,22 @@ class Scene:
         _after_render()
         return st.as_dict() if st else None
 
+    def gbuffer(self, rank=0, world=1, row_block=8, device=0):
+        """rt_gbuffer: the shard's first-hit records from the pixel-centre rays, as a dict of
+        (rows, W[, 3]) arrays: normal, depth (hit distance), albedo, emission, position (float32),
+        prim and mesh (int32, -1 on a miss).  See gbuffer_unpack / gbuffer_pack for the records."""
+        rows = shard_rows(self.height, rank, world, row_block)
+        rec = np.zeros((len(rows), self.width, GBUFFER_WORDS), np.float32)
+        p = self._params(0, rank, world, row_block, False, KERNEL_LANE, device=device)
+        _check(lib().rt_gbuffer(self._h, ctypes.byref(p), rec.ctypes.data_as(_c_f)))
+        return gbuffer_unpack(rec)
+
+    def gbuffer_device(self, d_out_ptr, stream_ptr=None, rank=0, world=1, row_block=8, device=0):
+        """rt_gbuffer_device: the same records into device memory (pixels x 16 floats) on a HIP
+        stream; upload(device) first."""
+        p = self._params(0, rank, world, row_block, False, KERNEL_LANE, device=device)
+        _check(lib().rt_gbuffer_device(self._h, ctypes.byref(p), ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(stream_ptr or 0)))
+
     def accumulator(self, rank=0, world=1, row_block=8, device=0, natural_order=False, heavy_order=False,
                     runahead=True, fast=False, fast_chunk=0):
         """Progressive rendering (rt_accum_create): the shard's per-pixel chain state on
@@ -456,10 +495,16 @@ class Accumulator:
     def device_sums_ptr(self):
         return int(lib().rt_accum_device_sums(self._h) or 0)
 
-    def frame(self):
-        """(rows, W, 3) uint8: the shard finished at spp = samples (on the device)."""
+    def frame(self, denoise=None):
+        """(rows, W, 3) uint8: the shard finished at spp = samples (on the device).  denoise: True
+        (the default parameters) or a dict of denoise_params' arguments runs the frame denoiser in
+        front of the finish (rt_accum_frame_u8_denoised; whole-frame accumulators only)."""
         out = np.zeros((len(self.rows), self._scene.width, 3), np.uint8)
-        _check(lib().rt_accum_frame_u8(self._h, out.ctypes.data_as(_c_b)))
+        if denoise is None or denoise is False:
+            _check(lib().rt_accum_frame_u8(self._h, out.ctypes.data_as(_c_b)))
+        else:
+            dp = denoise_params(**(denoise if isinstance(denoise, dict) else {}))
+            _check(lib().rt_accum_frame_u8_denoised(self._h, ctypes.byref(dp), out.ctypes.data_as(_c_b)))
         return out
 
     def state(self):
@@ -589,6 +634,80 @@ def tonemap_counts(sums, counts):
     rgb = np.zeros((h, w, 3), np.uint8)
     _check(lib().rt_tonemap_u8_counts(sums.ctypes.data_as(_c_f), counts.ctypes.data_as(_c_i), w, h, rgb.ctypes.data_as(_c_b)))
     return rgb
+
+
+def gbuffer_unpack(records):
+    """First-hit records (..., 16) float32 as the dict Scene.gbuffer returns ("records": the input)."""
+    rec = np.ascontiguousarray(records, np.float32)
+    ids = rec.view(np.int32)
+    return {"normal": rec[..., 0:3].copy(), "depth": rec[..., 3].copy(), "albedo": rec[..., 4:7].copy(),
+            "prim": ids[..., 7].copy(), "emission": rec[..., 8:11].copy(), "mesh": ids[..., 11].copy(),
+            "position": rec[..., 12:15].copy(), "records": rec}
+
+
+def gbuffer_pack(g):
+    """The (H, W, 16) float32 records of a Scene.gbuffer dict (or of an array of records)."""
+    if not isinstance(g, dict):
+        return np.ascontiguousarray(g, np.float32)
+    if "records" in g:
+        return np.ascontiguousarray(g["records"], np.float32)
+    n = np.asarray(g["normal"], np.float32)
+    rec = np.zeros(n.shape[:-1] + (GBUFFER_WORDS,), np.float32)
+    rec[..., 0:3], rec[..., 3] = n, g["depth"]
+    rec[..., 4:7], rec[..., 8:11], rec[..., 12:15] = g["albedo"], g["emission"], g["position"]
+    rec.view(np.int32)[..., 7] = g["prim"]
+    rec.view(np.int32)[..., 11] = g["mesh"]
+    return rec
+
+
+def denoise(sums, counts_or_spp, gbuffer, **params):
+    """rt_denoise (the host function): the (H, W, 3) float32 mean frame of the whole frame's sums,
+    filtered by the edge-avoiding a-trous filter its G-buffer guides.  counts_or_spp: an (H, W)
+    array of per-pixel sample counts, or one spp.  params: denoise_params' arguments."""
+    sums, counts, spp, rec = _denoise_inputs(sums, counts_or_spp, gbuffer)
+    h, w = sums.shape[0], sums.shape[1]
+    out = np.zeros((h, w, 3), np.float32)
+    dp = denoise_params(**params)
+    _check(lib().rt_denoise(sums.ctypes.data_as(_c_f), counts.ctypes.data_as(_c_i) if counts is not None else None, spp, w, h,
+                            rec.ctypes.data_as(_c_f), ctypes.byref(dp), out.ctypes.data_as(_c_f)))
+    return out
+
+
+def _denoise_inputs(sums, counts_or_spp, gbuffer):
+    sums = np.ascontiguousarray(sums, np.float32)
+    h, w = sums.shape[0], sums.shape[1]
+    rec = gbuffer_pack(gbuffer)
+    if rec.size != h * w * GBUFFER_WORDS:
+        raise ValueError("gbuffer must have one record per pixel")
+    counts, spp = None, 0
+    if np.ndim(counts_or_spp) == 0:
+        spp = int(counts_or_spp)
+    else:
+        counts = np.ascontiguousarray(counts_or_spp, np.int32)
+        if counts.size != h * w:
+            raise ValueError("counts must have one entry per pixel")
+    return sums, counts, spp, rec
+
+
+def denoise_frame_u8(sums, counts_or_spp, gbuffer, device=0, **params):
+    """rt_denoise_frame_u8: host arrays in, the denoised frame's (H, W, 3) bytes out, filtered and
+    finished on `device`."""
+    sums, counts, spp, rec = _denoise_inputs(sums, counts_or_spp, gbuffer)
+    h, w = sums.shape[0], sums.shape[1]
+    rgb = np.zeros((h, w, 3), np.uint8)
+    dp = denoise_params(**params)
+    _check(lib().rt_denoise_frame_u8(sums.ctypes.data_as(_c_f), counts.ctypes.data_as(_c_i) if counts is not None else None, spp,
+                                     w, h, rec.ctypes.data_as(_c_f), ctypes.byref(dp), device, rgb.ctypes.data_as(_c_b)))
+    return rgb
+
+
+def denoise_device(d_sums_ptr, d_counts_ptr, spp, width, height, d_gbuffer_ptr, d_out_ptr, stream_ptr=None, **params):
+    """rt_denoise_device: the same filter on the current HIP device (device pointers, e.g. torch
+    tensors; d_counts_ptr 0 / None: one spp), asynchronous on the stream."""
+    dp = denoise_params(**params)
+    _check(lib().rt_denoise_device(ctypes.c_void_p(d_sums_ptr), ctypes.c_void_p(d_counts_ptr or 0), int(spp), width, height,
+                                   ctypes.c_void_p(d_gbuffer_ptr), ctypes.byref(dp), ctypes.c_void_p(d_out_ptr),
+                                   ctypes.c_void_p(stream_ptr or 0)))
 
 
 def tonemap_device(d_sum_ptr, width, height, spp, d_rgb_ptr, stream_ptr=None):

@@ -12,6 +12,9 @@
 //                           chooses, as a compacted ascending list (with rt_select_scan_kernel),
 //                           and rt_mark_kernel / rt_counts_kernel beside it
 //   rt_rays_kernel          BVH::intersect + light pdf for explicit rays (test entry)
+//   rt_gbuffer_kernel       first-hit feature records from the pixel-centre rays (rt_gbuffer.h)
+//   rt_denoise_{prepare,level,resolve}_kernel  the edge-avoiding a-trous filter of a frame,
+//                           guided by those records (rt_denoise.h)
 // Every schedule writes the per-pixel float RGB sum (sample_canvas, scene.cpp:20,42) of the
 // owned rows; the bits do not depend on the kernel, the launch shape, the pixel order or the
 // partition.
@@ -49,6 +52,8 @@
 #include "rt_launch_plan.h"
 #include "rt_select.h"
 #include "rt_frame_plan.h"
+#include "rt_gbuffer.h"
+#include "rt_denoise.h"
 
 using rtd::Counters;
 using rtd::DevScene;
@@ -1712,6 +1717,13 @@ struct rt_accum {
     // A fast accumulator (rt_accum_create_fast): its chunk size, fixed for its life; 0 = parity.
     // Its chain buffer then holds fast records (rt_mega.h FastRec).
     int fast_c = 0;
+    // rt_accum_frame_u8_denoised's, made on first use and kept: the shard's first-hit records
+    // (rendered once: they depend on the scene alone), the filter's scratch and its mean frame
+    float4 *gbuf = nullptr;
+    bool gbuf_ready = false;   // the records have been rendered into gbuf
+    void *dn_ws = nullptr;
+    size_t dn_ws_bytes = 0;
+    float *dn_mean = nullptr;
 };
 
 // What rt_select_kernel reduces besides the list (device words, zeroed / set before the launch).
@@ -1927,7 +1939,8 @@ void accum_release(rt_accum *a) {
     if (a->chain || a->sums || a->rgb) {
         DeviceGuard guard(a->p.device);
         for (void *b : {(void *)a->chain, (void *)a->sums, (void *)a->rgb, (void *)a->mark_sums, (void *)a->mark_counts,
-                        (void *)a->sel_list, (void *)a->sel_blocks, (void *)a->sel_out, (void *)a->sel_mask, (void *)a->counts})
+                        (void *)a->sel_list, (void *)a->sel_blocks, (void *)a->sel_out, (void *)a->sel_mask, (void *)a->counts,
+                        (void *)a->gbuf, a->dn_ws, (void *)a->dn_mean})
             if (b) (void)hipFree(b);
     }
     delete a;
@@ -2443,6 +2456,282 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
 }
 
 void rt_accum_free(rt_accum *a) { accum_release(a); }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------ feature buffer, denoiser
+// rt_gbuffer* (include/rt_hw.h, rt_gbuffer.h): one lane per shard pixel, in the shape of
+// rt_rays_kernel; the pixel-centre ray, its closest hit and the hit's attributes, written as four
+// 16-byte stores per record.
+__global__ void __launch_bounds__(256) rt_gbuffer_kernel(DevScene sc, ShardGeom g, float4 *out) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= g.n_pixels) return;
+    int px, py;
+    rtd::shard_xy(g, p, px, py);
+    const rtd::GRecord r = rtd::gbuffer_pixel(sc, px, py);
+#pragma unroll
+    for (int k = 0; k < rtd::kGbufferQuads; ++k) out[rtd::kGbufferQuads * p + k] = r.q[k];
+}
+
+// rt_denoise_device (include/rt_hw.h, rt_denoise.h): prepare packs what a tap needs into three
+// 16-byte words per pixel, (L, kind), (N, t) and (P, 0); each level reads one (L, kind) buffer and
+// writes the other; resolve remodulates.  Every kernel maps consecutive lanes to consecutive x.
+__global__ void __launch_bounds__(256) rt_denoise_prepare_kernel(const float *__restrict__ sums, const int32_t *__restrict__ counts,
+                                                                  int spp, long long n, const rtdn::Q *__restrict__ g,
+                                                                  rtdn::Q *__restrict__ a, rtdn::Q *__restrict__ nt,
+                                                                  rtdn::Q *__restrict__ pp) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const rtdn::Q rec[4] = {g[4 * p], g[4 * p + 1], g[4 * p + 2], g[4 * p + 3]};
+    const float S[3] = {sums[3 * p], sums[3 * p + 1], sums[3 * p + 2]};
+    rtdn::Q qa, qn, qp;
+    rtdn::prepare_pixel(S, counts ? counts[p] : spp, rec, qa, qn, qp);
+    a[p] = qa;
+    nt[p] = qn;
+    pp[p] = qp;
+}
+
+// The level kernel's tile: kDnTileW x kDnTileH pixels per 256-thread block, tiles numbered row-major
+// in a one-dimensional grid.  STAGE (strides 1 and 2): the tile and its halo of 2 * stride pixels
+// are staged in LDS first, 3 x 16 B per pixel (stride 2: 40 x 16 pixels, 30 KB); at stride >= 4 the
+// halo outgrows the tile and the taps read through L2 (STAGE = 0: plain loads, any stride).
+// Measured against plain loads at strides 1 and 2 on the 1080p headline frame, two alternating
+// runs each (profiles/denoise_passes.jsonl): 5 iterations 0.753-0.759 ms staged
+// against 0.833-0.836 ms plain.
+constexpr int kDnTileW = 32, kDnTileH = 8;
+
+struct DnTileSrc {
+    const rtdn::Q *A, *NT, *PP;   // LDS
+    int x0, y0, tw;               // frame coordinates of the staged tile's corner, its width
+    __device__ __forceinline__ int at(int x, int y) const { return (y - y0) * tw + (x - x0); }
+    __device__ __forceinline__ rtdn::Q a(int x, int y) const { return A[at(x, y)]; }
+    __device__ __forceinline__ rtdn::Q nt(int x, int y) const { return NT[at(x, y)]; }
+    __device__ __forceinline__ rtdn::Q pp(int x, int y) const { return PP[at(x, y)]; }
+};
+
+template <int STAGE>
+__global__ void __launch_bounds__(256) rt_denoise_level_kernel(const rtdn::Q *__restrict__ a_in, const rtdn::Q *__restrict__ nt,
+                                                                const rtdn::Q *__restrict__ pp, rtdn::Q *__restrict__ a_out,
+                                                                int W, int H, int tiles_x, rtdn::Level lv) {
+    const int ty = (int)(blockIdx.x / (unsigned)tiles_x), tx = (int)(blockIdx.x - (unsigned)ty * (unsigned)tiles_x);
+    const int lx = (int)threadIdx.x % kDnTileW, ly = (int)threadIdx.x / kDnTileW;
+    const int x = tx * kDnTileW + lx, y = ty * kDnTileH + ly;
+    if constexpr (STAGE > 0) {
+        constexpr int halo = 2 * STAGE, tw = kDnTileW + 2 * halo, th = kDnTileH + 2 * halo;
+        __shared__ rtdn::Q tile[3][tw * th];
+        const int x0 = tx * kDnTileW - halo, y0 = ty * kDnTileH - halo;
+        for (int k = (int)threadIdx.x; k < tw * th; k += 256) {
+            const int gy = y0 + k / tw, gx = x0 + k % tw;
+            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {   // (a slot outside the frame is never read: level_pixel skips the tap)
+                const long long q = (long long)gy * W + gx;
+                tile[0][k] = a_in[q];
+                tile[1][k] = nt[q];
+                tile[2][k] = pp[q];
+            }
+        }
+        __syncthreads();
+        if (x < W && y < H)
+            a_out[(long long)y * W + x] = rtdn::level_pixel(DnTileSrc{tile[0], tile[1], tile[2], x0, y0, tw}, x, y, W, H, lv);
+    } else {
+        if (x < W && y < H) a_out[(long long)y * W + x] = rtdn::level_pixel(rtdn::PlainSrc{a_in, nt, pp, W}, x, y, W, H, lv);
+    }
+}
+
+// a == nullptr (iterations = 0): every pixel's own mean.
+__global__ void __launch_bounds__(256) rt_denoise_resolve_kernel(const float *__restrict__ sums, const int32_t *__restrict__ counts,
+                                                                  int spp, long long n, const rtdn::Q *__restrict__ g,
+                                                                  const rtdn::Q *__restrict__ a, float *__restrict__ out) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const float S[3] = {sums[3 * p], sums[3 * p + 1], sums[3 * p + 2]};
+    const int cnt = counts ? counts[p] : spp;
+    float m[3];
+    if (a) {
+        const rtdn::Q rec[4] = {g[4 * p], g[4 * p + 1], g[4 * p + 2], g[4 * p + 3]};
+        rtdn::resolve_pixel(S, cnt, rec, a[p], m);
+    } else {
+        const rtdn::Q none{0.f, 0.f, 0.f, rtm::u2f(rtdn::kPass)};
+        rtdn::resolve_pixel(S, cnt, nullptr, none, m);
+    }
+    out[3 * p] = m[0];
+    out[3 * p + 1] = m[1];
+    out[3 * p + 2] = m[2];
+}
+
+namespace {
+
+// The G-buffer of a shard into device memory (the current device is the scene copy's).
+int gbuffer_launch(rt_device_scene *d, const ShardGeom &g, float4 *d_out, hipStream_t stream) {
+    if (g.n_pixels == 0) return RT_OK;
+    hipLaunchKernelGGL(rt_gbuffer_kernel, dim3((unsigned)((g.n_pixels + 255) / 256)), dim3(256), 0, stream, d->ds, g, d_out);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// The filter on the current device.  `ws` / `ws_bytes`: the scratch of the call's owner (an
+// accumulator, or the device's cache below), grown here on first use; 64 B per pixel: the two
+// (L, kind) buffers, (N, t) and (P, 0).
+int denoise_launch(void **ws, size_t *ws_bytes, const float *d_sums, const int32_t *d_counts, int spp, int W, int H,
+                   const float *d_g, const rtdn::Params &dp, float *d_out, hipStream_t stream) {
+    const long long n = (long long)W * H;
+    const dim3 flat((unsigned)((n + 255) / 256));
+    const rtdn::Q *g = (const rtdn::Q *)d_g;
+    if (dp.iterations == 0) {
+        hipLaunchKernelGGL(rt_denoise_resolve_kernel, flat, dim3(256), 0, stream, d_sums, d_counts, spp, n, g,
+                           (const rtdn::Q *)nullptr, d_out);
+        HIP_TRY(hipGetLastError());
+        return RT_OK;
+    }
+    HIP_TRY(grow(ws, ws_bytes, (size_t)n * 4 * sizeof(rtdn::Q)));
+    rtdn::Q *a[2] = {(rtdn::Q *)*ws, (rtdn::Q *)*ws + n};
+    rtdn::Q *nt = (rtdn::Q *)*ws + 2 * n, *pp = (rtdn::Q *)*ws + 3 * n;
+    hipLaunchKernelGGL(rt_denoise_prepare_kernel, flat, dim3(256), 0, stream, d_sums, d_counts, spp, n, g, a[0], nt, pp);
+    const int tiles_x = (W + kDnTileW - 1) / kDnTileW, tiles_y = (H + kDnTileH - 1) / kDnTileH;
+    const dim3 tiles((unsigned)((long long)tiles_x * tiles_y));   // (below 2^31: the frame is)
+    for (int k = 0; k < dp.iterations; ++k) {
+        const rtdn::Level lv = rtdn::level_of(dp, k);
+        const rtdn::Q *in = a[k & 1];
+        rtdn::Q *out = a[(k + 1) & 1];
+        if (lv.stride == 1)
+            hipLaunchKernelGGL(rt_denoise_level_kernel<1>, tiles, dim3(256), 0, stream, in, nt, pp, out, W, H, tiles_x, lv);
+        else if (lv.stride == 2)
+            hipLaunchKernelGGL(rt_denoise_level_kernel<2>, tiles, dim3(256), 0, stream, in, nt, pp, out, W, H, tiles_x, lv);
+        else
+            hipLaunchKernelGGL(rt_denoise_level_kernel<0>, tiles, dim3(256), 0, stream, in, nt, pp, out, W, H, tiles_x, lv);
+    }
+    hipLaunchKernelGGL(rt_denoise_resolve_kernel, flat, dim3(256), 0, stream, d_sums, d_counts, spp, n, g,
+                       (const rtdn::Q *)a[dp.iterations & 1], d_out);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// rt_denoise_device's scratch, per device, from the first call on (only grows).
+std::mutex g_dn_mu;
+void *g_dn_ws[kRtMaxDevices] = {};
+size_t g_dn_ws_bytes[kRtMaxDevices] = {};
+
+}  // namespace
+
+extern "C" {
+
+int rt_gbuffer_device(rt_scene *s, const rt_params *p, float *d_out, void *stream) {
+    if (!s || !p || !d_out) return rt_fail(RT_ERR_ARG, "rt_gbuffer_device: NULL argument");
+    Shard sh;
+    if (int rc = shard_of(s, p, "rt_gbuffer_device", sh)) return rc;
+    if (p->device < 0 || p->device >= kRtMaxDevices || !s->dev[p->device])
+        return rt_fail(RT_ERR_ARG, "rt_gbuffer_device: scene not uploaded to device " + std::to_string(p->device));
+    rt_device_scene *d = s->dev[p->device];
+    DeviceGuard guard(d->device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    return gbuffer_launch(d, sh.g, (float4 *)d_out, (hipStream_t)stream);
+}
+
+int rt_gbuffer(rt_scene *s, const rt_params *p, float *out) {
+    if (!s || !p || !out) return rt_fail(RT_ERR_ARG, "rt_gbuffer: NULL argument");
+    Shard sh;
+    if (int rc = shard_of(s, p, "rt_gbuffer", sh)) return rc;
+    if (int rc = ensure_device_scene(s, p->device)) return rc;
+    rt_device_scene *d = s->dev[p->device];
+    DeviceGuard guard(d->device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    const size_t bytes = (size_t)sh.n_pixels * RT_GBUFFER_WORDS * sizeof(float);
+    float4 *d_out = nullptr;
+    HIP_TRY(hipMalloc((void **)&d_out, bytes ? bytes : 64));
+    int rc = gbuffer_launch(d, sh.g, d_out, nullptr);
+    if (rc == RT_OK && bytes) {
+        const hipError_t e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = rt_fail(RT_ERR_DEVICE, std::string("rt_gbuffer copy: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(d_out);
+    return rc;
+}
+
+int rt_denoise_device(const float *d_sums, const int32_t *d_counts, int32_t spp, int32_t width, int32_t height,
+                      const float *d_gbuffer, const rt_denoise_params *params, float *d_out_mean, void *stream) {
+    rtdn::Params dp;
+    if (int rc = rt_denoise_check("rt_denoise_device", d_sums, d_counts, spp, width, height, d_gbuffer, params, d_out_mean, &dp))
+        return rc;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= kRtMaxDevices) return rt_fail(RT_ERR_DEVICE, "rt_denoise_device: device id");
+    std::lock_guard<std::mutex> lock(g_dn_mu);
+    return denoise_launch(&g_dn_ws[dev], &g_dn_ws_bytes[dev], d_sums, d_counts, spp, width, height, d_gbuffer, dp, d_out_mean,
+                          (hipStream_t)stream);
+}
+
+int rt_denoise_frame_u8(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height, const float *gbuffer,
+                        const rt_denoise_params *params, int32_t device, uint8_t *out_rgb) {
+    if (!out_rgb) return rt_fail(RT_ERR_ARG, "rt_denoise_frame_u8: NULL argument");
+    rtdn::Params dp;
+    if (int rc = rt_denoise_check("rt_denoise_frame_u8", sums, counts, spp, width, height, gbuffer, params, sums, &dp)) return rc;
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev || device >= kRtMaxDevices)
+        return rt_fail(RT_ERR_DEVICE, "no HIP device " + std::to_string(device));
+    DeviceGuard guard(device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    // one staging allocation: sums, mean, G-buffer, counts, bytes (each part 256-byte aligned)
+    const size_t n = (size_t)width * height;
+    const size_t o_mean = rtp::align_up(n * 12), o_g = o_mean + rtp::align_up(n * 12), o_cnt = o_g + n * 64,
+                 o_rgb = o_cnt + rtp::align_up(n * 4), total = o_rgb + n * 3;
+    uint8_t *buf = nullptr;
+    HIP_TRY(hipMalloc((void **)&buf, total));
+    int32_t *d_counts = counts ? (int32_t *)(buf + o_cnt) : nullptr;
+    hipError_t e = hipMemcpy(buf, sums, n * 12, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + o_g, gbuffer, n * 64, hipMemcpyHostToDevice);
+    if (e == hipSuccess && counts) e = hipMemcpy(d_counts, counts, n * 4, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? RT_OK : rt_fail(RT_ERR_DEVICE, std::string("rt_denoise_frame_u8 copy: ") + hipGetErrorString(e));
+    if (rc == RT_OK) {
+        std::lock_guard<std::mutex> lock(g_dn_mu);
+        rc = denoise_launch(&g_dn_ws[device], &g_dn_ws_bytes[device], (const float *)buf, d_counts, spp, width, height,
+                            (const float *)(buf + o_g), dp, (float *)(buf + o_mean), nullptr);
+    }
+    if (rc == RT_OK) rc = rt_tonemap_u8_device((const float *)(buf + o_mean), width, height, 1, buf + o_rgb, nullptr);
+    if (rc == RT_OK) {
+        e = hipMemcpy(out_rgb, buf + o_rgb, n * 3, hipMemcpyDeviceToHost);   // (waits for the default stream)
+        if (e != hipSuccess) rc = rt_fail(RT_ERR_DEVICE, std::string("rt_denoise_frame_u8 copy: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(buf);
+    return rc;
+}
+
+int rt_accum_frame_u8_denoised(rt_accum *a, const rt_denoise_params *params, uint8_t *out_rgb) {
+    if (!a || !out_rgb) return rt_fail(RT_ERR_ARG, "rt_accum_frame_u8_denoised: NULL argument");
+    if (a->p.world != 1)
+        return rt_fail(RT_ERR_ARG, "rt_accum_frame_u8_denoised: the filter needs the whole frame (world = 1); gather the shards' "
+                                   "sums and G-buffers and use rt_denoise_device");
+    if (a->samples < 1) return rt_fail(RT_ERR_ARG, "rt_accum_frame_u8_denoised: no samples yet");
+    if (a->n_pixels == 0) return RT_OK;
+    DeviceGuard guard(a->p.device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    const int W = a->scene->width, H = a->rows;
+    // the parameters first: a refused call allocates and launches nothing (the check only asks
+    // that its pointers are not NULL, and the sums exist)
+    rtdn::Params dp;
+    const int spp = a->samples;
+    if (int rc = rt_denoise_check("rt_accum_frame_u8_denoised", a->sums, nullptr, spp, W, H, a->sums, params, a->sums, &dp))
+        return rc;
+    if (int rc = accum_buffer(a->gbuf, (size_t)a->n_pixels * rtd::kGbufferQuads)) return rc;
+    if (int rc = accum_buffer(a->dn_mean, (size_t)a->n_pixels * 3)) return rc;
+    if (int rc = accum_buffer(a->rgb, (size_t)a->n_pixels * 3)) return rc;
+    if (!a->gbuf_ready) {   // (set only once the records' launch was accepted: a call that fails before keeps it unset)
+        if (int rc = gbuffer_launch(a->scene->dev[a->p.device], a->geom, a->gbuf, a->stream)) return rc;
+        a->gbuf_ready = true;
+    }
+    const int32_t *counts = nullptr;
+    if (!accum_uniform(a)) {   // every pixel divided by its own count
+        if (int rc = accum_buffer(a->counts, (size_t)a->n_pixels)) return rc;
+        if (int rc = accum_counts_launch(a, a->counts, a->stream)) return rc;
+        counts = a->counts;
+    }
+    if (int rc = denoise_launch(&a->dn_ws, &a->dn_ws_bytes, a->sums, counts, spp, W, H, (const float *)a->gbuf, dp, a->dn_mean,
+                                a->stream))
+        return rc;
+    if (int rc = rt_tonemap_u8_device(a->dn_mean, W, H, 1, a->rgb, a->stream)) return rc;
+    if (int rc = accum_wait(a)) return rc;
+    HIP_TRY(hipMemcpy(out_rgb, a->rgb, (size_t)a->n_pixels * 3, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
 
 }  // extern "C"
 

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "rt_denoise.h"
 #include "rt_json.h"
 #include "rt_scene.h"
 #include "rt_select.h"
@@ -860,6 +861,38 @@ int rt_tonemap_u8_counts(const float *sum, const int32_t *counts, int32_t width,
     return RT_OK;
 }
 
+// The frame denoiser on the host (rt_denoise.h is its text; include/rt_hw.h its rules): prepare,
+// `iterations` levels between two buffers, resolve.
+int rt_denoise(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height, const float *gbuffer,
+               const rt_denoise_params *params, float *out_mean) {
+    rtdn::Params dp;
+    if (int rc = rt_denoise_check("rt_denoise", sums, counts, spp, width, height, gbuffer, params, out_mean, &dp)) return rc;
+    const int64_t n = (int64_t)width * height;
+    auto count_of = [&](int64_t p) { return counts ? counts[p] : spp; };
+    if (dp.iterations == 0) {
+        for (int64_t p = 0; p < n; ++p) {
+            const float rn = rtdn::mean_normalizer(count_of(p));
+            for (int c = 0; c < 3; ++c) out_mean[3 * p + c] = sums[3 * p + c] * rn;
+        }
+        return RT_OK;
+    }
+    std::vector<rtdn::Q> g((size_t)n * 4), a[2], nt((size_t)n), pp((size_t)n);
+    std::memcpy(g.data(), gbuffer, (size_t)n * 64);   // (the caller's records need not be 16-byte aligned)
+    a[0].resize((size_t)n);
+    a[1].resize((size_t)n);
+    for (int64_t p = 0; p < n; ++p) rtdn::prepare_pixel(sums + 3 * p, count_of(p), &g[4 * p], a[0][p], nt[p], pp[p]);
+    for (int k = 0; k < dp.iterations; ++k) {
+        const rtdn::Level lv = rtdn::level_of(dp, k);
+        const rtdn::PlainSrc src{a[k & 1].data(), nt.data(), pp.data(), width};
+        rtdn::Q *dst = a[(k + 1) & 1].data();
+        for (int y = 0; y < height; ++y)
+            for (int x = 0; x < width; ++x) dst[(int64_t)y * width + x] = rtdn::level_pixel(src, x, y, width, height, lv);
+    }
+    const rtdn::Q *fin = a[dp.iterations & 1].data();
+    for (int64_t p = 0; p < n; ++p) rtdn::resolve_pixel(sums + 3 * p, count_of(p), &g[4 * p], fin[p], out_mean + 3 * p);
+    return RT_OK;
+}
+
 int rt_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t height) {
     if (!path || !rgb || width <= 0 || height <= 0) return rt_fail(RT_ERR_ARG, "rt_write_ppm: bad argument");
     std::FILE *f = std::fopen(path, "wb");
@@ -875,6 +908,21 @@ const char *rt_last_error(void) { return g_last_error.c_str(); }
 int32_t rt_abi_version(void) { return RT_ABI_VERSION; }
 
 }  // extern "C"
+
+int rt_denoise_check(const char *who, const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
+                     const float *gbuffer, const rt_denoise_params *params, const float *out_mean, rtdn::Params *resolved) {
+    const std::string w = who;
+    if (!sums || !gbuffer || !out_mean) return rt_fail(RT_ERR_ARG, w + ": NULL argument");
+    if (width <= 0 || height <= 0) return rt_fail(RT_ERR_ARG, w + ": bad frame size");
+    if (!counts && spp < 1) return rt_fail(RT_ERR_ARG, w + ": without counts, spp must be at least 1");
+    if ((int64_t)width * height > INT32_MAX) return rt_fail(RT_ERR_LIMIT, w + ": frames above 2^31 pixels are not supported");
+    const rt_denoise_params none{-1, 0.f, 0.f, 0};
+    const rt_denoise_params &p = params ? *params : none;
+    if (rtdn::resolve_params(p.iterations, p.sigma_color, p.sigma_plane, p.normal_power_log2, *resolved))
+        return rt_fail(RT_ERR_ARG, w + ": iterations above " + std::to_string(rtdn::kMaxIterations) + ", normal_power_log2 above " +
+                                       std::to_string(rtdn::kMaxNormalPowerLog2) + " or a non-finite sigma");
+    return RT_OK;
+}
 
 int64_t rt_shard_rows_impl(int32_t height, int32_t rank, int32_t world, int32_t row_block, int32_t *rows_out) {
     if (height <= 0 || world <= 0 || rank < 0 || rank >= world || row_block <= 0) return rt_fail(RT_ERR_ARG, "rt_shard_rows: bad partition");

@@ -27,6 +27,18 @@
 //                       fast_chunk = c.  With RT_PASS_SPP and / or RT_ADAPT: the passes run on fast
 //                       accumulators (rt_accum_create_fast) with chunk size c; a checkpoint resumes
 //                       only into the kind and chunk size that wrote it.
+// Denoising and feature images (rt_denoise*, rt_gbuffer; unset, the bytes are the ones above):
+//   RT_DENOISE=k        every frame the run writes (the one-shot frame, each pass's preview, the
+//                       adaptive result) passes through the edge-avoiding a-trous filter with k
+//                       iterations (1..6; the other parameters at their defaults) before the 8-bit
+//                       finish.  One GPU with passes: on the accumulator (rt_accum_frame_u8_denoised).
+//                       Otherwise the float frame (and the counts) assembled from the shards and the
+//                       frame's G-buffer, rendered once on device 0, are filtered on device 0
+//                       (rt_denoise_frame_u8).  k = 0 is refused here, although the library takes
+//                       iterations = 0 (the unfiltered mean): it would be the run with RT_DENOISE unset.
+//   RT_AOV_OUT=pfx      the first-hit features of the frame: pfx.normal.ppm (N * 0.5 + 0.5),
+//                       pfx.albedo.ppm (the linear base colour) and pfx.depth.pgm (binary 16-bit PGM,
+//                       big-endian, hit distance / the frame's largest; a miss is 0).
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
@@ -43,11 +55,59 @@ static void check(int rc) {
     if (rc != RT_OK) throw std::runtime_error(rt_last_error());
 }
 
+// The whole frame's first-hit records (RT_GBUFFER_WORDS floats per pixel), rendered on device 0.
+static std::vector<float> frame_gbuffer(rt_scene *scene, int width, int height) {
+    std::vector<float> g((size_t)width * height * RT_GBUFFER_WORDS);
+    rt_params p{};
+    p.world = 1;
+    p.row_block = 8;
+    check(rt_gbuffer(scene, &p, g.data()));
+    return g;
+}
+
+// RT_DENOISE: the filter's parameters (k iterations, the rest at their defaults), or none.
+struct Denoise {
+    bool on = false;
+    rt_denoise_params params{-1, 0.f, 0.f, 0};
+    std::vector<float> gbuffer;   // the frame's, rendered at the first frame that needs it
+};
+
+static void write_file(const std::string &path, const char *header, const std::vector<uint8_t> &bytes) {
+    std::FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) throw std::runtime_error("RT_AOV_OUT: cannot write " + path);
+    std::fputs(header, f);
+    const bool ok = std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    if (std::fclose(f) != 0 || !ok) throw std::runtime_error("RT_AOV_OUT: short write to " + path);
+}
+
+// RT_AOV_OUT: the normal, albedo and depth images of the frame's G-buffer.
+static void write_aovs(const std::string &prefix, const std::vector<float> &g, int width, int height) {
+    const size_t n = (size_t)width * height;
+    auto byte_of = [](float v) { return (uint8_t)(std::min(std::max(v, 0.f), 1.f) * 255.f + 0.5f); };
+    std::vector<uint8_t> normal(n * 3), albedo(n * 3), depth(n * 2);
+    float far = 0.f;
+    for (size_t p = 0; p < n; ++p) far = std::max(far, g[p * RT_GBUFFER_WORDS + 3]);
+    for (size_t p = 0; p < n; ++p) {
+        const float *r = &g[p * RT_GBUFFER_WORDS];
+        for (int c = 0; c < 3; ++c) {
+            normal[3 * p + c] = byte_of(r[c] * 0.5f + 0.5f);
+            albedo[3 * p + c] = byte_of(r[4 + c]);
+        }
+        const int d = far > 0.f ? (int)(std::min(std::max(r[3] / far, 0.f), 1.f) * 65535.f + 0.5f) : 0;
+        depth[2 * p] = (uint8_t)(d >> 8);
+        depth[2 * p + 1] = (uint8_t)(d & 255);
+    }
+    const std::string size = std::to_string(width) + " " + std::to_string(height);
+    write_file(prefix + ".normal.ppm", ("P6\n" + size + "\n255\n").c_str(), normal);
+    write_file(prefix + ".albedo.ppm", ("P6\n" + size + "\n255\n").c_str(), albedo);
+    write_file(prefix + ".depth.pgm", ("P5\n" + size + "\n65535\n").c_str(), depth);
+}
+
 // The frame in passes: device d renders shard (rank d, world n) through its own accumulator.
 // `adapt` (RT_ADAPT): its threshold; the passes are then those of adaptive rendering (above).
 static void render_passes(rt_scene *scene, int width, int height, int samples, int n_gpus, int pass_spp,
                           const char *ckpt, const std::string &output, const float *adapt = nullptr,
-                          const char *counts_out = nullptr, int fast_chunk = 0) {
+                          const char *counts_out = nullptr, int fast_chunk = 0, Denoise *dn = nullptr) {
     const int n = n_gpus > 0 ? n_gpus : rt_device_count();
     if (n < 1) throw std::runtime_error("no HIP device");
     if (samples < 1) throw std::runtime_error("samples per pixel must be >= 1");
@@ -96,7 +156,37 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
     if (resume) std::cout << "Resumed from " << ckpt << " at " << done << " samples." << std::endl;
     std::vector<uint8_t> rgb((size_t)width * height * 3), part;
     std::vector<int32_t> rows((size_t)height);
+    std::vector<float> sums, spart;
+    std::vector<int32_t> counts, cshard;
     auto write_frame = [&]() {
+        if (dn && dn->on && n == 1) {   // the accumulator owns the whole frame: filtered where it lives
+            check(rt_accum_frame_u8_denoised(acc[0], &dn->params, rgb.data()));
+            check(rt_write_ppm(output.c_str(), rgb.data(), width, height));
+            return;
+        }
+        if (dn && dn->on) {   // the shards' sums and counts in frame order, filtered on device 0
+            sums.resize((size_t)width * height * 3);
+            counts.resize((size_t)width * height);
+            for (int r = 0; r < n; ++r) {
+                const int64_t k = rt_shard_rows(height, r, n, 8, rows.data());
+                if (k < 0) check((int)k);
+                spart.resize((size_t)k * width * 3);
+                cshard.resize((size_t)k * width);
+                check(rt_accum_sums(acc[(size_t)r], spart.data()));
+                check(rt_accum_counts(acc[(size_t)r], cshard.data()));
+                for (int64_t i = 0; i < k; ++i) {
+                    std::copy(spart.begin() + i * width * 3, spart.begin() + (i + 1) * width * 3,
+                              sums.begin() + (size_t)rows[(size_t)i] * width * 3);
+                    std::copy(cshard.begin() + i * width, cshard.begin() + (i + 1) * width,
+                              counts.begin() + (size_t)rows[(size_t)i] * width);
+                }
+            }
+            // (after rt_accum_sums has waited for every shard's pass: nothing else runs on device 0)
+            if (dn->gbuffer.empty()) dn->gbuffer = frame_gbuffer(scene, width, height);
+            check(rt_denoise_frame_u8(sums.data(), counts.data(), 0, width, height, dn->gbuffer.data(), &dn->params, 0, rgb.data()));
+            check(rt_write_ppm(output.c_str(), rgb.data(), width, height));
+            return;
+        }
         for (int r = 0; r < n; ++r) {
             const int64_t k = rt_shard_rows(height, r, n, 8, rows.data());
             if (k < 0) check((int)k);
@@ -204,6 +294,17 @@ int main(int argc, char *argv[]) {
     const char *adapt_env = std::getenv("RT_ADAPT"), *counts_out = std::getenv("RT_COUNTS_OUT");
     const bool adaptive = adapt_env && *adapt_env;
     const float adapt = adaptive ? std::strtof(adapt_env, nullptr) : 0.f;
+    Denoise dn;
+    if (const char *dn_env = std::getenv("RT_DENOISE"); dn_env && *dn_env) {
+        dn.on = true;
+        dn.params.iterations = std::atoi(dn_env);
+        if (dn.params.iterations < 1 || dn.params.iterations > 6) {
+            std::cerr << "rt_solution: RT_DENOISE must be 1..6" << std::endl;
+            rt_scene_free(scene);
+            return 1;
+        }
+    }
+    const char *aov_out = std::getenv("RT_AOV_OUT");
     const char *fast_env = std::getenv("RT_FAST");
     const int fast_chunk = fast_env && *fast_env ? std::atoi(fast_env) : 0;
     if (fast_env && *fast_env && fast_chunk < 1) throw std::runtime_error("RT_FAST must be >= 1");
@@ -213,7 +314,11 @@ int main(int argc, char *argv[]) {
         try {
             render_passes(scene, width, height, samples, n_gpus, pass_spp, ckpt && *ckpt ? ckpt : nullptr, output,
                           adaptive ? &adapt : nullptr, adaptive && counts_out && *counts_out ? counts_out : nullptr,
-                          fast_chunk);
+                          fast_chunk, &dn);
+            if (aov_out && *aov_out) {
+                if (dn.gbuffer.empty()) dn.gbuffer = frame_gbuffer(scene, width, height);
+                write_aovs(aov_out, dn.gbuffer, width, height);
+            }
         } catch (const std::exception &e) {   // (a checkpoint that does not fit, a failed pass: the message, status 1)
             std::cerr << "rt_solution: " << e.what() << std::endl;
             rt_scene_free(scene);
@@ -235,7 +340,18 @@ int main(int argc, char *argv[]) {
     rt_stats st{};
     // every shard finished to 8 bits on its GPU and gathered device-to-device onto GPU 0
     std::vector<uint8_t> rgb((size_t)width * height * 3);
-    check(rt_render_frame(scene, &p, n_gpus, nullptr, rgb.data(), nullptr, &st));
+    if (dn.on) {   // the float frame gathered instead, filtered on device 0, then the same finish
+        std::vector<float> sums((size_t)width * height * 3);
+        check(rt_render_frame(scene, &p, n_gpus, nullptr, nullptr, sums.data(), &st));
+        dn.gbuffer = frame_gbuffer(scene, width, height);
+        check(rt_denoise_frame_u8(sums.data(), nullptr, samples, width, height, dn.gbuffer.data(), &dn.params, 0, rgb.data()));
+    } else {
+        check(rt_render_frame(scene, &p, n_gpus, nullptr, rgb.data(), nullptr, &st));
+    }
+    if (aov_out && *aov_out) {
+        if (dn.gbuffer.empty()) dn.gbuffer = frame_gbuffer(scene, width, height);
+        write_aovs(aov_out, dn.gbuffer, width, height);
+    }
     double total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::cout << "      " << total << " seconds (" << total * 1000 << " ms) elapsed; render " << st.render_ms
               << " ms on " << st.devices << " MI355X." << std::endl;

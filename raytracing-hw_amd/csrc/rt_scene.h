@@ -40,5 +40,13 @@ int rt_fail(int code, const std::string &msg);
 // implemented in rt_device.hip: frees every device copy and the device image
 void rt_device_scene_release(rt_scene *s);
 
+// argument checks of rt_denoise / rt_denoise_device (rt_host.cpp): RT_OK and the resolved
+// parameters (rt_denoise.h), or the failure as `who` reports it
+namespace rtdn {
+struct Params;
+}
+int rt_denoise_check(const char *who, const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
+                     const float *gbuffer, const rt_denoise_params *params, const float *out_mean, rtdn::Params *resolved);
+
 // row partition helper (rt_host.cpp)
 int64_t rt_shard_rows_impl(int32_t height, int32_t rank, int32_t world, int32_t row_block, int32_t *rows_out);
