@@ -730,7 +730,9 @@ def device_selfcheck(which=0):
     (0: the fast reciprocal over every float with a normal reciprocal; 1: the computed linear
     texel decode over every byte and the packed LDS RNG word over every minstd state; 2: the
     cooperative leaf step over synthetic leaves; 3: the traversal's root-free cull, far_gt and
-    the squared 1e9 constant, against sqrtf(x) > acc over 2^24 pairs at the rounding boundary)."""
+    the squared 1e9 constant, against sqrtf(x) > acc over 2^24 pairs at the rounding boundary;
+    4: the material records of every scene that is on a device, dword for dword against the
+    scene's tables there; an error where no scene is uploaded)."""
     n = ctypes.c_uint64(0)
     _check(lib().rt_device_selfcheck(which, ctypes.byref(n)))
     return int(n.value)

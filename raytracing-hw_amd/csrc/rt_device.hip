@@ -48,6 +48,7 @@
 #include "rt_mega.h"
 #include "rt_quant_lut.h"
 #include "rt_scene.h"
+#include "rt_material.h"
 #include "rt_bvh_layout.h"
 #include "rt_launch_plan.h"
 #include "rt_select.h"
@@ -144,6 +145,24 @@ constexpr bool kSpecMaskLoad = RT_SPEC_MASK_LOAD != 0;
 #define RT_SPEC_FAR_DIST2 0
 #endif
 constexpr bool kPlainFarDist2 = RT_PLAIN_FAR_DIST2 != 0, kSpecFarDist2 = RT_SPEC_FAR_DIST2 != 0;
+// The shading pass's gather (rt_path.h RT_SHADE_GATHER), per kernel as the cull above, by the
+// same rule.  One call, three interleaved runs each, against the RT_SHADE_GATHER=0 build
+// (profiles/shgather_forms_ab.jsonl, the gather in both kernels):
+//   plain kernel, 1-GPU frame      984.0-985.1 ms against 1007.4-1008.8 (-23.6 ms, spread 1.4);
+//   runahead kernel, 8-way shards  slowest 174.3-176.1 against 174.8-176.0 ms: no gain.
+// Only the plain kernel (the parity render without counters: not COUNT, FAST, LSPLIT or the
+// accumulator's CHAIN) takes the gather: it is the one the rule was applied to.  The runahead
+// kernel keeps the tables' form, and so do the counting, fast-mode and accumulator
+// instantiations, which were not measured and whose spills the gather raises (fast 11 -> 28
+// VGPRs, fast accumulator 14 -> 49, counting 48 -> 55, counting fast 31 -> 52 at compile time).
+#ifndef RT_PLAIN_SHADE_GATHER
+#define RT_PLAIN_SHADE_GATHER RT_SHADE_GATHER
+#endif
+#ifndef RT_SPEC_SHADE_GATHER
+#define RT_SPEC_SHADE_GATHER 0
+#endif
+constexpr int kPlainShade = RT_PLAIN_SHADE_GATHER ? rtd::SHADE_GATHER_HOLD : rtd::SHADE_TABLES,
+              kSpecShade = RT_SPEC_SHADE_GATHER ? rtd::SHADE_GATHER_HOLD : rtd::SHADE_TABLES;
 // Leaf rounds per coop step (rt_wavefront.h trav_step_coop round_min): a further round
 // while at least this many leaf lanes are unserved.  Plain kernel: 8 (sponza 1080p 1292 ->
 // 1278 ms against one round per step).  The runahead kernel's depends on the scene
@@ -177,13 +196,15 @@ constexpr double kWfCompactBelow = 0.75;   // wavefront: dense queue until this 
 // The device image of a scene (built once on the host, copied to every device it renders on).
 struct rt_device_blob {
     std::vector<uint8_t> bytes;
-    size_t o_tri, o_attr, o_tan, o_node, o_light, o_lnode, o_mf, o_mt, o_nt, o_ti, o_tx, o_lut;
+    size_t o_tri, o_attr, o_tan, o_node, o_light, o_lnode, o_mf, o_mt, o_nt, o_ti, o_tx, o_lut, o_mat;
+    size_t n_texels;   // of the tiled texel array (rt_device_selfcheck 4)
 };
 
 struct rt_device_scene {
     int device = -1;
     void *buf = nullptr;               // one allocation holding every scene array
     DevScene ds{};
+    size_t n_texels = 0;               // of ds.texels
     unsigned long long *counters = nullptr;  // rtd::kCounterWords x u64: the render's, then the order pre-pass's (kOrderCounters)
     unsigned long long *queue = nullptr;     // the queue block: rtd::kQueueWords x u64 (rt_mega.h QueueWord)
     int cu_count = 0;
@@ -359,6 +380,8 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
                unsigned long long *queue, const int *order, unsigned *cost, int cs, int mode) {
     constexpr bool kSpec = SPEC && !COUNT && !FAST && !LSPLIT;
     constexpr bool kChain = CHAIN && !COUNT && !FAST && !LSPLIT;
+    // (the shading pass's form: RT_PLAIN_SHADE_GATHER / RT_SPEC_SHADE_GATHER above)
+    constexpr int kShade = kSpec ? kSpecShade : (!COUNT && !FAST && !LSPLIT && !kChain) ? kPlainShade : rtd::SHADE_TABLES;
     // (a pass of a fast accumulator: `cs` is its chunk size, `mode` the units per item)
     constexpr bool kFastChain = CHAIN && FAST && !COUNT && !LSPLIT && !SPEC;
     const int park_below = kFastChain ? 0 : rtp::mode_park_below(mode), resume_pct = kFastChain ? 0 : rtp::mode_resume_pct(mode);
@@ -621,16 +644,15 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
             if (L.state == rtd::M_READY) {
                 L.T.phase = 0;   // dead in a READY lane (its stack is empty: T.sp == 0)
                 L.T.sp = 0;
-                rtd::mega_shade<COUNT, FAST, kChain>(L, sc, g, st, spp, out, cost, root, S, cnt, kSpec && tail, park, queue);
+                rtd::mega_shade<COUNT, FAST, kChain, kShade>(L, sc, g, st, spp, out, cost, root, S, cnt, kSpec && tail, park, queue);
             } else {
                 L.T.phase = (int)(pk & 3u);
                 L.state = (int)((pk >> 2) & 7u);
                 L.T.sp = (int)(pk >> 5);
             }
         } else {
-            rtd::mega_iterate<COUNT, decltype(S), decltype(nodes), FAST, LSPLIT, kChain>(L, shade_now, sc, g, st, spp, out,
-                                                                                       cost, root, S, nodes, cnt,
-                                                                                       kSpec && tail, false, queue);
+            rtd::mega_iterate<COUNT, decltype(S), decltype(nodes), FAST, LSPLIT, kChain, kShade>(
+                L, shade_now, sc, g, st, spp, out, cost, root, S, nodes, cnt, kSpec && tail, false, queue);
             // RT_INV_RECOMPUTE: 1 / direction is recomputed after a shading pass (the same IEEE
             // division as make_ray, so the same bits), so a traversing lane does not hold it
             // through the pass's register peak (plain kernel 48 -> 42 spilled VGPRs; 39 with
@@ -943,29 +965,6 @@ size_t append(std::vector<uint8_t> &blob, const std::vector<T> &v, size_t pre = 
     return off;
 }
 
-// Device texture layout: texture t's texels in 4x4 tiles, tile (tx, ty) at tile index
-// ty * ceil(w/4) + tx, texel (x & 3, y & 3) at 4 * (y & 3) + (x & 3) inside it; tex_info keeps
-// (offset in texels, width, height, channels).
-void tile_textures(const std::vector<uint32_t> &info, const std::vector<uint8_t> &texels, std::vector<uint32_t> &info_out,
-                   std::vector<uint32_t> &out) {
-    const size_t n = info.size() / 4;
-    info_out = info;
-    out.clear();
-    for (size_t t = 0; t < n; ++t) {
-        const uint32_t off = info[4 * t], w = info[4 * t + 1], h = info[4 * t + 2];
-        const uint32_t tw = (w + 3) / 4, th = (h + 3) / 4;
-        const size_t base = out.size();
-        info_out[4 * t] = (uint32_t)base;
-        out.resize(base + (size_t)tw * th * 16, 0u);
-        for (uint32_t y = 0; y < h; ++y)
-            for (uint32_t x = 0; x < w; ++x) {
-                uint32_t v;
-                std::memcpy(&v, &texels[4 * ((size_t)off + (size_t)y * w + x)], 4);
-                out[base + ((size_t)(y >> 2) * tw + (x >> 2)) * 16 + (y & 3) * 4 + (x & 3)] = v;
-            }
-    }
-}
-
 // The device image of the scene, built once per scene (every device copies the same bytes).
 int ensure_blob(rt_scene *s) {
     if (s->blob) return RT_OK;
@@ -998,19 +997,36 @@ int ensure_blob(rt_scene *s) {
     // textures in 4x4-texel tiles (64 B, one cache line): a bilinear 2x2 footprint usually
     // stays in one line instead of always spanning two rows (rt_path.h tex_sample)
     std::vector<uint32_t> tinfo, tiled;
-    tile_textures(s->tex_info, s->texels, tinfo, tiled);
+    rtmat::tile_textures(s->tex_info, s->texels, tinfo, tiled);
     b->o_ti = append(blob, tinfo);
     b->o_tx = append(blob, tiled);
+    b->n_texels = tiled.size();
     std::vector<float> lut(512);
     rtd::fill_decode_lut(lut.data());
     b->o_lut = append(blob, lut);
+    // per-mesh material records (rt_material.h): 128 B each, 128-B aligned (every array starts
+    // 256-B aligned), descriptors of the tiled layout inline
+    std::vector<uint32_t> mat;
+    if (!rtmat::build_records(s->mesh_f.data(), s->mesh_tex.data(), s->mesh_f.size() / 12, tinfo.data(), tinfo.size() / 4, mat)) {
+        delete b;
+        return rt_fail(RT_ERR_FORMAT, "texture index out of range");
+    }
+    b->o_mat = append(blob, mat);
     blob.resize(rtp::align_up(blob.size()) + 256);
     s->blob = b;
     return RT_OK;
 }
 
+// The device copies that exist (rt_device_selfcheck 4 checks the material records of each).
+std::mutex g_live_mu;
+std::vector<rt_device_scene *> g_live;
+
 void free_device_scene(rt_device_scene *d) {
     if (!d) return;
+    {
+        std::lock_guard<std::mutex> lk(g_live_mu);
+        g_live.erase(std::remove(g_live.begin(), g_live.end(), d), g_live.end());
+    }
     DeviceGuard guard(d->device);
     if (guard.ok) {
         for (hipStream_t q : {d->fr.stream, d->fr.cp_stream})
@@ -1075,6 +1091,12 @@ int ensure_device_scene(rt_scene *s, int device) {
     ds.tex_info = (const uint4 *)(base + b.o_ti);
     ds.texels = (const uint32_t *)(base + b.o_tx);
     ds.lut = (const float *)(base + b.o_lut);
+    d->n_texels = b.n_texels;
+#if RT_SHADE_GATHER
+    ds.mat = (const uint4 *)(base + b.o_mat);
+    ds.any_nmap = 0;
+    for (size_t m = 0; m < s->mesh_tex.size() / 4; ++m) ds.any_nmap |= s->mesh_tex[4 * m + 1] >= 0;
+#endif
     ds.n_lights = (int)(s->light.size() / 16);
     ds.n_tris = (int)(s->tri.size() / 12);
     ds.n_nodes = (int)(s->node.size() / 8);
@@ -1089,6 +1111,10 @@ int ensure_device_scene(rt_scene *s, int device) {
     std::memcpy(ds.cam_axes, s->cam_axes, sizeof ds.cam_axes);
     std::memcpy(ds.tan_fov, s->tan_half_fov, sizeof ds.tan_fov);
     s->dev[device] = d;
+    {
+        std::lock_guard<std::mutex> lk(g_live_mu);
+        g_live.push_back(d);
+    }
     return RT_OK;
 }
 
@@ -3036,6 +3062,39 @@ __global__ void __launch_bounds__(256) decode_check_kernel(unsigned long long *b
     if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
 }
 
+// rt_device_selfcheck 4: every material record of an uploaded scene (rt_material.h), read the
+// way the shading pass reads it, against the scene's own tables on the device: the 12 mesh_f
+// floats and 4 mesh_tex indices bit for bit, each slot's descriptor against its texture's
+// tex_info row, (0, 1, 1) for an absent slot, zero padding; a present slot's texture must end
+// inside the texel array (n_texels).  Counts the dwords that differ.
+#if RT_SHADE_GATHER
+__global__ void __launch_bounds__(256) mat_check_kernel(rtd::DevScene sc, unsigned long long n_texels, unsigned long long *bad) {
+    unsigned long long local = 0;
+    for (int m = blockIdx.x * blockDim.x + threadIdx.x; m < sc.n_meshes; m += gridDim.x * blockDim.x) {
+        uint32_t r[32];
+        for (int q = 0; q < 8; ++q) {
+            const uint4 x = sc.mat[8 * m + q];
+            r[4 * q] = x.x; r[4 * q + 1] = x.y; r[4 * q + 2] = x.z; r[4 * q + 3] = x.w;
+        }
+        for (int k = 0; k < 12; ++k) local += r[k] != __float_as_uint(sc.mesh_f[12 * m + k]);
+        for (int k = 0; k < 4; ++k) {
+            const int t = sc.mesh_tex[4 * m + k];
+            local += r[rtmat::kRecTex + k] != (uint32_t)t;
+            uint4 ti = make_uint4(0u, 1u, 1u, 4u);
+            if (t >= 0) {
+                ti = sc.tex_info[t];
+                local += (unsigned long long)ti.x + (unsigned long long)((ti.y + 3) / 4) * ((ti.z + 3) / 4) * 16 > n_texels;
+            }
+            const uint32_t *d = r + rtmat::kRecDesc + 3 * k;
+            local += (d[0] != ti.x) + (d[1] != ti.y) + (d[2] != ti.z);
+        }
+        for (int k = 28; k < 32; ++k) local += r[k] != 0u;
+    }
+    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
+    if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
+}
+#endif
+
 // rt_device_selfcheck 3: the root-free cull (rt_wavefront.h far_gt, kFarMax2) against the
 // device's own sqrtf(x) > acc: 2^24 of the host test's generated pairs (far_case_acc /
 // far_case_x: every exponent of acc, x around acc * acc and around the exact boundary), the
@@ -3180,13 +3239,42 @@ void coop_cases(std::vector<float> &tri, std::vector<float> &rays, std::vector<u
         leaves[2 * (size_t)i + 1] = k0 + len;
     }
 }
+
+// rt_device_selfcheck 4 over every device copy that exists (an error where there is none).
+int mat_selfcheck(uint64_t *mismatches) {
+#if RT_SHADE_GATHER
+    std::lock_guard<std::mutex> lk(g_live_mu);
+    if (g_live.empty()) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck 4: no scene is uploaded");
+    uint64_t total = 0;
+    for (rt_device_scene *ds : g_live) {
+        DeviceGuard guard(ds->device);
+        if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "rt_device_selfcheck 4: hipSetDevice failed");
+        unsigned long long *d = nullptr, h = 0;
+        HIP_TRY(hipMalloc((void **)&d, sizeof *d));
+        hipError_t e = hipMemset(d, 0, sizeof *d);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(mat_check_kernel, dim3(64), dim3(256), 0, nullptr, ds->ds, (unsigned long long)ds->n_texels, d);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        if (e != hipSuccess) return rt_fail(RT_ERR_DEVICE, std::string("rt_device_selfcheck 4: ") + hipGetErrorString(e));
+        total += h;
+    }
+    *mismatches = total;
+    return RT_OK;
+#else
+    return rt_fail(RT_ERR_ARG, "rt_device_selfcheck 4: built without RT_SHADE_GATHER");
+#endif
+}
 }  // namespace
 
 extern "C" {
 
 int rt_device_selfcheck(int32_t which, uint64_t *mismatches) {
     if (!mismatches) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck: null output");
-    if (which < 0 || which > 3) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck: unknown check " + std::to_string(which));
+    if (which < 0 || which > 4) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck: unknown check " + std::to_string(which));
+    if (which == 4) return mat_selfcheck(mismatches);
     unsigned long long *d = nullptr;
     HIP_TRY(hipMalloc((void **)&d, sizeof *d));
     hipError_t e = hipMemset(d, 0, sizeof *d);

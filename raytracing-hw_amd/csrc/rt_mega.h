@@ -435,7 +435,9 @@ __device__ void spec_job_end(ML &L, const DevScene &sc, const ShardGeom &g, cons
 // `park` (wave-uniform; lane-resident kernel, hand-off): a path end that leaves the pixel
 // unfinished stops there (idle, still holding the pixel, for park_pixel) instead of starting
 // its next sample.
-template <bool COUNT, bool FAST = false, bool CHAIN = false, class Stack, class ML>
+// `G`: how the pass fetches (rt_path.h SHADE_TABLES / SHADE_GATHER_HOLD), chosen per kernel
+// (rt_device.hip RT_PLAIN_SHADE_GATHER, RT_SPEC_SHADE_GATHER).
+template <bool COUNT, bool FAST = false, bool CHAIN = false, int G = SHADE_TABLES, class Stack, class ML>
 __device__ __forceinline__ void mega_shade(ML &L, const DevScene &sc, const ShardGeom &g, const WfState &st,
                                            int spp, float *out, unsigned *cost, const NodeRec &root, Stack &stk,
                                            Counters &cnt, bool tail = false, bool park = false,
@@ -446,14 +448,31 @@ __device__ __forceinline__ void mega_shade(ML &L, const DevScene &sc, const Shar
     bool next = false;
     const bool shaded = h.prim >= 0 && h.t < sc.max_distance;
     if (shaded) {
-#if defined(__HIPCC__)
-        if constexpr (kUvRecompute) {   // (u, v) of the closest hit (rt_wavefront.h RT_UV_RECOMPUTE)
+        ShadeTri r1;
+        const ShadeTri *r1p = nullptr;
+#if RT_SHADE_GATHER && defined(__HIPCC__)
+        if constexpr (G != SHADE_TABLES) {
+            // round 1 of the gather (rt_path.h shade_pre): the triangle's three records, once for
+            // (u, v) and the geometric normal, and its four attribute records, issued together
             RT_CHECK(h.prim < sc.n_tris, 1, h.prim, h.prim = 0);
-            hit_uv(sc, L.r, h);
-        }
+            const float4 *tt = sc.tri + 3 * (size_t)h.prim, *ta = sc.tri_attr + 4 * (size_t)h.prim;
+            const float4 t0 = tt[0], t1 = tt[1];
+            r1 = ShadeTri{tt[2], ta[0], ta[1], ta[2], ta[3]};
+            r1p = &r1;
+            asm volatile("" ::"v"(t0.x), "v"(t1.x), "v"(r1.t2.x), "v"(r1.a0.x), "v"(r1.a1.x), "v"(r1.a2.x), "v"(r1.a3.x));
+            if constexpr (kUvRecompute) hit_uv_of(t0, t1, r1.t2, L.r, h);   // (rt_wavefront.h RT_UV_RECOMPUTE)
+        } else
 #endif
+        {
+#if defined(__HIPCC__)
+            if constexpr (kUvRecompute) {   // (u, v) of the closest hit (rt_wavefront.h RT_UV_RECOMPUTE)
+                RT_CHECK(h.prim < sc.n_tris, 1, h.prim, h.prim = 0);
+                hit_uv(sc, L.r, h);
+            }
+#endif
+        }
         Rng rng = lane_rng(L);
-        const bool cont = shade_hit<COUNT>(sc, L.r, h, rng, cnt, P, c.nv, stk);   // (stack free: T.sp == 0)
+        const bool cont = shade_hit<COUNT, G>(sc, L.r, h, rng, cnt, P, c.nv, stk, r1p);   // (stack free: T.sp == 0)
         lane_rng_set(L, rng);
         if (cont && c.power > 0) {
             c.power -= 1;
@@ -629,7 +648,8 @@ __device__ __forceinline__ void mega_shade_split(ML &L, const DevScene &sc, cons
 
 // One iteration of a wave's main loop for one lane, given the wave's decision: shade the
 // READY lanes this iteration (shade_now), or step the traversing lanes.
-template <bool COUNT, class Stack, class Nodes, bool FAST = false, bool LSPLIT = false, bool CHAIN = false, class ML>
+template <bool COUNT, class Stack, class Nodes, bool FAST = false, bool LSPLIT = false, bool CHAIN = false,
+          int G = SHADE_TABLES, class ML>
 __device__ __forceinline__ void mega_iterate(ML &L, bool shade_now, const DevScene &sc, const ShardGeom &g,
                                              const WfState &st, int spp, float *out, unsigned *cost,
                                              const NodeRec &root, Stack &stk, const Nodes &nodes, Counters &cnt,
@@ -648,7 +668,7 @@ __device__ __forceinline__ void mega_iterate(ML &L, bool shade_now, const DevSce
     }
     if (shade_now) {
         if (L.state == M_READY)
-            mega_shade<COUNT, FAST, CHAIN>(L, sc, g, st, spp, out, cost, root, stk, cnt, tail, park, queue);
+            mega_shade<COUNT, FAST, CHAIN, G>(L, sc, g, st, spp, out, cost, root, stk, cnt, tail, park, queue);
     } else if (L.state == M_TRAV) {
         if (trav_step<COUNT>(sc, L.r, L.T, stk, nodes, cnt)) L.state = M_READY;
     }

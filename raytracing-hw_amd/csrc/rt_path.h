@@ -109,6 +109,18 @@ __device__ __forceinline__ float texel_decode(const float *lut, uint32_t byte, b
 #endif
 }
 
+// RT_SHADE_GATHER: the lane-resident kernels' shading pass reads its material and texture data
+// in three rounds of loads issued together (shade_pre below) instead of one dependent round
+// trip per table and per texture.  0: the A/B build, the pass as it was.
+#ifndef RT_SHADE_GATHER
+#define RT_SHADE_GATHER 1
+#endif
+// How shade_pre / shade_post fetch (template parameter G): the tables one after the other, or
+// the gather, with the base-colour texels held in registers from shade_pre to shade_post
+// (shade_hit only: the light-split kernel's vertex crosses the light walk in a record, and
+// that kernel keeps the tables' form).
+enum { SHADE_TABLES = 0, SHADE_GATHER_HOLD = 1 };
+
 struct DevScene {
     const float4 *tri;        // 3 x float4 / triangle: (v0, U.x) (U.yz, V.xy) (V.z, n_geo)
     const float4 *tri_attr;   // 4 x float4 / triangle: normals, texcoords, mesh id
@@ -132,6 +144,10 @@ struct DevScene {
     float cam_pos[3];
     float cam_axes[9];
     float tan_fov[2];
+#if RT_SHADE_GATHER
+    const uint4 *mat;         // 8 x uint4 / mesh: the material record (rt_material.h)
+    int any_nmap;             // some mesh has a normal map (else no shaded hit reads tri_tan)
+#endif
 };
 
 struct Counters {
@@ -446,6 +462,64 @@ __device__ float light_pdf(const DevScene &sc, V3 point, V3 direction, Counters 
 
 // ------------------------------------------------------------------------ textures
 // Texture::interpolate_sample (primitive.h:182-215); RGBA8, four channels always.
+// tex_sample_ti (below) in two halves, so the shading pass can issue the loads of several
+// textures together (shade_pre, RT_SHADE_GATHER): tex_taps gives the four bilinear taps' indices
+// into the texel array and the weights' fractions, tex_decode the sample from the four
+// texels; the same operations, checked bit for bit by tests/native/shade_gather_host.cpp.
+// float -> int as the device converts (NaN to 0, saturating), defined on the host too.
+__device__ __forceinline__ int tex_f2i(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (int)x;
+#else
+    if (!(x == x)) return 0;
+    return x >= 2147483648.f ? 2147483647 : x < -2147483648.f ? (int)-2147483648LL : (int)x;
+#endif
+}
+#ifdef __HIPCC__
+constexpr bool kTexTiled = true;    // device copy: 4x4-texel tiles (rt_material.h tile_textures)
+#else
+constexpr bool kTexTiled = false;   // host view: row-major
+#endif
+template <bool TILED = kTexTiled>
+__device__ __forceinline__ void tex_taps(uint32_t off, int W, int H, V2 p, uint32_t idx[4], float &dx, float &dy) {
+    p.x -= floorf(p.x);
+    p.y -= floorf(p.y);
+    p.x *= (float)W;
+    p.y *= (float)H;
+    const int px = tex_f2i(floorf(p.x)), py = tex_f2i(floorf(p.y));
+    dx = p.x - floorf(p.x);
+    dy = p.y - floorf(p.y);
+    // (px + d) % W without a division: p - floorf(p) is in [0, 1], so px is in [0, W] and
+    // px + d in [0, W + 1] <= 2W; two conditional subtractions give the remainder (W = 1
+    // included).  NaN coordinates convert to 0 on the device, as they would for %.
+    auto wrap = [](int v, int n) {
+        v = v >= n ? v - n : v;
+        return v >= n ? v - n : v;
+    };
+#pragma unroll
+    for (int ddy = 0; ddy < 2; ++ddy)
+#pragma unroll
+        for (int ddx = 0; ddx < 2; ++ddx) {
+            const int x = wrap(px + ddx, W), y = wrap(py + ddy, H);
+            const uint32_t i = TILED ? (uint32_t)(((y >> 2) * ((W + 3) >> 2) + (x >> 2)) * 16 + (y & 3) * 4 + (x & 3))
+                                     : (uint32_t)(y * W + x);
+            idx[ddx * 2 + ddy] = off + i;
+        }
+}
+__device__ __forceinline__ V4 tex_decode(const float *lut, const uint32_t texel[4], float dx, float dy, bool srgb) {
+    float res[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t byte = (texel[k] >> (8 * c)) & 0xffu;
+            v[k] = texel_decode(lut, byte, srgb);   // kSrgbLut[byte] or (float)(int)byte / 255.f
+        }
+        res[c] = v[0] * (1 - dx) * (1 - dy) + v[1] * (1 - dx) * dy + v[2] * dx * (1 - dy) + v[3] * dx * dy;
+    }
+    return V4{res[0], res[1], res[2], res[3]};
+}
 __device__ __forceinline__ V4 tex_sample_ti(const DevScene &sc, const uint4 ti, V2 p, bool srgb) {
     const int W = (int)ti.y, H = (int)ti.z;
     p.x -= floorf(p.x);
@@ -850,45 +924,139 @@ __device__ __forceinline__ V3 fold_path(const LaneRec &P, int nv, bool last_here
 //   shade_post — pdf from its parts, BRDF factors of vertex nv-1, the bounce ray; false where
 //                pdf <= 0 or NaN.
 // ShadeMid is what crosses the split (a lane-slot record in the lane-resident kernel).
+// One texture slot of the gather's round 3: its four raw texels and the bilinear fractions.
+struct SlotTexels {
+    uint32_t x[4];
+    float dx, dy;
+};
 struct ShadeMid {
     V3 pos, N, dir;
     V2 tc;
     float r2, metallic;
     int mesh;
+    // SHADE_GATHER_HOLD only: the base-colour slot's index and gathered texels, fetched with the
+    // other slots' in shade_pre and decoded in shade_post (never in a record)
+    int mt_b;
+    SlotTexels base;
 };
 
-template <bool COUNT, class Rec>
+// Round 1 of the gather, where the caller issued it (rt_mega.h mega_shade, with the triangle
+// records that hit_uv needs): the triangle's third record and its four attribute records.
+struct ShadeTri {
+    float4 t2, a0, a1, a2, a3;
+};
+
+#if RT_SHADE_GATHER && defined(__HIPCC__)
+// Round 3 for one slot with descriptor d = (texel offset, width, height): skipped, tap
+// arithmetic included, by a wave in which no lane has the slot (computed for every slot of
+// every lane the arithmetic cost more than the gather saved, 1007 against 984 ms per frame).
+__device__ __forceinline__ SlotTexels slot_gather(const DevScene &sc, bool present, const uint32_t *d, V2 tc) {
+    SlotTexels o{{0u, 0u, 0u, 0u}, 0.f, 0.f};
+    if (__any(present)) {
+        uint32_t ix[4];
+        tex_taps(d[0], (int)d[1], (int)d[2], tc, ix, o.dx, o.dy);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o.x[k] = sc.texels[ix[k]];
+    }
+    return o;
+}
+#endif
+
+// The gather (G != SHADE_TABLES; every address is a function of (prim, u, v) and scene tables):
+//   round 1  the triangle's records and its four tri_attr records (mesh id, texcoords);
+//   round 2  the mesh's material record (rt_material.h: mesh_f, mesh_tex and the four slots'
+//            descriptors inline), and tri_tan where the scene has a normal map at all
+//            (DevScene::any_nmap, so the skip is wave-uniform);
+//   round 3  the four bilinear taps of the emission, normal, metallic-roughness and base
+//            slots, addresses by tex_taps.  A lane whose slot is absent loads texel 0
+//            through its record's (0, 1, 1) descriptor and never uses it; a wave in which no
+//            lane has a slot skips that slot's loads.
+// The arithmetic is the tables' form's, operation for operation: only where loads are issued
+// and where their results wait differs.
+template <bool COUNT, int G = SHADE_TABLES, class Rec>
 __device__ __forceinline__ bool shade_pre(const DevScene &sc, const Ray &r, const Hit &hit, Rng &rng, Counters &cnt,
-                                          Rec &P, int &nv, ShadeMid &m) {
+                                          Rec &P, int &nv, ShadeMid &m, const ShadeTri *r1 = nullptr) {
     RT_PROF_BEGIN
     if (COUNT) cnt.hits++;
     int id = hit.prim;
     RT_CHECK(id >= 0 && id < sc.n_tris, 1, id, id = 0);
     RT_CHECK(nv >= 0 && nv < kMaxDepth - 1, 2, nv, nv = 0);
     const float u = hit.u, v = hit.v;
-    const float4 t2 = sc.tri[3 * id + 2];
+    const bool have_r1 = G != SHADE_TABLES && r1;
+    const float4 t2 = have_r1 ? r1->t2 : sc.tri[3 * id + 2];
     V3 ngeo{t2.y, t2.z, t2.w};
     bool inside = false;
     if (rtv::dot(r.d, ngeo) > 0) { inside = true; ngeo = rtv::neg(ngeo); }
-    const float4 a0 = sc.tri_attr[4 * id], a1 = sc.tri_attr[4 * id + 1], a2 = sc.tri_attr[4 * id + 2],
-                 a3 = sc.tri_attr[4 * id + 3];
+    const float4 a0 = have_r1 ? r1->a0 : sc.tri_attr[4 * id], a1 = have_r1 ? r1->a1 : sc.tri_attr[4 * id + 1],
+                 a2 = have_r1 ? r1->a2 : sc.tri_attr[4 * id + 2], a3 = have_r1 ? r1->a3 : sc.tri_attr[4 * id + 3];
     int mesh = __float_as_int(a3.w);
     RT_CHECK(mesh >= 0 && mesh < sc.n_meshes, 3, mesh, mesh = 0);
-    const float *mf = sc.mesh_f + 12 * mesh;
-    const int *mt = sc.mesh_tex + 4 * mesh;
-    // texture descriptors of the emission, normal and metallic-roughness slots, read together
-    // (one round trip, not one per texture on the way)
-    const int mt_e = mt[3], mt_n = mt[1], mt_mr = mt[2];
-    const uint4 ti_e = sc.tex_info[mt_e >= 0 ? mt_e : 0], ti_n = sc.tex_info[mt_n >= 0 ? mt_n : 0],
-                ti_mr = sc.tex_info[mt_mr >= 0 ? mt_mr : 0];
+    float mrec[12];   // (gather: mesh_f from the record)
+    const float *mf = mrec;
+    int mt_e, mt_n, mt_mr;
+    uint4 ti_e{}, ti_n{}, ti_mr{};
+    float4 g0{}, g1{}, g2{};
+    uint32_t dsc[12] = {};                 // (gather: the four slots' descriptors from the record)
+    SlotTexels se{}, sn{}, sm{};           // (gather: emission, normal, metallic-roughness)
+#if RT_SHADE_GATHER
+    if constexpr (G != SHADE_TABLES) {
+        const uint4 *rec = sc.mat + 8 * mesh;
+        const uint4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4], q5 = rec[5], q6 = rec[6];
+        if (sc.any_nmap) {
+            g0 = sc.tri_tan[3 * id];
+            g1 = sc.tri_tan[3 * id + 1];
+            g2 = sc.tri_tan[3 * id + 2];
+        }
 #ifdef __HIPCC__
-    asm volatile("" ::"v"(ti_e.x), "v"(ti_n.x), "v"(ti_mr.x));   // (keep the reads here, not sunk into the branches)
+        asm volatile("" ::"v"(q0.x), "v"(q1.x), "v"(q2.x), "v"(q3.x), "v"(q4.x), "v"(q5.x), "v"(q6.x), "v"(g0.x), "v"(g1.x),
+                     "v"(g2.x));   // (one round trip: none of them sunk into the branches)
 #endif
+        const uint32_t f[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
+#pragma unroll
+        for (int k = 0; k < 12; ++k) mrec[k] = __uint_as_float(f[k]);
+        mt_n = (int)q3.y;
+        mt_mr = (int)q3.z;
+        mt_e = (int)q3.w;
+        const uint32_t d[12] = {q4.x, q4.y, q4.z, q4.w, q5.x, q5.y, q5.z, q5.w, q6.x, q6.y, q6.z, q6.w};
+#pragma unroll
+        for (int k = 0; k < 12; ++k) dsc[k] = d[k];
+        m.mt_b = (int)q3.x;
+    } else
+#endif
+    {
+        mf = sc.mesh_f + 12 * mesh;
+        const int *mt = sc.mesh_tex + 4 * mesh;
+        // texture descriptors of the emission, normal and metallic-roughness slots, read together
+        // (one round trip, not one per texture on the way)
+        mt_e = mt[3], mt_n = mt[1], mt_mr = mt[2];
+        ti_e = sc.tex_info[mt_e >= 0 ? mt_e : 0], ti_n = sc.tex_info[mt_n >= 0 ? mt_n : 0],
+        ti_mr = sc.tex_info[mt_mr >= 0 ? mt_mr : 0];
+#ifdef __HIPCC__
+        asm volatile("" ::"v"(ti_e.x), "v"(ti_n.x), "v"(ti_mr.x));   // (keep the reads here, not sunk into the branches)
+#endif
+    }
     const float w = 1 - u - v;
     const V2 tc{w * a2.y + u * a2.w + v * a3.y, w * a2.z + u * a3.x + v * a3.z};
+#if RT_SHADE_GATHER && defined(__HIPCC__)
+    if constexpr (G != SHADE_TABLES) {
+        se = slot_gather(sc, mt_e >= 0, dsc + 9, tc);
+        sn = slot_gather(sc, mt_n >= 0, dsc + 3, tc);
+        sm = slot_gather(sc, mt_mr >= 0, dsc + 6, tc);
+        m.base = slot_gather(sc, m.mt_b >= 0, dsc, tc);
+        // (issued together, not sunk into the branches)
+        asm volatile("" ::"v"(se.x[0]), "v"(se.x[1]), "v"(se.x[2]), "v"(se.x[3]), "v"(sn.x[0]), "v"(sn.x[1]), "v"(sn.x[2]),
+                     "v"(sn.x[3]), "v"(sm.x[0]), "v"(sm.x[1]), "v"(sm.x[2]), "v"(sm.x[3]), "v"(m.base.x[0]), "v"(m.base.x[1]),
+                     "v"(m.base.x[2]), "v"(m.base.x[3]));
+    }
+#endif
+    // a slot's sample: decoded from the gathered texels, or fetched here
+    auto slot_sample = [&](const uint4 ti, const SlotTexels &t, bool srgb) {
+        if constexpr (G != SHADE_TABLES) return tex_decode(sc.lut, t.x, t.dx, t.dy, srgb);
+        else return tex_sample_ti(sc, ti, tc, srgb);
+    };
     // Primitive::get_emission (primitive.cpp:121-129)
     V3 emission{mf[3], mf[4], mf[5]};
-    if (mt_e >= 0) emission = rtv::mulv(rtv::reduce(tex_sample_ti(sc, ti_e, tc, true)), emission);
+    if (mt_e >= 0) emission = rtv::mulv(rtv::reduce(slot_sample(ti_e, se, true)), emission);
     P.set_e(nv, emission);
     RT_PROF_SEG(0);
     // Primitive::get_shading_normal (primitive.cpp:86-105)
@@ -896,12 +1064,16 @@ __device__ __forceinline__ bool shade_pre(const DevScene &sc, const Ray &r, cons
     V3 lz = rtv::normal(rtv::add(rtv::add(rtv::mul(n0, w), rtv::mul(n1, u)), rtv::mul(n2, v)));
     V3 N = lz;
     if (mt_n >= 0) {
-        const float4 g0 = sc.tri_tan[3 * id], g1 = sc.tri_tan[3 * id + 1], g2 = sc.tri_tan[3 * id + 2];
+        if constexpr (G == SHADE_TABLES) {
+            g0 = sc.tri_tan[3 * id];
+            g1 = sc.tri_tan[3 * id + 1];
+            g2 = sc.tri_tan[3 * id + 2];
+        }
         V3 t0{g0.x, g0.y, g0.z}, t1{g1.x, g1.y, g1.z}, tt2{g2.x, g2.y, g2.z};
         V3 lx = rtv::normal(mul_vector_d(sc.mesh_nt + 16 * mesh,
                                          rtv::normal(rtv::add(rtv::add(rtv::mul(t0, w), rtv::mul(t1, u)), rtv::mul(tt2, v)))));
         V3 ly = rtv::mul(rtv::cross(lz, lx), g0.w);
-        V3 s = rtv::reduce(tex_sample_ti(sc, ti_n, tc, false));
+        V3 s = rtv::reduce(slot_sample(ti_n, sn, false));
         V3 ln = rtv::mul(rtv::addf(s, -0.5f), 2.f);
         N = rtv::normal(rtv::add(rtv::add(rtv::mul(lx, ln.x), rtv::mul(ly, ln.y)), rtv::mul(lz, ln.z)));
     }
@@ -910,7 +1082,7 @@ __device__ __forceinline__ bool shade_pre(const DevScene &sc, const Ray &r, cons
     // Primitive::get_metallic_roughness (primitive.cpp:131-140)
     float r2 = mf[7], metallic = mf[6];
     if (mt_mr >= 0) {
-        V4 mr = tex_sample_ti(sc, ti_mr, tc, false);
+        V4 mr = slot_sample(ti_mr, sm, false);
         float rr = mr.y * mr.y;
         r2 = rr * mf[7];
         metallic = mr.z * mf[6];
@@ -942,7 +1114,7 @@ __device__ __forceinline__ float scene_pdf_lp(const DevScene &sc, V3 N, V3 eye, 
     return (cosine_pdf(N, dir) + lp + vndf_pdf(N, eye, r2, dir)) / 3;
 }
 
-template <class Rec>
+template <int G = SHADE_TABLES, class Rec>
 __device__ __forceinline__ bool shade_post(const DevScene &sc, const V3 rd, const ShadeMid &m, float pdf, Rec &P, int nv,
                                            Ray &r_out) {
     RT_PROF_BEGIN
@@ -950,8 +1122,27 @@ __device__ __forceinline__ bool shade_post(const DevScene &sc, const V3 rd, cons
     const V3 pos = m.pos, N = m.N, dir = m.dir, eye = rtv::neg(rd);
     const V2 tc = m.tc;
     const float r2 = m.r2, metallic = m.metallic;
-    const float *mf = sc.mesh_f + 12 * m.mesh;
-    const int *mt = sc.mesh_tex + 4 * m.mesh;
+    float mrec[9];   // (gather: base colour and alpha from the record)
+    const float *mf = mrec;
+    const int *mt = nullptr;
+    int mt_b = -1;
+#if RT_SHADE_GATHER
+    if constexpr (G != SHADE_TABLES) {
+        // the record's base colour and alpha again (one round trip, not held through the
+        // sample and the pdf)
+        const uint4 *rec = sc.mat + 8 * m.mesh;
+        const uint4 q0 = rec[0], q2 = rec[2];
+        mrec[0] = __uint_as_float(q0.x);
+        mrec[1] = __uint_as_float(q0.y);
+        mrec[2] = __uint_as_float(q0.z);
+        mrec[8] = __uint_as_float(q2.x);
+        mt_b = m.mt_b;
+    } else
+#endif
+    {
+        mf = sc.mesh_f + 12 * m.mesh;
+        mt = sc.mesh_tex + 4 * m.mesh;
+    }
     // BRDF of this vertex (scene.cpp:134-154): used only if the child ray hits
     const float coeff = 1 / pdf;
     const V3 half = rtv::normal(rtv::sub(dir, rd));
@@ -959,7 +1150,11 @@ __device__ __forceinline__ bool shade_post(const DevScene &sc, const V3 rd, cons
     const float spec = ggx(r2, N, half) * vis;
     const float VdotH = fabsf(rtv::dot(eye, half));
     V3 base{mf[0], mf[1], mf[2]};
-    if (mt[0] >= 0) base = rtv::mulv(rtv::reduce(tex_sample(sc, mt[0], tc, true)), base);
+    if constexpr (G == SHADE_TABLES) {
+        if (mt[0] >= 0) base = rtv::mulv(rtv::reduce(tex_sample(sc, mt[0], tc, true)), base);
+    } else if (mt_b >= 0) {
+        base = rtv::mulv(rtv::reduce(tex_decode(sc.lut, m.base.x, m.base.dx, m.base.dy, true)), base);
+    }
     const float p5 = rtm::pow5_glibc(1.f - VdotH);
     const V3 fres{base.x + (1.f - base.x) * p5, base.y + (1.f - base.y) * p5, base.z + (1.f - base.z) * p5};
     const V3 metal = rtv::mul(fres, spec);
@@ -979,15 +1174,15 @@ __device__ __forceinline__ bool shade_post(const DevScene &sc, const V3 rd, cons
 // ray.  Returns false where the recursion returns at this vertex (sample below the surface,
 // pdf <= 0 or NaN).
 // `stk`: the light walk's stack (see light_pdf).
-template <bool COUNT, class Rec, class Stack>
+template <bool COUNT, int G = SHADE_TABLES, class Rec, class Stack>
 __device__ bool shade_hit(const DevScene &sc, Ray &r, const Hit &hit, Rng &rng, Counters &cnt, Rec &P, int &nv,
-                          Stack &stk) {
+                          Stack &stk, const ShadeTri *r1 = nullptr) {
     ShadeMid m;
-    if (!shade_pre<COUNT>(sc, r, hit, rng, cnt, P, nv, m)) return false;
+    if (!shade_pre<COUNT, G>(sc, r, hit, rng, cnt, P, nv, m, r1)) return false;
     RT_PROF_BEGIN
     const float pdf = scene_pdf<COUNT>(sc, m.pos, m.N, rtv::neg(r.d), m.r2, m.dir, cnt, stk);
     RT_PROF_SEG(4);
-    return shade_post(sc, r.d, m, pdf, P, nv, r);
+    return shade_post<G>(sc, r.d, m, pdf, P, nv, r);
 }
 template <bool COUNT, class Rec>
 __device__ bool shade_hit(const DevScene &sc, Ray &r, const Hit &hit, Rng &rng, Counters &cnt, Rec &P, int &nv) {

@@ -698,6 +698,13 @@ constexpr bool kUvRecompute = RT_UV_RECOMPUTE != 0;
 
 // (u, v) of a closest hit whose (t, triangle) the coop leaf step found (RT_UV_RECOMPUTE): the
 // same Moller-Trumbore test of the same triangle and ray, so the bits the step would have kept.
+// hit_uv_of: from the triangle's records already loaded (the shading pass's gather).
+__device__ __forceinline__ void hit_uv_of(const float4 t0, const float4 t1, const float4 t2, const Ray &r, Hit &h) {
+    TriHit th;
+    tri_hit_bl(V3{t0.x, t0.y, t0.z}, V3{t0.w, t1.x, t1.y}, V3{t1.z, t1.w, t2.x}, r, th);
+    h.u = th.u;
+    h.v = th.v;
+}
 __device__ __forceinline__ void hit_uv(const DevScene &sc, const Ray &r, Hit &h) {
     const float4 *t = sc.tri + 3 * (size_t)h.prim;
     const float4 t0 = t[0], t1 = t[1], t2 = t[2];
