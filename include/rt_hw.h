@@ -509,6 +509,94 @@ int rt_denoise_frame_u8(const float *sums, const int32_t *counts, int32_t spp, i
  * sample RT_ERR_ARG, like rt_accum_frame_u8. */
 int rt_accum_frame_u8_denoised(rt_accum *accum, const rt_denoise_params *params, uint8_t *out_rgb);
 
+/* The variance-guided mode of the denoiser (additive in ABI 6; after SVGF, Schied et al. 2017): the
+ * same a-trous filter with three changes.  Surfaces whose radiance is not albedo-modulated pass
+ * through; a firefly clamp runs before the filter; and the colour falloff is measured in standard
+ * deviations of a per-pixel variance, which is filtered along with the colour.  A preview filter:
+ * the clamp removes energy (on cornell 64 x 64 at 8 samples the filtered frame's
+ * mean over the clamped range is about three quarters of the converged frame's), and without a
+ * caller's variance the variance is a spatial estimate, which cannot tell noise from detail that
+ * the albedo does not carry.  rt_denoise and its kin above are untouched by it.
+ * csrc/rt_denoise_guided.h is its text, shared by the device kernels and the host function; the
+ * arithmetic rules are rt_denoise's (f32 +, -, *, /, comparisons and selects in the order written,
+ * nothing contracted, correctly rounded division), so host, device and a restatement agree bit
+ * for bit.
+ *
+ * Parameters.  A NULL params is all defaults.  iterations, sigma_plane, normal_power_log2: as
+ * rt_denoise_params.  sigma_var: <= 0 takes the default 2.  firefly: 0 takes the default 8, a
+ * negative one switches the clamp off.  A NaN or infinite sigma_var, sigma_plane or firefly is
+ * RT_ERR_ARG.  sigma_var = 2 and firefly = 8, and the 5 x 5 and 7 x 7 windows below, come from a
+ * coarse sweep on three small fixtures (cornell 64 x 64, sponza_mini 64 x 36, cornell_blob
+ * 48 x 48; sigma_var in {1, 2, 4}, firefly in {off, 2, 4, 8, 16}); they were not tuned on the
+ * headline frame.
+ *
+ * Inputs and out_mean as rt_denoise's.  variance: NULL, or W * H floats, the variance of each
+ * pixel's demodulated mean L summed over the channels (the seam for per-sample second moments,
+ * which no render kernel keeps today).  out_variance: NULL, or W * H floats (below).
+ *
+ * Write geo(p, q) = nd * wp with nd and wp exactly rt_denoise's normal and plane terms for centre
+ * p and tap q, and lum(L) = (0.2126f * L.x + 0.7152f * L.y) + 0.0722f * L.z.
+ * 1. Prepare: rt_denoise's m, a', L and kind, and then: a hit whose three albedo channels are all
+ *    not > 1e-3f is of kind pass, whatever its count (an emitter, a black surface: its own mean
+ *    goes through and it reaches no other pixel).  Only a valid pixel keeps its L.
+ * 2. Firefly clamp, skipped when firefly < 0; every pixel reads the unclamped frame.  For a valid
+ *    p, over the 24 taps q = p + (dx, dy), dy = -2 .. 2 outer, dx = -2 .. 2 inner, centre skipped,
+ *    using a tap that is inside the frame, valid and has g = geo(p, q) > 0:
+ *      sg = sg + g;  sl = sl + g * lum(Lq)                         both from +0
+ *    and when sg > 0:  mean = sl / sg;  cap = firefly * (mean > 0 ? mean : 0);  when lum(Lp) > cap,
+ *    scale = cap / lum(Lp) and each channel of Lp is multiplied by scale.
+ * 3. Variance V.  With `variance` given: the caller's value for a valid pixel when it is finite
+ *    and > 0, else 0.  With NULL: for a valid p over the 49 taps of the 7 x 7 window on the
+ *    clamped L (centre included, dy outer, dx inner), using a tap as in 2:
+ *      sg = sg + g;  s1 = s1 + g * Lq;  s2 = s2 + g * (Lq * Lq)   per channel; the tap is counted
+ *      mu = s1 / sg;  var = s2 / sg - mu * mu;  var = var > 0 ? var : 0   per channel
+ *      V = (var.x + var.y) + var.z;  V = 0 when fewer than 2 taps were counted or V is not finite
+ *    A pixel that is not valid holds V = 0.
+ * 4. Level k = 0 .. iterations - 1, stride s = 2^k, reading one buffer of (L, kind, V) and writing
+ *    the other.  A pass centre is copied.  Otherwise first the variance prefilter over the 3 x 3
+ *    taps q = p + (dx, dy) (stride 1, dy outer, dx inner) that are inside and valid in the level's
+ *    input, c(0) = 1/2, c(+-1) = 1/4:
+ *      gw = gw + c(dx) * c(dy);  gv = gv + (c(dx) * c(dy)) * Vq
+ *      vbar = gw > 0 ? gv / gw : 0;  cden = (sigma_var * sigma_var) * vbar + 1e-8f
+ *    (no halving per level: the variance shrinks by itself), then rt_denoise's 25 taps with its
+ *    skips and its h, nd, wp, and
+ *      wc = 1 for a fill centre, else 1 / (1 + ((d.x * d.x + d.y * d.y) + d.z * d.z) / cden)
+ *      w  = ((h * nd) * wp) * wc;  a tap whose w is not > 0 is skipped
+ *      sw = sw + w;  sL = sL + w * Lq;  sV = sV + (w * w) * Vq
+ *    The centre becomes (sL / sw, valid, sV / (sw * sw)) when sw > 0 and the three colour
+ *    quotients are finite, keeping its old V when the new one is not finite; (0, 0, 0, its kind,
+ *    V = 0) when sw is not > 0; and stays as it was when a colour quotient overflowed.
+ * 5. Resolve as rt_denoise.  out_variance receives V after the last level for a pixel that is
+ *    valid then and 0 for every other.  With iterations = 0 out_mean is m bit for bit, nothing is
+ *    clamped, and out_variance is all zeros.
+ *
+ * rt_denoise_guided runs on the host; rt_denoise_guided_device on the current HIP device,
+ * asynchronously on `stream`, every pointer but params a device pointer, with the host function's
+ * bits.  Its scratch (72 B per pixel: rt_denoise's 64 and the two variance words) is the one
+ * rt_denoise_device keeps per device, so it only grows and one call of either per device may be in
+ * flight.  Refusals as rt_denoise's.  rt_denoise_guided_frame_u8 is rt_denoise_frame_u8 with this
+ * mode (variance NULL or W * H host floats); rt_accum_frame_u8_guided is
+ * rt_accum_frame_u8_denoised with this mode and variance = NULL: the same accumulator contract
+ * (world = 1, nothing written into the accumulator, the G-buffer rendered on first use, world > 1
+ * and "no samples" RT_ERR_ARG, a refused call leaves nothing half made). */
+typedef struct {
+    int32_t iterations;          /* 0..6; < 0: 5 (0 is a value: the mean, bit for bit)             */
+    float sigma_var;             /* <= 0: 2.  colour falloff in standard deviations                 */
+    float sigma_plane;           /* <= 0: 0.02, as rt_denoise_params                                */
+    int32_t normal_power_log2;   /* 1..16; <= 0: 6, as rt_denoise_params                            */
+    float firefly;               /* 0: 8.  < 0: no clamp.  > 0: cap = firefly x neighbourhood mean  */
+} rt_denoise_guided_params;
+int rt_denoise_guided(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
+                      const float *gbuffer, const float *variance, const rt_denoise_guided_params *params,
+                      float *out_mean, float *out_variance);
+int rt_denoise_guided_device(const float *d_sums, const int32_t *d_counts, int32_t spp, int32_t width, int32_t height,
+                             const float *d_gbuffer, const float *d_variance, const rt_denoise_guided_params *params,
+                             float *d_out_mean, float *d_out_variance, void *stream);
+int rt_denoise_guided_frame_u8(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
+                               const float *gbuffer, const float *variance, const rt_denoise_guided_params *params,
+                               int32_t device, uint8_t *out_rgb);
+int rt_accum_frame_u8_guided(rt_accum *accum, const rt_denoise_guided_params *params, uint8_t *out_rgb);
+
 /* --- misc --------------------------------------------------------------------------- */
 const char *rt_last_error(void);
 int32_t rt_abi_version(void);

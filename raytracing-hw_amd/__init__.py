@@ -82,6 +82,16 @@ def denoise_params(iterations=-1, sigma_color=0.0, sigma_plane=0.0, normal_power
     return RtDenoiseParams(int(iterations), float(sigma_color), float(sigma_plane), int(normal_power_log2))
 
 
+class RtDenoiseGuidedParams(ctypes.Structure):
+    """include/rt_hw.h rt_denoise_guided_params; firefly 0 takes the default, a negative one switches the clamp off."""
+    _fields_ = [("iterations", ctypes.c_int32), ("sigma_var", ctypes.c_float), ("sigma_plane", ctypes.c_float),
+                ("normal_power_log2", ctypes.c_int32), ("firefly", ctypes.c_float)]
+
+
+def denoise_guided_params(iterations=-1, sigma_var=0.0, sigma_plane=0.0, normal_power_log2=0, firefly=0.0):
+    return RtDenoiseGuidedParams(int(iterations), float(sigma_var), float(sigma_plane), int(normal_power_log2), float(firefly))
+
+
 class RtStats(ctypes.Structure):
     _fields_ = [("pixels", ctypes.c_uint64), ("samples", ctypes.c_uint64), ("rays", ctypes.c_uint64),
                 ("aabb_tests", ctypes.c_uint64), ("tri_tests", ctypes.c_uint64), ("light_queries", ctypes.c_uint64),
@@ -158,6 +168,15 @@ ABI = {
     "rt_denoise_frame_u8": (ctypes.c_int, [_c_f, _c_i, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_f,
                                            ctypes.POINTER(RtDenoiseParams), ctypes.c_int32, _c_b]),
     "rt_accum_frame_u8_denoised": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtDenoiseParams), _c_b]),
+    # the denoiser's variance-guided mode
+    "rt_denoise_guided": (ctypes.c_int, [_c_f, _c_i, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_f, _c_f,
+                                         ctypes.POINTER(RtDenoiseGuidedParams), _c_f, _c_f]),
+    "rt_denoise_guided_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(RtDenoiseGuidedParams),
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rt_denoise_guided_frame_u8": (ctypes.c_int, [_c_f, _c_i, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_f, _c_f,
+                                                  ctypes.POINTER(RtDenoiseGuidedParams), ctypes.c_int32, _c_b]),
+    "rt_accum_frame_u8_guided": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtDenoiseGuidedParams), _c_b]),
 }
 
 _lib_handle = None
@@ -495,13 +514,20 @@ class Accumulator:
     def device_sums_ptr(self):
         return int(lib().rt_accum_device_sums(self._h) or 0)
 
-    def frame(self, denoise=None):
+    def frame(self, denoise=None, guided=False):
         """(rows, W, 3) uint8: the shard finished at spp = samples (on the device).  denoise: True
         (the default parameters) or a dict of denoise_params' arguments runs the frame denoiser in
-        front of the finish (rt_accum_frame_u8_denoised; whole-frame accumulators only)."""
+        front of the finish (rt_accum_frame_u8_denoised; whole-frame accumulators only).  guided:
+        with denoise, the variance-guided mode (rt_accum_frame_u8_guided; the dict then holds
+        denoise_guided_params' arguments)."""
         out = np.zeros((len(self.rows), self._scene.width, 3), np.uint8)
         if denoise is None or denoise is False:
+            if guided:
+                raise ValueError("guided=True needs denoise=True or a dict of denoise_guided_params' arguments")
             _check(lib().rt_accum_frame_u8(self._h, out.ctypes.data_as(_c_b)))
+        elif guided:
+            gp = denoise_guided_params(**(denoise if isinstance(denoise, dict) else {}))
+            _check(lib().rt_accum_frame_u8_guided(self._h, ctypes.byref(gp), out.ctypes.data_as(_c_b)))
         else:
             dp = denoise_params(**(denoise if isinstance(denoise, dict) else {}))
             _check(lib().rt_accum_frame_u8_denoised(self._h, ctypes.byref(dp), out.ctypes.data_as(_c_b)))
@@ -708,6 +734,59 @@ def denoise_device(d_sums_ptr, d_counts_ptr, spp, width, height, d_gbuffer_ptr, 
     _check(lib().rt_denoise_device(ctypes.c_void_p(d_sums_ptr), ctypes.c_void_p(d_counts_ptr or 0), int(spp), width, height,
                                    ctypes.c_void_p(d_gbuffer_ptr), ctypes.byref(dp), ctypes.c_void_p(d_out_ptr),
                                    ctypes.c_void_p(stream_ptr or 0)))
+
+
+def _variance_input(variance, h, w):
+    if variance is None:
+        return None
+    variance = np.ascontiguousarray(variance, np.float32)
+    if variance.size != h * w:
+        raise ValueError("variance must have one entry per pixel")
+    return variance
+
+
+def denoise_guided(sums, counts_or_spp, gbuffer, variance=None, return_variance=False, **params):
+    """rt_denoise_guided (the host function): the variance-guided mode of the denoiser, with its
+    firefly clamp.  variance: None (the spatial estimate) or an (H, W) array, the variance of each
+    pixel's demodulated mean.  return_variance: also the (H, W) filtered variance.  params:
+    denoise_guided_params' arguments."""
+    sums, counts, spp, rec = _denoise_inputs(sums, counts_or_spp, gbuffer)
+    h, w = sums.shape[0], sums.shape[1]
+    variance = _variance_input(variance, h, w)
+    out = np.zeros((h, w, 3), np.float32)
+    out_v = np.zeros((h, w), np.float32) if return_variance else None
+    gp = denoise_guided_params(**params)
+    _check(lib().rt_denoise_guided(sums.ctypes.data_as(_c_f), counts.ctypes.data_as(_c_i) if counts is not None else None, spp, w, h,
+                                   rec.ctypes.data_as(_c_f), variance.ctypes.data_as(_c_f) if variance is not None else None,
+                                   ctypes.byref(gp), out.ctypes.data_as(_c_f),
+                                   out_v.ctypes.data_as(_c_f) if return_variance else None))
+    return (out, out_v) if return_variance else out
+
+
+def denoise_guided_frame_u8(sums, counts_or_spp, gbuffer, variance=None, device=0, **params):
+    """rt_denoise_guided_frame_u8: host arrays in, the guided mode's (H, W, 3) bytes out, filtered
+    and finished on `device`."""
+    sums, counts, spp, rec = _denoise_inputs(sums, counts_or_spp, gbuffer)
+    h, w = sums.shape[0], sums.shape[1]
+    variance = _variance_input(variance, h, w)
+    rgb = np.zeros((h, w, 3), np.uint8)
+    gp = denoise_guided_params(**params)
+    _check(lib().rt_denoise_guided_frame_u8(sums.ctypes.data_as(_c_f), counts.ctypes.data_as(_c_i) if counts is not None else None,
+                                            spp, w, h, rec.ctypes.data_as(_c_f),
+                                            variance.ctypes.data_as(_c_f) if variance is not None else None, ctypes.byref(gp),
+                                            device, rgb.ctypes.data_as(_c_b)))
+    return rgb
+
+
+def denoise_guided_device(d_sums_ptr, d_counts_ptr, spp, width, height, d_gbuffer_ptr, d_out_ptr, stream_ptr=None,
+                          d_variance_ptr=None, d_out_variance_ptr=None, **params):
+    """rt_denoise_guided_device: the guided mode on the current HIP device (device pointers;
+    d_counts_ptr, d_variance_ptr, d_out_variance_ptr 0 / None: not given), asynchronous on the stream."""
+    gp = denoise_guided_params(**params)
+    _check(lib().rt_denoise_guided_device(ctypes.c_void_p(d_sums_ptr), ctypes.c_void_p(d_counts_ptr or 0), int(spp), width, height,
+                                          ctypes.c_void_p(d_gbuffer_ptr), ctypes.c_void_p(d_variance_ptr or 0), ctypes.byref(gp),
+                                          ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(d_out_variance_ptr or 0),
+                                          ctypes.c_void_p(stream_ptr or 0)))
 
 
 def tonemap_device(d_sum_ptr, width, height, spp, d_rgb_ptr, stream_ptr=None):

@@ -15,6 +15,8 @@
 //   rt_gbuffer_kernel       first-hit feature records from the pixel-centre rays (rt_gbuffer.h)
 //   rt_denoise_{prepare,level,resolve}_kernel  the edge-avoiding a-trous filter of a frame,
 //                           guided by those records (rt_denoise.h)
+//   rt_denoise_guided_{prepare,clamp,variance,given,level,varout}_kernel  its variance-guided
+//                           mode with a firefly clamp (rt_denoise_guided.h)
 // Every schedule writes the per-pixel float RGB sum (sample_canvas, scene.cpp:20,42) of the
 // owned rows; the bits do not depend on the kernel, the launch shape, the pixel order or the
 // partition.
@@ -55,6 +57,7 @@
 #include "rt_frame_plan.h"
 #include "rt_gbuffer.h"
 #include "rt_denoise.h"
+#include "rt_denoise_guided.h"
 
 using rtd::Counters;
 using rtd::DevScene;
@@ -2584,6 +2587,132 @@ __global__ void __launch_bounds__(256) rt_denoise_resolve_kernel(const float *__
     out[3 * p + 2] = m[2];
 }
 
+// rt_denoise_guided_device (include/rt_hw.h, rt_denoise_guided.h): the variance-guided mode.  The
+// three packed words per pixel are rt_denoise_device's and the variance is a float of its own per
+// pixel; the clamp writes the other (L, kind) buffer, the variance kernel the first V buffer, and
+// each level reads one (L, kind) and V buffer and writes the other pair.  The windowed kernels use
+// the level kernel's 32 x 8 tile and stage it with a halo of REACH pixels in LDS wherever the halo is
+// smaller than the tile: the clamp (2: 36 x 12 pixels x 48 B, 20.3 KB), the variance estimate (3:
+// 38 x 14 x 48 B, 24.9 KB), the levels at strides 1 and 2 (2 and 4: 36 x 12 and 40 x 16 pixels x
+// 52 B, 21.9 and 32.5 KB); the levels at strides >= 4 read through L2.  Measured against plain
+// loads in all of them on the 1080p headline frame, two alternating runs each
+// (profiles/denoise_guided_passes.jsonl): 5 iterations 1.19 ms staged against
+// 1.60 ms plain.
+__global__ void __launch_bounds__(256) rt_denoise_guided_prepare_kernel(const float *__restrict__ sums,
+                                                                         const int32_t *__restrict__ counts, int spp, long long n,
+                                                                         const rtdn::Q *__restrict__ g, rtdn::Q *__restrict__ a,
+                                                                         rtdn::Q *__restrict__ nt, rtdn::Q *__restrict__ pp) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const rtdn::Q rec[4] = {g[4 * p], g[4 * p + 1], g[4 * p + 2], g[4 * p + 3]};
+    const float S[3] = {sums[3 * p], sums[3 * p + 1], sums[3 * p + 2]};
+    rtdn::Q qa, qn, qp;
+    rtdg::prepare_pixel(S, counts ? counts[p] : spp, rec, qa, qn, qp);
+    a[p] = qa;
+    nt[p] = qn;
+    pp[p] = qp;
+}
+
+struct DgTileSrc {
+    const rtdn::Q *A, *NT, *PP;   // LDS
+    const float *V;               // LDS (the level kernel only)
+    int x0, y0, tw;
+    __device__ __forceinline__ int at(int x, int y) const { return (y - y0) * tw + (x - x0); }
+    __device__ __forceinline__ rtdn::Q a(int x, int y) const { return A[at(x, y)]; }
+    __device__ __forceinline__ rtdn::Q nt(int x, int y) const { return NT[at(x, y)]; }
+    __device__ __forceinline__ rtdn::Q pp(int x, int y) const { return PP[at(x, y)]; }
+    __device__ __forceinline__ float v(int x, int y) const { return V[at(x, y)]; }
+};
+
+// Stages the tile at (tx, ty) with a halo of REACH pixels: slot k of tile[0..2] (and tv, where
+// v_in is given) is frame pixel (x0 + k % tw, y0 + k / tw).  A slot outside the frame is never
+// read: every window skips such a tap.
+template <int REACH>
+__device__ __forceinline__ void dg_stage(rtdn::Q (*tile)[(kDnTileW + 2 * REACH) * (kDnTileH + 2 * REACH)], float *tv,
+                                         const rtdn::Q *__restrict__ a_in, const rtdn::Q *__restrict__ nt,
+                                         const rtdn::Q *__restrict__ pp, const float *__restrict__ v_in, int x0, int y0, int W, int H) {
+    constexpr int tw = kDnTileW + 2 * REACH, th = kDnTileH + 2 * REACH;
+    for (int k = (int)threadIdx.x; k < tw * th; k += 256) {
+        const int gy = y0 + k / tw, gx = x0 + k % tw;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            const long long q = (long long)gy * W + gx;
+            tile[0][k] = a_in[q];
+            tile[1][k] = nt[q];
+            tile[2][k] = pp[q];
+            if (tv) tv[k] = v_in[q];
+        }
+    }
+    __syncthreads();
+}
+
+__global__ void __launch_bounds__(256) rt_denoise_guided_clamp_kernel(const rtdn::Q *__restrict__ a_in, const rtdn::Q *__restrict__ nt,
+                                                                       const rtdn::Q *__restrict__ pp, rtdn::Q *__restrict__ a_out,
+                                                                       int W, int H, int tiles_x, rtdg::Params dp) {
+    constexpr int reach = rtdg::kClampReach, tw = kDnTileW + 2 * reach, th = kDnTileH + 2 * reach;
+    const int ty = (int)(blockIdx.x / (unsigned)tiles_x), tx = (int)(blockIdx.x - (unsigned)ty * (unsigned)tiles_x);
+    const int lx = (int)threadIdx.x % kDnTileW, ly = (int)threadIdx.x / kDnTileW;
+    const int x = tx * kDnTileW + lx, y = ty * kDnTileH + ly;
+    __shared__ rtdn::Q tile[3][tw * th];
+    const int x0 = tx * kDnTileW - reach, y0 = ty * kDnTileH - reach;
+    dg_stage<reach>(tile, nullptr, a_in, nt, pp, nullptr, x0, y0, W, H);
+    if (x < W && y < H)
+        a_out[(long long)y * W + x] = rtdg::clamp_pixel(DgTileSrc{tile[0], tile[1], tile[2], nullptr, x0, y0, tw}, x, y, W, H, dp);
+}
+
+__global__ void __launch_bounds__(256) rt_denoise_guided_variance_kernel(const rtdn::Q *__restrict__ a_in,
+                                                                          const rtdn::Q *__restrict__ nt,
+                                                                          const rtdn::Q *__restrict__ pp, float *__restrict__ v_out,
+                                                                          int W, int H, int tiles_x, rtdg::Params dp) {
+    constexpr int reach = rtdg::kVarianceReach, tw = kDnTileW + 2 * reach, th = kDnTileH + 2 * reach;
+    const int ty = (int)(blockIdx.x / (unsigned)tiles_x), tx = (int)(blockIdx.x - (unsigned)ty * (unsigned)tiles_x);
+    const int lx = (int)threadIdx.x % kDnTileW, ly = (int)threadIdx.x / kDnTileW;
+    const int x = tx * kDnTileW + lx, y = ty * kDnTileH + ly;
+    __shared__ rtdn::Q tile[3][tw * th];
+    const int x0 = tx * kDnTileW - reach, y0 = ty * kDnTileH - reach;
+    dg_stage<reach>(tile, nullptr, a_in, nt, pp, nullptr, x0, y0, W, H);
+    if (x < W && y < H)
+        v_out[(long long)y * W + x] = rtdg::variance_pixel(DgTileSrc{tile[0], tile[1], tile[2], nullptr, x0, y0, tw}, x, y, W, H, dp);
+}
+
+// The caller's variance in place of the estimate.
+__global__ void __launch_bounds__(256) rt_denoise_guided_given_kernel(const rtdn::Q *__restrict__ a, const float *__restrict__ variance,
+                                                                       long long n, float *__restrict__ v_out) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) v_out[p] = rtdg::given_variance(rtm::f2u(a[p].w), variance[p]);
+}
+
+template <int STAGE>
+__global__ void __launch_bounds__(256) rt_denoise_guided_level_kernel(const rtdn::Q *__restrict__ a_in, const float *__restrict__ v_in,
+                                                                       const rtdn::Q *__restrict__ nt, const rtdn::Q *__restrict__ pp,
+                                                                       rtdn::Q *__restrict__ a_out, float *__restrict__ v_out, int W,
+                                                                       int H, int tiles_x, rtdg::Level lv) {
+    const int ty = (int)(blockIdx.x / (unsigned)tiles_x), tx = (int)(blockIdx.x - (unsigned)ty * (unsigned)tiles_x);
+    const int lx = (int)threadIdx.x % kDnTileW, ly = (int)threadIdx.x / kDnTileW;
+    const int x = tx * kDnTileW + lx, y = ty * kDnTileH + ly;
+    rtdg::Pixel r;
+    if constexpr (STAGE > 0) {
+        constexpr int reach = 2 * STAGE, tw = kDnTileW + 2 * reach, th = kDnTileH + 2 * reach;
+        __shared__ rtdn::Q tile[3][tw * th];
+        __shared__ float tv[tw * th];
+        const int x0 = tx * kDnTileW - reach, y0 = ty * kDnTileH - reach;
+        dg_stage<reach>(tile, tv, a_in, nt, pp, v_in, x0, y0, W, H);
+        if (x >= W || y >= H) return;
+        r = rtdg::level_pixel(DgTileSrc{tile[0], tile[1], tile[2], tv, x0, y0, tw}, x, y, W, H, lv);
+    } else {
+        if (x >= W || y >= H) return;
+        r = rtdg::level_pixel(rtdg::PlainSrc{a_in, nt, pp, v_in, W}, x, y, W, H, lv);
+    }
+    a_out[(long long)y * W + x] = r.a;
+    v_out[(long long)y * W + x] = r.v;
+}
+
+// a == nullptr (iterations = 0): zeros.
+__global__ void __launch_bounds__(256) rt_denoise_guided_varout_kernel(const rtdn::Q *__restrict__ a, const float *__restrict__ v,
+                                                                        long long n, float *__restrict__ out) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) out[p] = a ? rtdg::resolve_variance(a[p], v[p]) : 0.f;
+}
+
 namespace {
 
 // The G-buffer of a shard into device memory (the current device is the scene copy's).
@@ -2631,10 +2760,146 @@ int denoise_launch(void **ws, size_t *ws_bytes, const float *d_sums, const int32
     return RT_OK;
 }
 
-// rt_denoise_device's scratch, per device, from the first call on (only grows).
+// The variance-guided mode on the current device, on the same scratch rules; 72 B per pixel:
+// denoise_launch's 64 and the two variance buffers (d_var / d_out_var: the caller's variance, the
+// filtered variance out, or NULL).
+int denoise_guided_launch(void **ws, size_t *ws_bytes, const float *d_sums, const int32_t *d_counts, int spp, int W, int H,
+                          const float *d_g, const float *d_var, const rtdg::Params &dp, float *d_out, float *d_out_var,
+                          hipStream_t stream) {
+    const long long n = (long long)W * H;
+    const dim3 flat((unsigned)((n + 255) / 256));
+    const rtdn::Q *g = (const rtdn::Q *)d_g;
+    if (dp.iterations == 0) {
+        hipLaunchKernelGGL(rt_denoise_resolve_kernel, flat, dim3(256), 0, stream, d_sums, d_counts, spp, n, g,
+                           (const rtdn::Q *)nullptr, d_out);
+        if (d_out_var)
+            hipLaunchKernelGGL(rt_denoise_guided_varout_kernel, flat, dim3(256), 0, stream, (const rtdn::Q *)nullptr,
+                               (const float *)nullptr, n, d_out_var);
+        HIP_TRY(hipGetLastError());
+        return RT_OK;
+    }
+    HIP_TRY(grow(ws, ws_bytes, (size_t)n * (4 * sizeof(rtdn::Q) + 2 * sizeof(float))));
+    rtdn::Q *a[2] = {(rtdn::Q *)*ws, (rtdn::Q *)*ws + n};
+    rtdn::Q *nt = (rtdn::Q *)*ws + 2 * n, *pp = (rtdn::Q *)*ws + 3 * n;
+    float *v[2] = {(float *)((rtdn::Q *)*ws + 4 * n), (float *)((rtdn::Q *)*ws + 4 * n) + n};
+    hipLaunchKernelGGL(rt_denoise_guided_prepare_kernel, flat, dim3(256), 0, stream, d_sums, d_counts, spp, n, g, a[0], nt, pp);
+    const int tiles_x = (W + kDnTileW - 1) / kDnTileW, tiles_y = (H + kDnTileH - 1) / kDnTileH;
+    const dim3 tiles((unsigned)((long long)tiles_x * tiles_y));
+    int cur = 0;   // the buffers that hold (L, kind) and V
+    if (!(dp.firefly < 0.f)) {
+        hipLaunchKernelGGL(rt_denoise_guided_clamp_kernel, tiles, dim3(256), 0, stream, (const rtdn::Q *)a[0], (const rtdn::Q *)nt,
+                           (const rtdn::Q *)pp, a[1], W, H, tiles_x, dp);
+        cur = 1;
+    }
+    if (d_var)
+        hipLaunchKernelGGL(rt_denoise_guided_given_kernel, flat, dim3(256), 0, stream, (const rtdn::Q *)a[cur], d_var, n, v[cur]);
+    else
+        hipLaunchKernelGGL(rt_denoise_guided_variance_kernel, tiles, dim3(256), 0, stream, (const rtdn::Q *)a[cur], (const rtdn::Q *)nt,
+                           (const rtdn::Q *)pp, v[cur], W, H, tiles_x, dp);
+    for (int k = 0; k < dp.iterations; ++k, cur ^= 1) {
+        const rtdg::Level lv = rtdg::level_of(dp, k);
+        const rtdn::Q *in = a[cur], *cnt = nt, *cpp = pp;
+        const float *vin = v[cur];
+        if (lv.stride == 1)
+            hipLaunchKernelGGL(rt_denoise_guided_level_kernel<1>, tiles, dim3(256), 0, stream, in, vin, cnt, cpp, a[cur ^ 1], v[cur ^ 1],
+                               W, H, tiles_x, lv);
+        else if (lv.stride == 2)
+            hipLaunchKernelGGL(rt_denoise_guided_level_kernel<2>, tiles, dim3(256), 0, stream, in, vin, cnt, cpp, a[cur ^ 1], v[cur ^ 1],
+                               W, H, tiles_x, lv);
+        else
+            hipLaunchKernelGGL(rt_denoise_guided_level_kernel<0>, tiles, dim3(256), 0, stream, in, vin, cnt, cpp, a[cur ^ 1], v[cur ^ 1],
+                               W, H, tiles_x, lv);
+    }
+    hipLaunchKernelGGL(rt_denoise_resolve_kernel, flat, dim3(256), 0, stream, d_sums, d_counts, spp, n, g, (const rtdn::Q *)a[cur],
+                       d_out);
+    if (d_out_var)
+        hipLaunchKernelGGL(rt_denoise_guided_varout_kernel, flat, dim3(256), 0, stream, (const rtdn::Q *)a[cur], (const float *)v[cur],
+                           n, d_out_var);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// rt_denoise_device's and rt_denoise_guided_device's scratch, per device, from the first call on
+// (only grows).
 std::mutex g_dn_mu;
 void *g_dn_ws[kRtMaxDevices] = {};
 size_t g_dn_ws_bytes[kRtMaxDevices] = {};
+
+// rt_accum_frame_u8_denoised / rt_accum_frame_u8_guided: the accumulator's frame through a filter
+// in front of the finish.  check(spp, W, H) resolves the parameters before anything is allocated
+// or launched; launch(counts, spp, W, H) filters a->sums into a->dn_mean on a->stream.
+template <class Check, class Launch>
+int accum_filtered_frame(rt_accum *a, const std::string &who, const char *frame_entry, uint8_t *out_rgb, Check check, Launch launch) {
+    if (!a || !out_rgb) return rt_fail(RT_ERR_ARG, who + ": NULL argument");
+    if (a->p.world != 1)
+        return rt_fail(RT_ERR_ARG, who + ": the filter needs the whole frame (world = 1); gather the shards' "
+                                         "sums and G-buffers and use " + frame_entry);
+    if (a->samples < 1) return rt_fail(RT_ERR_ARG, who + ": no samples yet");
+    if (a->n_pixels == 0) return RT_OK;
+    DeviceGuard guard(a->p.device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    const int W = a->scene->width, H = a->rows;
+    // the parameters first: a refused call allocates and launches nothing
+    const int spp = a->samples;
+    if (int rc = check(spp, W, H)) return rc;
+    if (int rc = accum_buffer(a->gbuf, (size_t)a->n_pixels * rtd::kGbufferQuads)) return rc;
+    if (int rc = accum_buffer(a->dn_mean, (size_t)a->n_pixels * 3)) return rc;
+    if (int rc = accum_buffer(a->rgb, (size_t)a->n_pixels * 3)) return rc;
+    if (!a->gbuf_ready) {   // (set only once the records' launch was accepted: a call that fails before keeps it unset)
+        if (int rc = gbuffer_launch(a->scene->dev[a->p.device], a->geom, a->gbuf, a->stream)) return rc;
+        a->gbuf_ready = true;
+    }
+    const int32_t *counts = nullptr;
+    if (!accum_uniform(a)) {   // every pixel divided by its own count
+        if (int rc = accum_buffer(a->counts, (size_t)a->n_pixels)) return rc;
+        if (int rc = accum_counts_launch(a, a->counts, a->stream)) return rc;
+        counts = a->counts;
+    }
+    if (int rc = launch(counts, spp, W, H)) return rc;
+    if (int rc = rt_tonemap_u8_device(a->dn_mean, W, H, 1, a->rgb, a->stream)) return rc;
+    if (int rc = accum_wait(a)) return rc;
+    HIP_TRY(hipMemcpy(out_rgb, a->rgb, (size_t)a->n_pixels * 3, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// rt_denoise_frame_u8 / rt_denoise_guided_frame_u8: host arrays to `device`, filtered there by
+// launch(d_sums, d_counts, d_gbuffer, d_variance, d_mean) under the device cache's lock, finished
+// at spp = 1, the bytes copied back.  variance may be NULL.
+template <class Launch>
+int denoise_frame_bytes(const std::string &who, const float *sums, const int32_t *counts, int32_t width, int32_t height,
+                        const float *gbuffer, const float *variance, int32_t device, uint8_t *out_rgb, Launch launch) {
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev || device >= kRtMaxDevices)
+        return rt_fail(RT_ERR_DEVICE, "no HIP device " + std::to_string(device));
+    DeviceGuard guard(device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    // one staging allocation: sums, mean, G-buffer, counts, variance, bytes (each part 256-byte aligned)
+    const size_t n = (size_t)width * height;
+    const size_t o_mean = rtp::align_up(n * 12), o_g = o_mean + rtp::align_up(n * 12), o_cnt = o_g + n * 64,
+                 o_var = o_cnt + rtp::align_up(n * 4), o_rgb = o_var + (variance ? rtp::align_up(n * 4) : 0), total = o_rgb + n * 3;
+    uint8_t *buf = nullptr;
+    HIP_TRY(hipMalloc((void **)&buf, total));
+    int32_t *d_counts = counts ? (int32_t *)(buf + o_cnt) : nullptr;
+    float *d_var = variance ? (float *)(buf + o_var) : nullptr;
+    hipError_t e = hipMemcpy(buf, sums, n * 12, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + o_g, gbuffer, n * 64, hipMemcpyHostToDevice);
+    if (e == hipSuccess && counts) e = hipMemcpy(d_counts, counts, n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && variance) e = hipMemcpy(d_var, variance, n * 4, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? RT_OK : rt_fail(RT_ERR_DEVICE, who + " copy: " + hipGetErrorString(e));
+    if (rc == RT_OK) {
+        std::lock_guard<std::mutex> lock(g_dn_mu);
+        rc = launch((const float *)buf, (const int32_t *)d_counts, (const float *)(buf + o_g), (const float *)d_var,
+                    (float *)(buf + o_mean));
+    }
+    if (rc == RT_OK) rc = rt_tonemap_u8_device((const float *)(buf + o_mean), width, height, 1, buf + o_rgb, nullptr);
+    if (rc == RT_OK) {
+        e = hipMemcpy(out_rgb, buf + o_rgb, n * 3, hipMemcpyDeviceToHost);   // (waits for the default stream)
+        if (e != hipSuccess) rc = rt_fail(RT_ERR_DEVICE, who + " copy: " + hipGetErrorString(e));
+    }
+    (void)hipFree(buf);
+    return rc;
+}
 
 }  // namespace
 
@@ -2690,73 +2955,66 @@ int rt_denoise_frame_u8(const float *sums, const int32_t *counts, int32_t spp, i
     if (!out_rgb) return rt_fail(RT_ERR_ARG, "rt_denoise_frame_u8: NULL argument");
     rtdn::Params dp;
     if (int rc = rt_denoise_check("rt_denoise_frame_u8", sums, counts, spp, width, height, gbuffer, params, sums, &dp)) return rc;
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev || device >= kRtMaxDevices)
-        return rt_fail(RT_ERR_DEVICE, "no HIP device " + std::to_string(device));
-    DeviceGuard guard(device);
-    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
-    // one staging allocation: sums, mean, G-buffer, counts, bytes (each part 256-byte aligned)
-    const size_t n = (size_t)width * height;
-    const size_t o_mean = rtp::align_up(n * 12), o_g = o_mean + rtp::align_up(n * 12), o_cnt = o_g + n * 64,
-                 o_rgb = o_cnt + rtp::align_up(n * 4), total = o_rgb + n * 3;
-    uint8_t *buf = nullptr;
-    HIP_TRY(hipMalloc((void **)&buf, total));
-    int32_t *d_counts = counts ? (int32_t *)(buf + o_cnt) : nullptr;
-    hipError_t e = hipMemcpy(buf, sums, n * 12, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(buf + o_g, gbuffer, n * 64, hipMemcpyHostToDevice);
-    if (e == hipSuccess && counts) e = hipMemcpy(d_counts, counts, n * 4, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? RT_OK : rt_fail(RT_ERR_DEVICE, std::string("rt_denoise_frame_u8 copy: ") + hipGetErrorString(e));
-    if (rc == RT_OK) {
-        std::lock_guard<std::mutex> lock(g_dn_mu);
-        rc = denoise_launch(&g_dn_ws[device], &g_dn_ws_bytes[device], (const float *)buf, d_counts, spp, width, height,
-                            (const float *)(buf + o_g), dp, (float *)(buf + o_mean), nullptr);
-    }
-    if (rc == RT_OK) rc = rt_tonemap_u8_device((const float *)(buf + o_mean), width, height, 1, buf + o_rgb, nullptr);
-    if (rc == RT_OK) {
-        e = hipMemcpy(out_rgb, buf + o_rgb, n * 3, hipMemcpyDeviceToHost);   // (waits for the default stream)
-        if (e != hipSuccess) rc = rt_fail(RT_ERR_DEVICE, std::string("rt_denoise_frame_u8 copy: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(buf);
-    return rc;
+    return denoise_frame_bytes("rt_denoise_frame_u8", sums, counts, width, height, gbuffer, nullptr, device, out_rgb,
+                               [&](const float *d_sums, const int32_t *d_counts, const float *d_g, const float *, float *d_mean) {
+                                   return denoise_launch(&g_dn_ws[device], &g_dn_ws_bytes[device], d_sums, d_counts, spp, width, height,
+                                                         d_g, dp, d_mean, nullptr);
+                               });
 }
 
 int rt_accum_frame_u8_denoised(rt_accum *a, const rt_denoise_params *params, uint8_t *out_rgb) {
-    if (!a || !out_rgb) return rt_fail(RT_ERR_ARG, "rt_accum_frame_u8_denoised: NULL argument");
-    if (a->p.world != 1)
-        return rt_fail(RT_ERR_ARG, "rt_accum_frame_u8_denoised: the filter needs the whole frame (world = 1); gather the shards' "
-                                   "sums and G-buffers and use rt_denoise_device");
-    if (a->samples < 1) return rt_fail(RT_ERR_ARG, "rt_accum_frame_u8_denoised: no samples yet");
-    if (a->n_pixels == 0) return RT_OK;
-    DeviceGuard guard(a->p.device);
-    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
-    const int W = a->scene->width, H = a->rows;
-    // the parameters first: a refused call allocates and launches nothing (the check only asks
-    // that its pointers are not NULL, and the sums exist)
     rtdn::Params dp;
-    const int spp = a->samples;
-    if (int rc = rt_denoise_check("rt_accum_frame_u8_denoised", a->sums, nullptr, spp, W, H, a->sums, params, a->sums, &dp))
+    return accum_filtered_frame(
+        a, "rt_accum_frame_u8_denoised", "rt_denoise_device", out_rgb,
+        [&](int spp, int W, int H) {   // (the check only asks that its pointers are not NULL, and the sums exist)
+            return rt_denoise_check("rt_accum_frame_u8_denoised", a->sums, nullptr, spp, W, H, a->sums, params, a->sums, &dp);
+        },
+        [&](const int32_t *counts, int spp, int W, int H) {
+            return denoise_launch(&a->dn_ws, &a->dn_ws_bytes, a->sums, counts, spp, W, H, (const float *)a->gbuf, dp, a->dn_mean,
+                                  a->stream);
+        });
+}
+
+int rt_denoise_guided_device(const float *d_sums, const int32_t *d_counts, int32_t spp, int32_t width, int32_t height,
+                             const float *d_gbuffer, const float *d_variance, const rt_denoise_guided_params *params,
+                             float *d_out_mean, float *d_out_variance, void *stream) {
+    rtdg::Params dp;
+    if (int rc = rt_denoise_guided_check("rt_denoise_guided_device", d_sums, d_counts, spp, width, height, d_gbuffer, params,
+                                         d_out_mean, &dp))
         return rc;
-    if (int rc = accum_buffer(a->gbuf, (size_t)a->n_pixels * rtd::kGbufferQuads)) return rc;
-    if (int rc = accum_buffer(a->dn_mean, (size_t)a->n_pixels * 3)) return rc;
-    if (int rc = accum_buffer(a->rgb, (size_t)a->n_pixels * 3)) return rc;
-    if (!a->gbuf_ready) {   // (set only once the records' launch was accepted: a call that fails before keeps it unset)
-        if (int rc = gbuffer_launch(a->scene->dev[a->p.device], a->geom, a->gbuf, a->stream)) return rc;
-        a->gbuf_ready = true;
-    }
-    const int32_t *counts = nullptr;
-    if (!accum_uniform(a)) {   // every pixel divided by its own count
-        if (int rc = accum_buffer(a->counts, (size_t)a->n_pixels)) return rc;
-        if (int rc = accum_counts_launch(a, a->counts, a->stream)) return rc;
-        counts = a->counts;
-    }
-    if (int rc = denoise_launch(&a->dn_ws, &a->dn_ws_bytes, a->sums, counts, spp, W, H, (const float *)a->gbuf, dp, a->dn_mean,
-                                a->stream))
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= kRtMaxDevices) return rt_fail(RT_ERR_DEVICE, "rt_denoise_guided_device: device id");
+    std::lock_guard<std::mutex> lock(g_dn_mu);
+    return denoise_guided_launch(&g_dn_ws[dev], &g_dn_ws_bytes[dev], d_sums, d_counts, spp, width, height, d_gbuffer, d_variance, dp,
+                                 d_out_mean, d_out_variance, (hipStream_t)stream);
+}
+
+int rt_denoise_guided_frame_u8(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
+                               const float *gbuffer, const float *variance, const rt_denoise_guided_params *params, int32_t device,
+                               uint8_t *out_rgb) {
+    if (!out_rgb) return rt_fail(RT_ERR_ARG, "rt_denoise_guided_frame_u8: NULL argument");
+    rtdg::Params dp;
+    if (int rc = rt_denoise_guided_check("rt_denoise_guided_frame_u8", sums, counts, spp, width, height, gbuffer, params, sums, &dp))
         return rc;
-    if (int rc = rt_tonemap_u8_device(a->dn_mean, W, H, 1, a->rgb, a->stream)) return rc;
-    if (int rc = accum_wait(a)) return rc;
-    HIP_TRY(hipMemcpy(out_rgb, a->rgb, (size_t)a->n_pixels * 3, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return denoise_frame_bytes("rt_denoise_guided_frame_u8", sums, counts, width, height, gbuffer, variance, device, out_rgb,
+                               [&](const float *d_sums, const int32_t *d_counts, const float *d_g, const float *d_var, float *d_mean) {
+                                   return denoise_guided_launch(&g_dn_ws[device], &g_dn_ws_bytes[device], d_sums, d_counts, spp, width,
+                                                                height, d_g, d_var, dp, d_mean, nullptr, nullptr);
+                               });
+}
+
+int rt_accum_frame_u8_guided(rt_accum *a, const rt_denoise_guided_params *params, uint8_t *out_rgb) {
+    rtdg::Params dp;
+    return accum_filtered_frame(
+        a, "rt_accum_frame_u8_guided", "rt_denoise_guided_device", out_rgb,
+        [&](int spp, int W, int H) {
+            return rt_denoise_guided_check("rt_accum_frame_u8_guided", a->sums, nullptr, spp, W, H, a->sums, params, a->sums, &dp);
+        },
+        [&](const int32_t *counts, int spp, int W, int H) {
+            return denoise_guided_launch(&a->dn_ws, &a->dn_ws_bytes, a->sums, counts, spp, W, H, (const float *)a->gbuf, nullptr, dp,
+                                         a->dn_mean, nullptr, a->stream);
+        });
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "rt_denoise.h"
+#include "rt_denoise_guided.h"
 #include "rt_json.h"
 #include "rt_scene.h"
 #include "rt_select.h"
@@ -893,6 +894,65 @@ int rt_denoise(const float *sums, const int32_t *counts, int32_t spp, int32_t wi
     return RT_OK;
 }
 
+// The variance-guided mode on the host (rt_denoise_guided.h is its text): prepare, the firefly
+// clamp, the variance (the caller's or the spatial estimate), `iterations` levels between two
+// buffers of (L, kind) and V, resolve.
+int rt_denoise_guided(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height, const float *gbuffer,
+                      const float *variance, const rt_denoise_guided_params *params, float *out_mean, float *out_variance) {
+    rtdg::Params dp;
+    if (int rc = rt_denoise_guided_check("rt_denoise_guided", sums, counts, spp, width, height, gbuffer, params, out_mean, &dp))
+        return rc;
+    const int64_t n = (int64_t)width * height;
+    auto count_of = [&](int64_t p) { return counts ? counts[p] : spp; };
+    if (dp.iterations == 0) {
+        for (int64_t p = 0; p < n; ++p) {
+            const float rn = rtdn::mean_normalizer(count_of(p));
+            for (int c = 0; c < 3; ++c) out_mean[3 * p + c] = sums[3 * p + c] * rn;
+            if (out_variance) out_variance[p] = 0.f;
+        }
+        return RT_OK;
+    }
+    std::vector<rtdn::Q> g((size_t)n * 4), a[2], nt((size_t)n), pp((size_t)n);
+    std::vector<float> v[2];
+    std::memcpy(g.data(), gbuffer, (size_t)n * 64);
+    for (int i = 0; i < 2; ++i) {
+        a[i].resize((size_t)n);
+        v[i].assign((size_t)n, 0.f);
+    }
+    for (int64_t p = 0; p < n; ++p) rtdg::prepare_pixel(sums + 3 * p, count_of(p), &g[4 * p], a[0][p], nt[p], pp[p]);
+    int cur = 0;   // the buffer that holds (L, kind)
+    if (!(dp.firefly < 0.f)) {
+        const rtdg::PlainSrc src{a[0].data(), nt.data(), pp.data(), nullptr, width};
+        for (int y = 0; y < height; ++y)
+            for (int x = 0; x < width; ++x) a[1][(int64_t)y * width + x] = rtdg::clamp_pixel(src, x, y, width, height, dp);
+        cur = 1;
+    }
+    {
+        const rtdg::PlainSrc src{a[cur].data(), nt.data(), pp.data(), nullptr, width};
+        for (int y = 0; y < height; ++y)
+            for (int x = 0; x < width; ++x) {
+                const int64_t p = (int64_t)y * width + x;
+                v[cur][p] = variance ? rtdg::given_variance(rtm::f2u(a[cur][p].w), variance[p])
+                                     : rtdg::variance_pixel(src, x, y, width, height, dp);
+            }
+    }
+    for (int k = 0; k < dp.iterations; ++k, cur ^= 1) {
+        const rtdg::Level lv = rtdg::level_of(dp, k);
+        const rtdg::PlainSrc src{a[cur].data(), nt.data(), pp.data(), v[cur].data(), width};
+        for (int y = 0; y < height; ++y)
+            for (int x = 0; x < width; ++x) {
+                const rtdg::Pixel r = rtdg::level_pixel(src, x, y, width, height, lv);
+                a[cur ^ 1][(int64_t)y * width + x] = r.a;
+                v[cur ^ 1][(int64_t)y * width + x] = r.v;
+            }
+    }
+    for (int64_t p = 0; p < n; ++p) {
+        rtdn::resolve_pixel(sums + 3 * p, count_of(p), &g[4 * p], a[cur][p], out_mean + 3 * p);
+        if (out_variance) out_variance[p] = rtdg::resolve_variance(a[cur][p], v[cur][p]);
+    }
+    return RT_OK;
+}
+
 int rt_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t height) {
     if (!path || !rgb || width <= 0 || height <= 0) return rt_fail(RT_ERR_ARG, "rt_write_ppm: bad argument");
     std::FILE *f = std::fopen(path, "wb");
@@ -921,6 +981,22 @@ int rt_denoise_check(const char *who, const float *sums, const int32_t *counts, 
     if (rtdn::resolve_params(p.iterations, p.sigma_color, p.sigma_plane, p.normal_power_log2, *resolved))
         return rt_fail(RT_ERR_ARG, w + ": iterations above " + std::to_string(rtdn::kMaxIterations) + ", normal_power_log2 above " +
                                        std::to_string(rtdn::kMaxNormalPowerLog2) + " or a non-finite sigma");
+    return RT_OK;
+}
+
+int rt_denoise_guided_check(const char *who, const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
+                            const float *gbuffer, const rt_denoise_guided_params *params, const float *out_mean,
+                            rtdg::Params *resolved) {
+    const std::string w = who;
+    if (!sums || !gbuffer || !out_mean) return rt_fail(RT_ERR_ARG, w + ": NULL argument");
+    if (width <= 0 || height <= 0) return rt_fail(RT_ERR_ARG, w + ": bad frame size");
+    if (!counts && spp < 1) return rt_fail(RT_ERR_ARG, w + ": without counts, spp must be at least 1");
+    if ((int64_t)width * height > INT32_MAX) return rt_fail(RT_ERR_LIMIT, w + ": frames above 2^31 pixels are not supported");
+    const rt_denoise_guided_params none{-1, 0.f, 0.f, 0, 0.f};
+    const rt_denoise_guided_params &p = params ? *params : none;
+    if (rtdg::resolve_params(p.iterations, p.sigma_var, p.sigma_plane, p.normal_power_log2, p.firefly, *resolved))
+        return rt_fail(RT_ERR_ARG, w + ": iterations above " + std::to_string(rtdn::kMaxIterations) + ", normal_power_log2 above " +
+                                       std::to_string(rtdn::kMaxNormalPowerLog2) + " or a non-finite sigma or firefly factor");
     return RT_OK;
 }
 

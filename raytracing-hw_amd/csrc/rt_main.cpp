@@ -36,6 +36,10 @@
 //                       frame's G-buffer, rendered once on device 0, are filtered on device 0
 //                       (rt_denoise_frame_u8).  k = 0 is refused here, although the library takes
 //                       iterations = 0 (the unfiltered mean): it would be the run with RT_DENOISE unset.
+//   RT_DENOISE_GUIDED=k the same frames through the filter's variance-guided mode with its firefly
+//                       clamp instead (rt_accum_frame_u8_guided, rt_denoise_guided_frame_u8; k
+//                       iterations, 1..6, the other parameters at their defaults).  Setting both
+//                       variables is an error, reported before anything is rendered.
 //   RT_AOV_OUT=pfx      the first-hit features of the frame: pfx.normal.ppm (N * 0.5 + 0.5),
 //                       pfx.albedo.ppm (the linear base colour) and pfx.depth.pgm (binary 16-bit PGM,
 //                       big-endian, hit distance / the frame's largest; a miss is 0).
@@ -65,11 +69,21 @@ static std::vector<float> frame_gbuffer(rt_scene *scene, int width, int height) 
     return g;
 }
 
-// RT_DENOISE: the filter's parameters (k iterations, the rest at their defaults), or none.
+// RT_DENOISE / RT_DENOISE_GUIDED: the filter's parameters (k iterations, the rest at their
+// defaults), or none.
 struct Denoise {
-    bool on = false;
+    bool on = false, guided = false;
     rt_denoise_params params{-1, 0.f, 0.f, 0};
+    rt_denoise_guided_params guided_params{-1, 0.f, 0.f, 0, 0.f};
     std::vector<float> gbuffer;   // the frame's, rendered at the first frame that needs it
+
+    int accum_frame(rt_accum *acc, uint8_t *rgb) const {
+        return guided ? rt_accum_frame_u8_guided(acc, &guided_params, rgb) : rt_accum_frame_u8_denoised(acc, &params, rgb);
+    }
+    int frame(const float *sums, const int32_t *counts, int spp, int width, int height, uint8_t *rgb) const {
+        return guided ? rt_denoise_guided_frame_u8(sums, counts, spp, width, height, gbuffer.data(), nullptr, &guided_params, 0, rgb)
+                      : rt_denoise_frame_u8(sums, counts, spp, width, height, gbuffer.data(), &params, 0, rgb);
+    }
 };
 
 static void write_file(const std::string &path, const char *header, const std::vector<uint8_t> &bytes) {
@@ -160,7 +174,7 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
     std::vector<int32_t> counts, cshard;
     auto write_frame = [&]() {
         if (dn && dn->on && n == 1) {   // the accumulator owns the whole frame: filtered where it lives
-            check(rt_accum_frame_u8_denoised(acc[0], &dn->params, rgb.data()));
+            check(dn->accum_frame(acc[0], rgb.data()));
             check(rt_write_ppm(output.c_str(), rgb.data(), width, height));
             return;
         }
@@ -183,7 +197,7 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
             }
             // (after rt_accum_sums has waited for every shard's pass: nothing else runs on device 0)
             if (dn->gbuffer.empty()) dn->gbuffer = frame_gbuffer(scene, width, height);
-            check(rt_denoise_frame_u8(sums.data(), counts.data(), 0, width, height, dn->gbuffer.data(), &dn->params, 0, rgb.data()));
+            check(dn->frame(sums.data(), counts.data(), 0, width, height, rgb.data()));
             check(rt_write_ppm(output.c_str(), rgb.data(), width, height));
             return;
         }
@@ -304,6 +318,20 @@ int main(int argc, char *argv[]) {
             return 1;
         }
     }
+    if (const char *dg_env = std::getenv("RT_DENOISE_GUIDED"); dg_env && *dg_env) {
+        if (dn.on) {
+            std::cerr << "rt_solution: RT_DENOISE and RT_DENOISE_GUIDED are both set; choose one filter" << std::endl;
+            rt_scene_free(scene);
+            return 1;
+        }
+        dn.on = dn.guided = true;
+        dn.guided_params.iterations = std::atoi(dg_env);
+        if (dn.guided_params.iterations < 1 || dn.guided_params.iterations > 6) {
+            std::cerr << "rt_solution: RT_DENOISE_GUIDED must be 1..6" << std::endl;
+            rt_scene_free(scene);
+            return 1;
+        }
+    }
     const char *aov_out = std::getenv("RT_AOV_OUT");
     const char *fast_env = std::getenv("RT_FAST");
     const int fast_chunk = fast_env && *fast_env ? std::atoi(fast_env) : 0;
@@ -344,7 +372,7 @@ int main(int argc, char *argv[]) {
         std::vector<float> sums((size_t)width * height * 3);
         check(rt_render_frame(scene, &p, n_gpus, nullptr, nullptr, sums.data(), &st));
         dn.gbuffer = frame_gbuffer(scene, width, height);
-        check(rt_denoise_frame_u8(sums.data(), nullptr, samples, width, height, dn.gbuffer.data(), &dn.params, 0, rgb.data()));
+        check(dn.frame(sums.data(), nullptr, samples, width, height, rgb.data()));
     } else {
         check(rt_render_frame(scene, &p, n_gpus, nullptr, rgb.data(), nullptr, &st));
     }
