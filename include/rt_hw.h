@@ -612,7 +612,12 @@ int rt_device_synchronize(void);
  * in equal-t ties, NaN and infinite vertices (four launches); which 3: the traversal's
  * root-free cull (rt_wavefront.h far_gt and kFarMax2) against the device's sqrtf(x) > acc over
  * 2^24 generated pairs around the rounding boundary, the special values and the floats
- * around the 1e9 constant; *mismatches = values (cases) that differ (0 = exact). */
+ * around the 1e9 constant; which 4: the material records of every uploaded scene against the
+ * scene's own tables; which 5: whole closest-hit queries of 16,384 hashed rays on every
+ * uploaded scene through the cooperative step (one and two frames popped per step; 12 and 4
+ * stack frames in LDS) against the per-lane step loop (t, triangle, local
+ * best, AABB and triangle counts; a query that does not end within 4 x (nodes + triangles) +
+ * 64 steps is a mismatch); *mismatches = values (cases) that differ (0 = exact). */
 int rt_device_selfcheck(int32_t which, uint64_t *mismatches);
 
 #ifdef __cplusplus

@@ -166,6 +166,20 @@ constexpr bool kPlainFarDist2 = RT_PLAIN_FAR_DIST2 != 0, kSpecFarDist2 = RT_SPEC
 #endif
 constexpr int kPlainShade = RT_PLAIN_SHADE_GATHER ? rtd::SHADE_GATHER_HOLD : rtd::SHADE_TABLES,
               kSpecShade = RT_SPEC_SHADE_GATHER ? rtd::SHADE_GATHER_HOLD : rtd::SHADE_TABLES;
+// Frames a coop step pops at most (rt_wavefront.h RT_MAX_POPS, trav_pop MAXP), per kernel and by
+// the rule above.  One frame: the return is a single stack read without a loop, and the pop
+// block, which runs in 98% of the traversal iterations for 8 of a wave's 64 lanes, is about half
+// as long.  The runahead kernel's 8-way shards gain too, but their slowest shard
+// misses the margin (3.0 ms against three times a spread of 1.6), so it keeps two frames.  The
+// counting, fast-mode and light-split instantiations and the wavefront kernel were not measured
+// and keep RT_MAX_POPS.
+#ifndef RT_PLAIN_MAX_POPS
+#define RT_PLAIN_MAX_POPS 1
+#endif
+#ifndef RT_SPEC_MAX_POPS
+#define RT_SPEC_MAX_POPS 2
+#endif
+constexpr int kMaxPopsPlain = RT_PLAIN_MAX_POPS, kMaxPopsSpec = RT_SPEC_MAX_POPS;
 // Leaf rounds per coop step (rt_wavefront.h trav_step_coop round_min): a further round
 // while at least this many leaf lanes are unserved.  Plain kernel: 8 (sponza 1080p 1292 ->
 // 1278 ms against one round per step).  The runahead kernel's depends on the scene
@@ -436,6 +450,7 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
     unsigned long long pf[7] = {0, 0, 0, 0, 0, 0, 0};
     if (threadIdx.x < 8) rt_prof_lds[threadIdx.x] = 0;
     if (threadIdx.x < 16) rtd::spec_prof_lds[threadIdx.x] = 0;
+    if (threadIdx.x < 4 * rtd::kPopProfN) rtd::pop_prof_lds[threadIdx.x / rtd::kPopProfN][threadIdx.x % rtd::kPopProfN] = 0;
     if ((threadIdx.x & 63) == 0) rtd::spec_wave_t0_lds[threadIdx.x >> 6] = wall_clock64();
     __syncthreads();
     long long tp = clock64();
@@ -618,7 +633,8 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
             do {
                 if (rtd::trav_step_coop<COUNT, kSpec ? kCoopLeavesSpec : kCoopLeavesPlain, kSpec && kSpecMaskLoad,
                                         kSpec ? rtd::kLeafDefer : (COUNT ? 0 : rtd::kLeafDeferPlain),
-                                        kSpec ? kSpecFarDist2 : kPlainFarDist2>(
+                                        kSpec ? kSpecFarDist2 : kPlainFarDist2,
+                                        kSpec ? kMaxPopsSpec : (COUNT ? rtd::kMaxPops : kMaxPopsPlain)>(
                         sc, L.r, L.T, S, nodes, cnt, L.state == rtd::M_TRAV, kSpec ? st.round_min : kCoopRoundMinPlain,
                         rtd::NoHook{}, &leaf_defer))
                     L.state = rtd::M_READY;
@@ -687,6 +703,9 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
     __syncthreads();
     if (threadIdx.x < 8) atomicAdd(&g_mega_seg[threadIdx.x], rt_prof_lds[threadIdx.x]);
     if (threadIdx.x < 16) atomicAdd(&rtd::g_spec_prof[threadIdx.x], rtd::spec_prof_lds[threadIdx.x]);
+    if (threadIdx.x < rtd::kPopProfN)
+        atomicAdd(&rtd::g_pop_prof[threadIdx.x], rtd::pop_prof_lds[0][threadIdx.x] + rtd::pop_prof_lds[1][threadIdx.x] +
+                                                     rtd::pop_prof_lds[2][threadIdx.x] + rtd::pop_prof_lds[3][threadIdx.x]);
 #endif
     rtd::counters_flush<COUNT>(cnt, counters);
 }
@@ -3446,6 +3465,61 @@ __global__ void __launch_bounds__(256) coop_check_kernel(const float4 *tri, int 
     if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
 }
 
+// rt_device_selfcheck 5: whole closest-hit queries on an uploaded scene through trav_step_coop (K
+// stack frames in LDS, at most POPS frames popped per step), against the per-lane trav_step loop
+// over an ArrayStack in scratch, in the same kernel: t, triangle, the local best and the AABB
+// and triangle counts, bit for bit.  The waves hold the real mix of node, leaf and pop lanes
+// (the plain kernel's coop records, leaf rounds and leaf deferral); with K = 4 most waves hold
+// lanes whose frames are in scratch.  Ray i starts inside the root box with a direction uniform
+// on the sphere, both from a hash of i; every 64th lane is inactive from the start and the last
+// wave has a single active lane.  Both loops are bounded by `bound` steps: a lane still
+// traversing there counts as a mismatch (a liveness bug fails the check, it does not hang).
+__device__ __forceinline__ uint32_t pop_check_hash(uint32_t x) {   // (lowbias32)
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+template <int K, int POPS>
+__global__ void __launch_bounds__(256) pop_check_kernel(DevScene sc, int n_rays, int bound, unsigned long long *bad) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    const int lane = (int)(threadIdx.x & 63);
+    const bool last_wave = i >= n_rays - 64;
+    const bool valid = i < n_rays && (last_wave ? lane == 0 : lane != 63);
+    const rtd::NodeRec root = rtd::load_node(sc.node, 0);
+    float u[6];
+    for (int c = 0; c < 6; ++c) u[c] = (float)(pop_check_hash(6u * (uint32_t)i + (uint32_t)c) >> 8) * 0x1p-24f;
+    rtv::V3 o{root.mn[0] + u[0] * (root.mx[0] - root.mn[0]), root.mn[1] + u[1] * (root.mx[1] - root.mn[1]),
+              root.mn[2] + u[2] * (root.mx[2] - root.mn[2])};
+    const float z = 2.f * u[3] - 1.f, ph = 6.28318530718f * u[4], s = sqrtf(fmaxf(0.f, 1.f - z * z));
+    const rtd::Ray r = rtd::make_ray(o, rtv::V3{s * cosf(ph), s * sinf(ph), z});
+    const rtd::GlobalNodes gn{sc.node};
+    // the coop query
+    rtd::TravStateU T;
+    Counters cnt{0, 0, 0, 0, 0, 0, 0};
+    uint2 spill[rtd::kStack - K];
+    rtd::LdsStackT<K> S{spill};
+    bool active = rtd::trav_start<true>(0u, root.a, root.b, T, cnt) && valid;
+    int leaf_defer = 0;
+    for (int it = 0; it < bound && __any(active); ++it)
+        if (rtd::trav_step_coop<true, kCoopLeavesPlain, false, rtd::kLeafDeferPlain, kPlainFarDist2, POPS>(
+                sc, r, T, S, gn, cnt, active, kCoopRoundMinPlain, rtd::NoHook{}, &leaf_defer))
+            active = false;
+    // the per-lane query
+    rtd::TravState T2;
+    Counters cnt2{0, 0, 0, 0, 0, 0, 0};
+    uint2 frames[rtd::kStack];
+    rtd::ArrayStack S2{frames};
+    bool active2 = rtd::trav_start<true>(0u, root.a, root.b, T2, cnt2) && valid;
+    for (int it = 0; it < bound && active2; ++it)
+        if (rtd::trav_step<true, kPlainFarDist2>(sc, r, T2, S2, gn, cnt2)) active2 = false;
+    unsigned long long local = 0;
+    if (valid)
+        local = (active | active2 | (T.best.prim != T2.best.prim) | (__float_as_uint(T.best.t) != __float_as_uint(T2.best.t)) |
+                 (__float_as_uint(T.acc) != __float_as_uint(T2.acc)) | (cnt.aabb != cnt2.aabb) | (cnt.tri != cnt2.tri))
+                    ? 1ull : 0ull;
+    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
+    if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
+}
+
 namespace {
 // Host-made cases of selfcheck 2 (deterministic): 8-triangle groups of a base triangle, its
 // exact copy, a coplanar one behind an equal-t prefix, its copy, a NaN-vertex one, a random
@@ -3525,14 +3599,49 @@ int mat_selfcheck(uint64_t *mismatches) {
     return rt_fail(RT_ERR_ARG, "rt_device_selfcheck 4: built without RT_SHADE_GATHER");
 #endif
 }
+// rt_device_selfcheck 5 over every device copy that exists (an error where there is none).
+template <int K, int POPS>
+void pop_check_launch(const DevScene &sc, int n_rays, int bound, unsigned long long *d) {
+    hipLaunchKernelGGL((pop_check_kernel<K, POPS>), dim3((unsigned)(n_rays / 256)), dim3(256), 0, nullptr, sc, n_rays, bound, d);
+}
+int pop_selfcheck(uint64_t *mismatches) {
+    std::lock_guard<std::mutex> lk(g_live_mu);
+    if (g_live.empty()) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck 5: no scene is uploaded");
+    uint64_t total = 0;
+    for (rt_device_scene *ds : g_live) {
+        DeviceGuard guard(ds->device);
+        if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "rt_device_selfcheck 5: hipSetDevice failed");
+        if (ds->ds.n_nodes < 1 || ds->ds.n_tris < 1) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck 5: empty scene");
+        const int n_rays = 16384;
+        const long long bound = 4ll * ((long long)ds->ds.n_nodes + ds->ds.n_tris) + 64;
+        if (bound > 0x7fffffffll) return rt_fail(RT_ERR_LIMIT, "rt_device_selfcheck 5: scene too large");
+        unsigned long long *d = nullptr, h = 0;
+        HIP_TRY(hipMalloc((void **)&d, sizeof *d));
+        hipError_t e = hipMemset(d, 0, sizeof *d);
+        if (e == hipSuccess) {
+            pop_check_launch<rtd::kLdsStack, 1>(ds->ds, n_rays, (int)bound, d);
+            pop_check_launch<rtd::kLdsStack, 2>(ds->ds, n_rays, (int)bound, d);
+            pop_check_launch<4, 1>(ds->ds, n_rays, (int)bound, d);   // (frames in scratch in most waves)
+            pop_check_launch<4, 2>(ds->ds, n_rays, (int)bound, d);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        if (e != hipSuccess) return rt_fail(RT_ERR_DEVICE, std::string("rt_device_selfcheck 5: ") + hipGetErrorString(e));
+        total += h;
+    }
+    *mismatches = total;
+    return RT_OK;
+}
 }  // namespace
 
 extern "C" {
 
 int rt_device_selfcheck(int32_t which, uint64_t *mismatches) {
     if (!mismatches) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck: null output");
-    if (which < 0 || which > 4) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck: unknown check " + std::to_string(which));
+    if (which < 0 || which > 5) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck: unknown check " + std::to_string(which));
     if (which == 4) return mat_selfcheck(mismatches);
+    if (which == 5) return pop_selfcheck(mismatches);
     unsigned long long *d = nullptr;
     HIP_TRY(hipMalloc((void **)&d, sizeof *d));
     hipError_t e = hipMemset(d, 0, sizeof *d);

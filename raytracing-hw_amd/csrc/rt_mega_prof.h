@@ -46,6 +46,8 @@ int mega_prof_reset(hipStream_t stream) {
     HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mega_prof), z, 8 * sizeof z[0], 0, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mega_seg), z, 8 * sizeof z[0], 0, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(rtd::g_spec_prof), z, sizeof z, 0, hipMemcpyHostToDevice, stream));
+    static const unsigned long long zp[rtd::kPopProfN] = {};
+    HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(rtd::g_pop_prof), zp, sizeof zp, 0, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_wave_n), z, sizeof(unsigned), 0, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(rtd::g_chain_n), z, sizeof(unsigned), 0, hipMemcpyHostToDevice, stream));
     static const std::vector<unsigned long long> ztb(kTb * kTbN, 0ull);
@@ -127,6 +129,23 @@ int mega_prof_report(hipStream_t stream, bool count, long long n_pixels, const i
                  "normal=%.0f mr=%.0f sample=%.0f pdf=%.0f base+brdf=%.0f\n",
                  (double)sg[0] / pf[3], (double)sg[1] / pf[3], (double)sg[2] / pf[3],
                  (double)sg[3] / pf[3], (double)sg[4] / pf[3], (double)sg[5] / pf[3]);
+    // the pop block of the coop step (rt_wavefront.h g_pop_prof): how often it runs, for how many
+    // lanes, and its share of the traversal iterations' cycles
+    unsigned long long pp[rtd::kPopProfN];
+    HIP_TRY(hipMemcpyFromSymbolAsync(pp, HIP_SYMBOL(rtd::g_pop_prof), sizeof pp, 0, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (pp[0]) {
+        const double st = (double)pp[0];
+        std::fprintf(stderr, "[mega pop] coop steps/wave=%.0f lanes at step end: node=%.1f leaf=%.1f pop=%.1f | "
+                     "steps with a pop=%.3f popping lanes/such step=%.2f cyc/pop block=%.0f "
+                     "pop cycles/step=%.0f share of cyc/trav_iter=%.3f\n",
+                     st / pf[7], pp[1] / st, pp[2] / st, pp[3] / st, pp[4] / st,
+                     pp[4] ? (double)pp[5] / pp[4] : 0.0, pp[4] ? (double)pp[6] / pp[4] : 0.0, pp[6] / st,
+                     pf[1] ? (double)pp[6] / (double)pf[1] : 0.0);
+        std::fprintf(stderr, "[mega pop] steps with a pop by popping lanes (1-4, 5-8, ..., 61-64):");
+        for (int b = 0; b < 16; ++b) std::fprintf(stderr, " %.4f", pp[4] ? (double)pp[8 + b] / pp[4] : 0.0);
+        std::fprintf(stderr, "\n");
+    }
     // wave finish times relative to the first wave start: percentiles (ms)
     unsigned nw = 0;
     HIP_TRY(hipMemcpyFromSymbolAsync(&nw, HIP_SYMBOL(g_wave_n), sizeof nw, 0, hipMemcpyDeviceToHost, stream));

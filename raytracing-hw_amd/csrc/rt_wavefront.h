@@ -484,6 +484,8 @@ __device__ __forceinline__ bool trav_start(uint32_t bits, uint32_t root_a, uint3
 // TP_POP), so a lane that unwinds many frames no longer holds its whole wave in the pop
 // loop: sponza 1080p 1280 -> 1148 ms, slowest 8-way shard 246 -> 217 ms, C5 at 16 spp
 // 348 -> 308 ms; 1 pop: 1150 / 219 ms, 3: 1164 / 221 (profiles/r03_ab.jsonl r03y).  0: no cap.
+// Measured again since the coop step, leaf deferral and the root-free cull: the plain kernel takes
+// 1 (frame 964 against 985 ms), the runahead kernel keeps 2 (rt_device.hip RT_PLAIN_MAX_POPS).
 #ifndef RT_MAX_POPS
 #define RT_MAX_POPS 2
 #endif
@@ -494,7 +496,9 @@ constexpr int kMaxPops = RT_MAX_POPS;
 // DIST2: far frames hold the squared entry distance (node_step); the cull compares it with
 // far_thr(acc), made once here and again only where a best frame changes acc, so a far frame
 // costs one conversion and one f64 compare in place of the f32 compare.
-template <bool DIST2 = kFarDist2, class Stack, class TS>
+// MAXP: the cap for this caller (the lane-resident kernels' coop step passes its kernel's own,
+// rt_device.hip RT_PLAIN_MAX_POPS / RT_SPEC_MAX_POPS).
+template <bool DIST2 = kFarDist2, int MAXP = kMaxPops, class Stack, class TS>
 __device__ __forceinline__ bool trav_pop(TS &T, Stack &stk) {
     float acc = T.acc;
     int sp = T.sp;
@@ -505,7 +509,7 @@ __device__ __forceinline__ bool trav_pop(TS &T, Stack &stk) {
             T.acc = acc;
             return true;
         }
-        if (kMaxPops > 0 && n == kMaxPops) {   // the rest next step (T.phase stays TP_POP)
+        if (MAXP > 0 && n == MAXP) {   // the rest next step (T.phase stays TP_POP)
             T.sp = sp;
             T.acc = acc;
             return false;
@@ -780,8 +784,53 @@ constexpr int kLeafDefer = RT_LEAF_DEFER, kLeafDeferMax = RT_LEAF_DEFER_MAX;
 #define RT_PLAIN_LEAF_DEFER 6
 #endif
 constexpr int kLeafDeferPlain = RT_PLAIN_LEAF_DEFER;
-template <bool COUNT, int kCoopLeaves, bool MASK_LOAD, int DEFER = kLeafDefer, bool DIST2 = kFarDist2, class Stack,
-          class Nodes, class TS, class Hook = NoHook>
+// Diagnostics build (RT_MEGA_PROF): what the pop block costs and for how many lanes it runs,
+// per wave in LDS (lane 0 adds), summed into g_pop_prof at the kernel's end.
+// [0] coop steps [1]-[3] lanes at TP_NODE / TP_LEAF / TP_POP when the step ends [4] steps in
+// which trav_pop runs [5] lanes it runs for [6] its clock64 cycles [7] unused
+// [8]-[23] steps by popping lanes: 1-4, 5-8, ..., 61-64
+constexpr int kPopProfN = 24;
+#if defined(RT_MEGA_PROF) && defined(__HIPCC__)
+__device__ unsigned long long g_pop_prof[kPopProfN];
+__shared__ unsigned long long pop_prof_lds[4][kPopProfN];
+// One coop step's line of the pop profile (every lane calls; `trav`: still traversing).
+__device__ __forceinline__ void pop_prof_step(bool trav, int phase, int n_pop, long long cyc) {
+    const int nn = __popcll(__ballot(trav && phase == TP_NODE)), nl = __popcll(__ballot(trav && phase == TP_LEAF)),
+              np = __popcll(__ballot(trav && phase == TP_POP));
+    if ((threadIdx.x & 63) == 0) {
+        unsigned long long *c = pop_prof_lds[threadIdx.x >> 6];
+        c[0] += 1;
+        c[1] += (unsigned long long)nn;
+        c[2] += (unsigned long long)nl;
+        c[3] += (unsigned long long)np;
+        if (n_pop > 0) {
+            c[4] += 1;
+            c[5] += (unsigned long long)n_pop;
+            c[6] += (unsigned long long)cyc;
+            c[8 + (n_pop - 1) / 4] += 1;
+        }
+    }
+}
+#endif
+// The coop step's tail: the node lanes' pair test, then the return up the stack (POPS frames at most).
+template <bool COUNT, bool DIST2, int POPS, class Stack, class TS>
+__device__ __forceinline__ bool coop_tail(bool at_node, bool active, const float4 q[4], const Ray &r, TS &T, Stack &stk,
+                                          Counters &cnt) {
+    if (at_node) node_step<COUNT, DIST2>(q, r, T, stk, cnt);
+#if defined(RT_MEGA_PROF)
+    const unsigned long long pm = __ballot(active && T.phase == TP_POP);
+    const long long pc0 = clock64();
+    bool done = false;
+    if (active && T.phase == TP_POP) done = trav_pop<DIST2, POPS>(T, stk);
+    pop_prof_step(active && !done, T.phase, __popcll(pm), pm ? clock64() - pc0 : 0);
+    return done;
+#else
+    if (active && T.phase == TP_POP) return trav_pop<DIST2, POPS>(T, stk);
+    return false;
+#endif
+}
+template <bool COUNT, int kCoopLeaves, bool MASK_LOAD, int DEFER = kLeafDefer, bool DIST2 = kFarDist2,
+          int POPS = kMaxPops, class Stack, class Nodes, class TS, class Hook = NoHook>
 __device__ __forceinline__ bool trav_step_coop(const DevScene &sc, const Ray &r, TS &T, Stack &stk,
                                                const Nodes &nodes, Counters &cnt, bool active, int round_min,
                                                const Hook &hook = Hook{}, int *leaf_defer = nullptr) {
@@ -881,10 +930,7 @@ __device__ __forceinline__ bool trav_step_coop(const DevScene &sc, const Ray &r,
         }
     }
     hook();
-    // node lanes: the pair test
-    if (at_node) node_step<COUNT, DIST2>(q, r, T, stk, cnt);
-    if (active && T.phase == TP_POP) return trav_pop<DIST2>(T, stk);
-    return false;
+    return coop_tail<COUNT, DIST2, POPS>(at_node, active, q, r, T, stk, cnt);
 }
 
 #endif
