@@ -531,8 +531,8 @@ int rt_accum_frame_u8_denoised(rt_accum *accum, const rt_denoise_params *params,
  * headline frame.
  *
  * Inputs and out_mean as rt_denoise's.  variance: NULL, or W * H floats, the variance of each
- * pixel's demodulated mean L summed over the channels (the seam for per-sample second moments,
- * which no render kernel keeps today).  out_variance: NULL, or W * H floats (below).
+ * pixel's demodulated mean L summed over the channels (a moments accumulator measures it:
+ * rt_accum_variance below).  out_variance: NULL, or W * H floats (below).
  *
  * Write geo(p, q) = nd * wp with nd and wp exactly rt_denoise's normal and plane terms for centre
  * p and tap q, and lum(L) = (0.2126f * L.x + 0.7152f * L.y) + 0.0722f * L.z.
@@ -596,6 +596,67 @@ int rt_denoise_guided_frame_u8(const float *sums, const int32_t *counts, int32_t
                                const float *gbuffer, const float *variance, const rt_denoise_guided_params *params,
                                int32_t device, uint8_t *out_rgb);
 int rt_accum_frame_u8_guided(rt_accum *accum, const rt_denoise_guided_params *params, uint8_t *out_rgb);
+
+/* --- per-sample second moments: measured variance ----------------------------------------
+ * A moments accumulator is a fast accumulator (rt_accum_create_fast) that keeps, beside the sum S
+ * of a pixel's sample colours x, the sum Q of their squares.  For sample s of a pixel with colour
+ * x (three f32 values), q[ch] = x[ch] * x[ch], one f32 multiply.  Q is the fast fold of q exactly
+ * as S is the fast fold of x: with chunk size c, the partials of a chunk are added in sample order
+ * from +0.f, the chunk partials in chunk order from +0.f, and an open chunk is carried as open2
+ * and reported as total2 + open2 when n % c != 0.  Non-finite samples give non-finite moments;
+ * nothing is clamped.  Per pixel the accumulator keeps a moment record of eight words in a buffer
+ * of its own (total2 x y z, open2 x y z, 0, 0) and the reported moment (three floats).
+ *
+ * Variance of the mean, V = variance_of_mean(n, S, Q, albedo, hit), the `variance` input of
+ * rt_denoise_guided: a miss (triangle id of the first-hit record < 0) or n < 2 gives 0; otherwise
+ * r = 1.f / (float)n, r1 = 1.f / (float)(n - 1) and per channel
+ *   m = S * r;  e2 = Q * r;  v = e2 - m * m;  v = v > 0 ? v : 0;  vm = v * r1
+ *   a' = albedo > 1e-3f ? albedo : 1e-3f;  d = vm / (a' * a')
+ * V = (d0 + d1) + d2, and a V that is not finite gives 0.
+ * Relative error, relative_error(n, S, Q), n >= 2, with m and vm as above:
+ *   ((sqrtf(vm0) + sqrtf(vm1)) + sqrtf(vm2)) / sqrtf(((m0 + m1) + m2) + 1e-4f)
+ * the standard error of the mean normalised as rt_accum_select's estimate is.
+ * Known limit: e2 - m * m cancels in f32; the error of vm is bounded by
+ * 4 (n + 2) 2^-24 e2 r1 (each of e2 and m * m carries at most n + 2 roundings).
+ *
+ * rt_accum_create_fast_moments is rt_accum_create_fast with the moment buffers, made once at
+ * creation; the same refusals.  On a moments accumulator every other rt_accum_* entry behaves as on
+ * a fast one, and its sums are a fast accumulator's bit for bit.  rt_accum_has_moments: 0 or 1.
+ * rt_accum_moments writes the reported moments (shard layout, three floats per pixel) to host
+ * memory and waits; rt_accum_device_moments is their device buffer, valid until rt_accum_free.  On
+ * an accumulator without moments the first is RT_ERR_ARG and the second NULL.
+ *
+ * rt_variance_from_moments runs on the host: width * height pixels (any pixel range with its own
+ * first-hit records: it is per pixel, so a shard is fine), counts or NULL and one spp as
+ * rt_denoise's, out width * height floats.  rt_variance_from_moments_device runs on the current
+ * HIP device, asynchronously on `stream`, every pointer a device pointer, with the same bits.
+ * Refusals as rt_denoise's.  rt_accum_variance writes V of the accumulator's own pixels (its
+ * counts, its G-buffer: rendered on first use, for any world) to host memory and waits.
+ *
+ * rt_accum_frame_u8_guided_measured is rt_accum_frame_u8_guided with `variance` set to the
+ * measured V instead of NULL: the same contract (world = 1, nothing written into the accumulator).
+ *
+ * rt_accum_select_variance is rt_accum_select with its steps 1 and 2 unchanged, then
+ *   n_b < 2 -> selected;  otherwise selected iff relative_error(n_b, S_b, Q_b) > threshold
+ * (a NaN is never selected).  It needs no mark and ignores one.  rt_accum_add_selected,
+ * rt_accum_selection and the pending-selection rules apply unchanged.
+ *
+ * rt_accum_save on a moments accumulator writes magic "RTMACCUM", version 1: the fast file's
+ * header (the chunk size in its place), the fast records verbatim, then the moment records
+ * verbatim.  rt_accum_load reads all three kinds and returns that kind; for this one a wrong
+ * length, and non-zero open2 or pad words where next % c == 0, are RT_ERR_FORMAT before any
+ * device call.  Every entry below that needs moments is RT_ERR_ARG on an accumulator without. */
+int rt_accum_create_fast_moments(rt_scene *scene, const rt_params *params, rt_accum **out);
+int32_t rt_accum_has_moments(const rt_accum *accum);
+int rt_accum_moments(rt_accum *accum, float *out);
+const float *rt_accum_device_moments(rt_accum *accum);
+int rt_variance_from_moments(const float *sums, const float *moments, const int32_t *counts, int32_t spp, int32_t width,
+                             int32_t height, const float *gbuffer, float *out);
+int rt_variance_from_moments_device(const float *d_sums, const float *d_moments, const int32_t *d_counts, int32_t spp,
+                                    int32_t width, int32_t height, const float *d_gbuffer, float *d_out, void *stream);
+int rt_accum_variance(rt_accum *accum, float *out);
+int rt_accum_frame_u8_guided_measured(rt_accum *accum, const rt_denoise_guided_params *params, uint8_t *out_rgb);
+int rt_accum_select_variance(rt_accum *accum, const rt_select *select, void *stream, int64_t *n_selected);
 
 /* --- misc --------------------------------------------------------------------------- */
 const char *rt_last_error(void);

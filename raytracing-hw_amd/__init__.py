@@ -177,6 +177,19 @@ ABI = {
     "rt_denoise_guided_frame_u8": (ctypes.c_int, [_c_f, _c_i, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_f, _c_f,
                                                   ctypes.POINTER(RtDenoiseGuidedParams), ctypes.c_int32, _c_b]),
     "rt_accum_frame_u8_guided": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtDenoiseGuidedParams), _c_b]),
+    # per-sample second moments of fast-mode accumulators: measured variance
+    "rt_accum_create_fast_moments": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtParams), ctypes.POINTER(ctypes.c_void_p)]),
+    "rt_accum_has_moments": (ctypes.c_int32, [ctypes.c_void_p]),
+    "rt_accum_moments": (ctypes.c_int, [ctypes.c_void_p, _c_f]),
+    "rt_accum_device_moments": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "rt_variance_from_moments": (ctypes.c_int, [_c_f, _c_f, _c_i, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_f, _c_f]),
+    "rt_variance_from_moments_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p]),
+    "rt_accum_variance": (ctypes.c_int, [ctypes.c_void_p, _c_f]),
+    "rt_accum_frame_u8_guided_measured": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtDenoiseGuidedParams), _c_b]),
+    "rt_accum_select_variance": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtSelect), ctypes.c_void_p,
+                                                ctypes.POINTER(ctypes.c_int64)]),
 }
 
 _lib_handle = None
@@ -417,31 +430,45 @@ class Scene:
         _check(lib().rt_gbuffer_device(self._h, ctypes.byref(p), ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(stream_ptr or 0)))
 
     def accumulator(self, rank=0, world=1, row_block=8, device=0, natural_order=False, heavy_order=False,
-                    runahead=True, fast=False, fast_chunk=0):
+                    runahead=True, fast=False, fast_chunk=0, moments=False):
         """Progressive rendering (rt_accum_create): the shard's per-pixel chain state on
         `device` (uploaded here if need be), rendered further in passes of any size; after
         passes of n1 + ... + nk samples the sums are those of render_sums(n1 + ... + nk), bit
         for bit.  fast=True (rt_accum_create_fast): a fast-mode accumulator with chunks of
         fast_chunk samples (0 = 2), fixed for its life; a pixel with n samples then holds the
-        fast sum of n samples in chunks of that size, whatever the passes were."""
+        fast sum of n samples in chunks of that size, whatever the passes were.  moments=True
+        (with fast; rt_accum_create_fast_moments): it also keeps the sum of every sample's squared
+        colour (moments(), variance(), select_variance(), frame(measured=True))."""
+        if moments and not fast:
+            raise ValueError("moments=True needs fast=True (only fast-mode accumulators keep moments)")
         self.upload(device)
         p = self._params(0, rank, world, row_block, False, KERNEL_LANE, device=device, natural_order=natural_order,
                          runahead=runahead, heavy_order=heavy_order, fast=fast, fast_chunk=fast_chunk if fast else 0)
         h = ctypes.c_void_p()
-        _check((lib().rt_accum_create_fast if fast else lib().rt_accum_create)(self._h, ctypes.byref(p), ctypes.byref(h)))
+        create = lib().rt_accum_create_fast_moments if moments else lib().rt_accum_create_fast if fast else lib().rt_accum_create
+        _check(create(self._h, ctypes.byref(p), ctypes.byref(h)))
         return Accumulator(self, h.value, rank, world, row_block)
 
-    def render_adaptive(self, min_spp, max_spp, step, threshold, device=0, fast=False, fast_chunk=0):
+    def render_adaptive(self, min_spp, max_spp, step, threshold, device=0, fast=False, fast_chunk=0, moments=False):
         """Adaptive sampling of the whole frame on one shard (the loop of the CLI's RT_ADAPT):
         min_spp samples everywhere in two halves with a mark between them, then rounds of
         select(target = min(max_spp, largest count + step), threshold), mark, add_selected until
         nothing is selected or max_spp is reached.  Returns (sums (H, W, 3), counts (H, W),
         frame (H, W, 3) uint8 finished per pixel by its own count).  fast / fast_chunk: on a
-        fast-mode accumulator (see accumulator)."""
+        fast-mode accumulator (see accumulator).  moments (with fast): on a moments accumulator,
+        min_spp samples in one pass and then rounds of select_variance, add_selected, with no mark."""
         if min_spp < 2 or max_spp < min_spp or step < 1:
             raise ValueError("render_adaptive: need 2 <= min_spp <= max_spp and step >= 1")
-        acc = self.accumulator(device=device, fast=fast, fast_chunk=fast_chunk)
+        acc = self.accumulator(device=device, fast=fast, fast_chunk=fast_chunk, moments=moments)
         try:
+            if moments:
+                acc.add(min_spp)
+                while acc.samples < max_spp:
+                    target = min(max_spp, acc.samples + step)
+                    if acc.select_variance(target, threshold=threshold) == 0:
+                        break
+                    acc.add_selected()
+                return acc.sums(), acc.counts(), acc.frame()
             acc.add(min_spp // 2)
             acc.mark()
             acc.add(min_spp - min_spp // 2)
@@ -479,8 +506,8 @@ class Accumulator:
 
     @classmethod
     def load(cls, scene, path, device=0):
-        """rt_accum_load: the accumulator rt_accum_save wrote (of either kind: see fast_chunk),
-        checked against `scene`."""
+        """rt_accum_load: the accumulator rt_accum_save wrote (of any of the three kinds: see
+        fast_chunk and has_moments), checked against `scene`."""
         h = ctypes.c_void_p()
         _check(lib().rt_accum_load(scene.handle, device, os.fsencode(path), ctypes.byref(h)))
         with open(path, "rb") as f:   # rank, world, row_block: int32 words 6-8 of the header
@@ -504,6 +531,29 @@ class Accumulator:
         """The chunk size of a fast-mode accumulator (rt_accum_fast_chunk); 0 for a parity one."""
         return int(lib().rt_accum_fast_chunk(self._h))
 
+    @property
+    def has_moments(self):
+        """True for a moments accumulator (rt_accum_has_moments)."""
+        return bool(lib().rt_accum_has_moments(self._h))
+
+    def moments(self):
+        """(rows, W, 3) float32: per pixel the sum of its samples' squared colours, folded as the
+        sums are (rt_accum_moments; a moments accumulator only)."""
+        out = np.zeros((len(self.rows), self._scene.width, 3), np.float32)
+        _check(lib().rt_accum_moments(self._h, out.ctypes.data_as(_c_f)))
+        return out
+
+    @property
+    def device_moments_ptr(self):
+        return int(lib().rt_accum_device_moments(self._h) or 0)
+
+    def variance(self):
+        """(rows, W) float32: the measured variance of each owned pixel's demodulated mean
+        (rt_accum_variance), the `variance` input of denoise_guided."""
+        out = np.zeros((len(self.rows), self._scene.width), np.float32)
+        _check(lib().rt_accum_variance(self._h, out.ctypes.data_as(_c_f)))
+        return out
+
     def sums(self):
         """(rows, W, 3) float sums so far, as render_sums returns them."""
         out = np.zeros((len(self.rows), self._scene.width, 3), np.float32)
@@ -514,20 +564,25 @@ class Accumulator:
     def device_sums_ptr(self):
         return int(lib().rt_accum_device_sums(self._h) or 0)
 
-    def frame(self, denoise=None, guided=False):
+    def frame(self, denoise=None, guided=False, measured=False):
         """(rows, W, 3) uint8: the shard finished at spp = samples (on the device).  denoise: True
         (the default parameters) or a dict of denoise_params' arguments runs the frame denoiser in
         front of the finish (rt_accum_frame_u8_denoised; whole-frame accumulators only).  guided:
         with denoise, the variance-guided mode (rt_accum_frame_u8_guided; the dict then holds
-        denoise_guided_params' arguments)."""
+        denoise_guided_params' arguments).  measured: with guided, the filter's variance input is
+        the accumulator's measured variance (rt_accum_frame_u8_guided_measured; a moments
+        accumulator only)."""
         out = np.zeros((len(self.rows), self._scene.width, 3), np.uint8)
+        if measured and not guided:
+            raise ValueError("measured=True needs guided=True")
         if denoise is None or denoise is False:
             if guided:
                 raise ValueError("guided=True needs denoise=True or a dict of denoise_guided_params' arguments")
             _check(lib().rt_accum_frame_u8(self._h, out.ctypes.data_as(_c_b)))
         elif guided:
             gp = denoise_guided_params(**(denoise if isinstance(denoise, dict) else {}))
-            _check(lib().rt_accum_frame_u8_guided(self._h, ctypes.byref(gp), out.ctypes.data_as(_c_b)))
+            entry = lib().rt_accum_frame_u8_guided_measured if measured else lib().rt_accum_frame_u8_guided
+            _check(entry(self._h, ctypes.byref(gp), out.ctypes.data_as(_c_b)))
         else:
             dp = denoise_params(**(denoise if isinstance(denoise, dict) else {}))
             _check(lib().rt_accum_frame_u8_denoised(self._h, ctypes.byref(dp), out.ctypes.data_as(_c_b)))
@@ -554,6 +609,16 @@ class Accumulator:
         those below it, inside window = (x0, y0, x1, y1) (frame coordinates, half-open), with a
         non-zero byte in mask ((rows, W), the shard's layout) and, with threshold > 0, whose
         error estimate since the last mark exceeds it.  Returns how many were selected."""
+        return self._select(lib().rt_accum_select, target, window, mask, threshold, stream_ptr)
+
+    def select_variance(self, target, window=None, mask=None, threshold=0.0, stream_ptr=None):
+        """rt_accum_select_variance (a moments accumulator only): select() with the error test
+        replaced by the relative standard error of the pixel's mean, from its moments: a pixel
+        with fewer than 2 samples is selected, any other iff that error exceeds threshold.  It
+        needs no mark and ignores one."""
+        return self._select(lib().rt_accum_select_variance, target, window, mask, threshold, stream_ptr)
+
+    def _select(self, entry, target, window, mask, threshold, stream_ptr):
         x0, y0, x1, y1 = window if window is not None else (0, 0, 0, 0)
         m = None
         if mask is not None:
@@ -563,7 +628,7 @@ class Accumulator:
         sel = RtSelect(int(target), int(x0), int(y0), int(x1), int(y1), m.ctypes.data_as(_c_b) if m is not None else None,
                        float(threshold))
         n = ctypes.c_int64(0)
-        _check(lib().rt_accum_select(self._h, ctypes.byref(sel), ctypes.c_void_p(stream_ptr or 0), ctypes.byref(n)))
+        _check(entry(self._h, ctypes.byref(sel), ctypes.c_void_p(stream_ptr or 0), ctypes.byref(n)))
         self._n_selected = int(n.value)
         return self._n_selected
 
@@ -734,6 +799,32 @@ def denoise_device(d_sums_ptr, d_counts_ptr, spp, width, height, d_gbuffer_ptr, 
     _check(lib().rt_denoise_device(ctypes.c_void_p(d_sums_ptr), ctypes.c_void_p(d_counts_ptr or 0), int(spp), width, height,
                                    ctypes.c_void_p(d_gbuffer_ptr), ctypes.byref(dp), ctypes.c_void_p(d_out_ptr),
                                    ctypes.c_void_p(stream_ptr or 0)))
+
+
+def variance_from_moments(sums, moments, counts_or_spp, gbuffer):
+    """rt_variance_from_moments (the host function): the (H, W) float32 variance of each pixel's
+    demodulated mean, from its (H, W, 3) sums and moments (Accumulator.sums / moments), its count
+    and its first-hit record.  Per pixel, so any pixel range with its own records will do."""
+    sums, counts, spp, rec = _denoise_inputs(sums, counts_or_spp, gbuffer)
+    moments = np.ascontiguousarray(moments, np.float32)
+    if moments.shape != sums.shape:
+        raise ValueError("moments must have the sums' shape")
+    h, w = sums.shape[0], sums.shape[1]
+    out = np.zeros((h, w), np.float32)
+    _check(lib().rt_variance_from_moments(sums.ctypes.data_as(_c_f), moments.ctypes.data_as(_c_f),
+                                          counts.ctypes.data_as(_c_i) if counts is not None else None, spp, w, h,
+                                          rec.ctypes.data_as(_c_f), out.ctypes.data_as(_c_f)))
+    return out
+
+
+def variance_from_moments_device(d_sums_ptr, d_moments_ptr, d_counts_ptr, spp, width, height, d_gbuffer_ptr, d_out_ptr,
+                                 stream_ptr=None):
+    """rt_variance_from_moments_device: the same on the current HIP device (device pointers;
+    d_counts_ptr 0 / None: one spp), asynchronous on the stream."""
+    _check(lib().rt_variance_from_moments_device(ctypes.c_void_p(d_sums_ptr), ctypes.c_void_p(d_moments_ptr),
+                                                 ctypes.c_void_p(d_counts_ptr or 0), int(spp), width, height,
+                                                 ctypes.c_void_p(d_gbuffer_ptr), ctypes.c_void_p(d_out_ptr),
+                                                 ctypes.c_void_p(stream_ptr or 0)))
 
 
 def _variance_input(variance, h, w):

@@ -54,6 +54,7 @@
 #include "rt_bvh_layout.h"
 #include "rt_launch_plan.h"
 #include "rt_select.h"
+#include "rt_moments.h"
 #include "rt_frame_plan.h"
 #include "rt_gbuffer.h"
 #include "rt_denoise.h"
@@ -391,7 +392,11 @@ __global__ void __launch_bounds__(256) rt_finish_counts_kernel(const float *sum,
 // end `spp` (rt_mega.h mega_assign_fast_chain).  The kernel only reads records; its partials go to
 // the unit-major partial buffer and rt_fast_fold_chain_kernel folds them.  A unit past its pixel's
 // own starts nothing (the lane claims again), so a wave may leave only once the queue is empty.
-template <bool COUNT, bool FAST = false, bool LSPLIT = false, bool SPEC = false, bool CHAIN = false>
+// MOM (FAST + CHAIN only, rt_accum_create_fast_moments): that pass, keeping per unit a second
+// partial, of the samples' squared colours (rt_moments.h), in the second half of the partial
+// buffer; rt_fast_fold_chain_kernel<true> folds both.  Its own instantiation: the others are the
+// code they were.
+template <bool COUNT, bool FAST = false, bool LSPLIT = false, bool SPEC = false, bool CHAIN = false, bool MOM = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SPEC ? kMegaWpeSpec : kMegaWpe, 8)))
 rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out, unsigned long long *counters,
                unsigned long long *queue, const int *order, unsigned *cost, int cs, int mode) {
@@ -401,6 +406,7 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
     constexpr int kShade = kSpec ? kSpecShade : (!COUNT && !FAST && !LSPLIT && !kChain) ? kPlainShade : rtd::SHADE_TABLES;
     // (a pass of a fast accumulator: `cs` is its chunk size, `mode` the units per item)
     constexpr bool kFastChain = CHAIN && FAST && !COUNT && !LSPLIT && !SPEC;
+    constexpr bool kMom = MOM && kFastChain;
     const int park_below = kFastChain ? 0 : rtp::mode_park_below(mode), resume_pct = kFastChain ? 0 : rtp::mode_resume_pct(mode);
     const uint4 *resume = kSpec && resume_pct > 0 ? (const uint4 *)queue[rtd::kQueueParkList] : nullptr;
     // (CHAIN: the pass's item count, the shard's pixels for a full pass or a selection's length
@@ -537,7 +543,10 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
                 if (need) {
                     const long long p = (long long)base + below;
                     if (p < n_items) {
-                        if constexpr (kFastChain)
+                        if constexpr (kMom)
+                            rtd::mega_assign_fast_chain<COUNT, true>(L, sc, g, p, st.n, order, cs, spp, root, cnt, rtd::chain_of(queue),
+                                                                     queue);
+                        else if constexpr (kFastChain)
                             rtd::mega_assign_fast_chain<COUNT>(L, sc, g, p, st.n, order, cs, spp, root, cnt, rtd::chain_of(queue));
                         else if (FAST) rtd::mega_assign_fast<COUNT>(L, sc, g, p, cs, spp, root, cnt);
                         else if constexpr (kChain)
@@ -670,7 +679,7 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
                 L.T.sp = (int)(pk >> 5);
             }
         } else {
-            rtd::mega_iterate<COUNT, decltype(S), decltype(nodes), FAST, LSPLIT, kChain, kShade>(
+            rtd::mega_iterate<COUNT, decltype(S), decltype(nodes), FAST, LSPLIT, kChain, kShade, kMom>(
                 L, shade_now, sc, g, st, spp, out, cost, root, S, nodes, cnt, kSpec && tail, false, queue);
             // RT_INV_RECOMPUTE: 1 / direction is recomputed after a shading pass (the same IEEE
             // division as make_ray, so the same bits), so a traversing lane does not hold it
@@ -749,6 +758,50 @@ __global__ void __launch_bounds__(256) rt_fast_fold_chain_kernel(uint4 *chain, c
     sums[3 * p + 0] = s[0];
     sums[3 * p + 1] = s[1];
     sums[3 * p + 2] = s[2];
+}
+
+// The fold of a moments accumulator's pass (rt_moments.h): the same fold on both partial sets, the
+// sums' at `part` and the squares' at part + 3 * n_list * units, into the fast record and the
+// moment record (mom: 32 bytes per pixel, rt_mega.h moment_rec), and both reported values.  The
+// moment record's `next` is the fast record's, so both folds see the same units.  Pixels not
+// listed, and items already at `target`, are not touched.
+__global__ void __launch_bounds__(256) rt_fast_fold_moments_kernel(uint4 *chain, uint4 *mom, const int *items, long long n_list,
+                                                                    int units, int c, int target, const float *__restrict__ part,
+                                                                    float *sums, float *moments) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_list) return;
+    const long long p = items ? (long long)items[i] : i;
+    rtd::FastRec q = rtd::fast_rec(chain, p);
+    const int own = rtfu::units_of(q.r.next, target, c);
+    if (own < 1 || own > units) return;
+    rtfu::Rec m;
+    m.next = q.r.next;
+    rtd::moment_rec(mom, p, m);
+    rtfu::fold(q.r, target, c, FastPartials{part, n_list, i});
+    rtfu::fold(m, target, c, FastPartials{part + 3 * n_list * (long long)units, n_list, i});
+    rtd::fast_rec_store(chain, p, q.r);
+    rtd::moment_rec_store(mom, p, m);
+    float s[3], s2[3];
+    rtfu::reported(q.r, c, s);
+    rtfu::reported(m, c, s2);
+    for (int ch = 0; ch < 3; ++ch) {
+        sums[3 * p + ch] = s[ch];
+        moments[3 * p + ch] = s2[ch];
+    }
+}
+
+// The measured variance (rt_moments.h variance_of_pixel): one thread per pixel, consecutive lanes
+// on consecutive pixels; counts or, when null, `spp` for every pixel.
+__global__ void __launch_bounds__(256) rt_variance_kernel(const float *__restrict__ sums, const float *__restrict__ moments,
+                                                           const int32_t *__restrict__ counts, int spp, long long n,
+                                                           const float4 *__restrict__ g, float *__restrict__ out) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const float4 g1 = g[rtd::kGbufferQuads * p + 1];
+    const float S[3] = {sums[3 * p], sums[3 * p + 1], sums[3 * p + 2]};
+    const float Q[3] = {moments[3 * p], moments[3 * p + 1], moments[3 * p + 2]};
+    const float al[3] = {g1.x, g1.y, g1.z};
+    out[p] = rtmo::variance_of_mean(counts ? counts[p] : spp, S, Q, al, __float_as_int(g1.w) >= 0);
 }
 
 // Pixel order, step 1: the sort's values (shard pixel ids) and keys (pre-pass costs).
@@ -1419,6 +1472,9 @@ struct ChainPass {
     // A fast accumulator's pass (rt_accum_create_fast): its chunk size and the work units every
     // item of this launch gets (rt_launch_plan.h PlanIn.fast_units); 0, 0 for a parity pass.
     int fast_c = 0, fast_units = 0;
+    // A moments accumulator's pass: its moment records and reported moments (else null).
+    uint4 *mom = nullptr;
+    float *moments = nullptr;
 };
 
 // One word of the queue block, written in stream order.
@@ -1546,7 +1602,9 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
     if (in.kernel == RT_KERNEL_LANE && g.n_pixels > 0) in.spec_blocks = resident_blocks(d, rk);
     const rtp::Schedule plan = rtp::plan_schedule(in);
     if (plan.refused) return rt_fail(plan.refused.code, plan.refused.msg);
-    const MegaKernel mk = mega_kernel_of(plan.v);
+    const bool moments_pass = cp && cp->mom && plan.v.fast && plan.v.chain;
+    // (a moments pass: the fast accumulator's schedule on the instantiation that keeps the squares)
+    const MegaKernel mk = moments_pass ? rt_mega_kernel<false, true, false, false, true, true> : mega_kernel_of(plan.v);
     rtp::Grid grid;
     if (plan.lane) grid = rtp::plan_grid(plan, resident_blocks(d, mk));
     if (grid.refused) return rt_fail(grid.refused.code, grid.refused.msg);
@@ -1583,7 +1641,9 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
         if (st) HIP_TRY(hipEventRecord(ev.ordered, stream));
         float *k_out = d_out;
         if (plan.v.fast) {   // chunk-major partial sums, folded below
-            HIP_TRY(grow((void **)&d->fast_part, &d->fast_part_bytes, (size_t)plan.n_items * 3 * sizeof(float)));
+            // (a moments pass: the units' partials of squares follow the sums', six floats per unit)
+            HIP_TRY(grow((void **)&d->fast_part, &d->fast_part_bytes,
+                         (size_t)plan.n_items * (moments_pass ? 6 : 3) * sizeof(float)));
             k_out = d->fast_part;
         }
 #ifdef RT_MEGA_PROF
@@ -1592,6 +1652,10 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
         // the chain buffer's address, where the chain kernels read it
         if (cp)
             if (int rc = set_queue_word(d, rtd::kChainWord, cp->chain, stream)) return rc;
+        if (moments_pass) {
+            if (int rc = set_queue_word(d, rtd::kMomentWord, cp->mom, stream)) return rc;
+            if (int rc = set_queue_word(d, rtd::kMomentPartWord, k_out + 3 * plan.n_items, stream)) return rc;
+        }
         const bool fast_pass = plan.v.fast && plan.v.chain;   // (its `mode` argument: the units per item)
         hipLaunchKernelGGL(mk, dim3((unsigned)grid.blocks), dim3(256), 0, stream, d->ds, g, w, in.spp, k_out, d->counters,
                            d->queue, order, (unsigned *)nullptr, plan.cs,
@@ -1599,7 +1663,11 @@ int launch(rt_scene *s, const rt_params *p, float *d_out, hipStream_t stream, rt
         HIP_TRY(hipGetLastError());
         if (plan.handoff)
             if (int rc = launch_handoff(d, g, grid, rk, w, in.spp, k_out, stream)) return rc;
-        if (fast_pass) {   // the items' partials into their records and reported sums (d_out: the accumulator's sums)
+        if (moments_pass) {   // both partial sets into both records, the reported sums and moments
+            hipLaunchKernelGGL(rt_fast_fold_moments_kernel, dim3((unsigned)((w.n + 255) / 256)), dim3(256), 0, stream, cp->chain,
+                               cp->mom, order, w.n, plan.chunks, plan.cs, in.spp, (const float *)d->fast_part, d_out, cp->moments);
+            HIP_TRY(hipGetLastError());
+        } else if (fast_pass) {   // the items' partials into their records and reported sums (d_out: the accumulator's sums)
             hipLaunchKernelGGL(rt_fast_fold_chain_kernel, dim3((unsigned)((w.n + 255) / 256)), dim3(256), 0, stream, cp->chain,
                                order, w.n, plan.chunks, plan.cs, in.spp, (const float *)d->fast_part, d_out);
             HIP_TRY(hipGetLastError());
@@ -1765,6 +1833,13 @@ struct rt_accum {
     // A fast accumulator (rt_accum_create_fast): its chunk size, fixed for its life; 0 = parity.
     // Its chain buffer then holds fast records (rt_mega.h FastRec).
     int fast_c = 0;
+    // A moments accumulator (rt_accum_create_fast_moments, rt_moments.h): a fast one that also keeps
+    // per pixel the moment record (32 bytes, rt_mega.h moment_rec) and the reported moment
+    // (n_pixels x 3); both made at creation.  `var`: the measured variance, made on first use.
+    bool has_moments = false;
+    uint4 *mom = nullptr;
+    float *moments = nullptr;
+    float *var = nullptr;
     // rt_accum_frame_u8_denoised's, made on first use and kept: the shard's first-hit records
     // (rendered once: they depend on the scene alone), the filter's scratch and its mean frame
     float4 *gbuf = nullptr;
@@ -1789,7 +1864,11 @@ struct SelectOut {
 // and WRITE = true evaluates the same rule again and writes pixel p to
 // list[blocks[b] + selected in the block's earlier waves + selected lanes below (mbcnt)]: the
 // list is in ascending shard-pixel order, holds each pixel at most once, and no atomic orders it.
-template <bool WRITE>
+// VAR (rt_accum_select_variance, a moments accumulator): steps 1 and 2 of the rule, then the
+// relative standard error of the mean from the moments (rt_moments.h relative_error) in place of
+// steps 3 and 4; `mark_sums` then carries the reported moments and `mark_counts` is null (no
+// mark is read).  The scan and the list order are the same.
+template <bool WRITE, bool VAR = false>
 __global__ void __launch_bounds__(256) rt_select_kernel(ShardGeom g, rtsel::Rule rule, const uint4 *chain, const float *sums,
                                                          const float *mark_sums, const int32_t *mark_counts,
                                                          const uint8_t *mask, unsigned *blocks, int *list, SelectOut *out) {
@@ -1805,14 +1884,19 @@ __global__ void __launch_bounds__(256) rt_select_kernel(ShardGeom g, rtsel::Rule
         int x, y;
         rtd::shard_xy(g, p, x, y);
         const float S_b[3] = {sums[3 * p], sums[3 * p + 1], sums[3 * p + 2]};
-        const int n_a = mark_counts ? mark_counts[p] : 0;
-        float S_a[3] = {0.f, 0.f, 0.f};
-        if (mark_sums) {
-            S_a[0] = mark_sums[3 * p];
-            S_a[1] = mark_sums[3 * p + 1];
-            S_a[2] = mark_sums[3 * p + 2];
+        if constexpr (VAR) {
+            const float Q_b[3] = {mark_sums[3 * p], mark_sums[3 * p + 1], mark_sums[3 * p + 2]};
+            sel = rtmo::selected(rule, x, y, mask ? mask[p] : 1u, n_b, S_b, Q_b);
+        } else {
+            const int n_a = mark_counts ? mark_counts[p] : 0;
+            float S_a[3] = {0.f, 0.f, 0.f};
+            if (mark_sums) {
+                S_a[0] = mark_sums[3 * p];
+                S_a[1] = mark_sums[3 * p + 1];
+                S_a[2] = mark_sums[3 * p + 2];
+            }
+            sel = rtsel::selected(rule, x, y, mask ? mask[p] : 1u, n_b, S_b, n_a, S_a);
         }
-        sel = rtsel::selected(rule, x, y, mask ? mask[p] : 1u, n_b, S_b, n_a, S_a);
     }
     const unsigned long long m = __ballot(sel);
     if (lane == 0) wave_n[wave] = (unsigned)__popcll(m);
@@ -1924,6 +2008,10 @@ constexpr uint32_t kAccumVersion = 1;
 // pad[0], and fast records (pixel, next sample, total x, y | total z, open x, y, z) verbatim.
 constexpr char kFastAccumMagic[8] = {'R', 'T', 'F', 'A', 'C', 'C', 'U', 'M'};
 constexpr uint32_t kFastAccumVersion = 1;
+// A moments accumulator's file: its own magic (version 1), the fast file's header and records, then
+// the moment records (total2 x, y, z, open2 x | open2 y, z, 0, 0) verbatim.
+constexpr char kMomentAccumMagic[8] = {'R', 'T', 'M', 'A', 'C', 'C', 'U', 'M'};
+constexpr uint32_t kMomentAccumVersion = 1;
 struct AccumHeader {
     char magic[8];
     uint32_t version;
@@ -1988,15 +2076,15 @@ void accum_release(rt_accum *a) {
         DeviceGuard guard(a->p.device);
         for (void *b : {(void *)a->chain, (void *)a->sums, (void *)a->rgb, (void *)a->mark_sums, (void *)a->mark_counts,
                         (void *)a->sel_list, (void *)a->sel_blocks, (void *)a->sel_out, (void *)a->sel_mask, (void *)a->counts,
-                        (void *)a->gbuf, a->dn_ws, (void *)a->dn_mean})
+                        (void *)a->gbuf, a->dn_ws, (void *)a->dn_mean, (void *)a->mom, (void *)a->moments, (void *)a->var})
             if (b) (void)hipFree(b);
     }
     delete a;
 }
 
 // Host-side part of create / load: parameters and shard, no device call.
-// `fast`: a fast accumulator (p->fast_chunk its chunk size, 0 = 2).
-int accum_new(rt_scene *s, const rt_params *p, const char *who, rt_accum **out, bool fast = false) {
+// `fast`: a fast accumulator (p->fast_chunk its chunk size, 0 = 2); `moments`: one with moments.
+int accum_new(rt_scene *s, const rt_params *p, const char *who, rt_accum **out, bool fast = false, bool moments = false) {
     if (int rc = fast ? accum_check_params_fast(p, who) : accum_check_params(p, who)) return rc;
     if (p->device < 0 || p->device >= kRtMaxDevices) return rt_fail(RT_ERR_ARG, std::string(who) + ": bad device " + std::to_string(p->device));
     Shard sh;
@@ -2014,6 +2102,7 @@ int accum_new(rt_scene *s, const rt_params *p, const char *who, rt_accum **out, 
         a->fast_c = p->fast_chunk > 0 ? p->fast_chunk : 2;
         a->p.flags = RT_FLAG_FAST;
         a->p.fast_chunk = a->fast_c;
+        a->has_moments = moments;
     }
     *out = a;
     return RT_OK;
@@ -2026,6 +2115,12 @@ int accum_alloc(rt_accum *a) {
     const size_t n = (size_t)std::max<long long>(a->n_pixels, 1);
     HIP_TRY(hipMalloc((void **)&a->chain, n * 32));
     HIP_TRY(hipMalloc((void **)&a->sums, n * 3 * sizeof(float)));
+    if (a->has_moments) {   // (zero words: no samples, total2 and open2 +0.f)
+        HIP_TRY(hipMalloc((void **)&a->mom, n * 32));
+        HIP_TRY(hipMalloc((void **)&a->moments, n * 3 * sizeof(float)));
+        HIP_TRY(hipMemset(a->mom, 0, n * 32));
+        HIP_TRY(hipMemset(a->moments, 0, n * 3 * sizeof(float)));
+    }
     return RT_OK;
 }
 
@@ -2053,11 +2148,11 @@ int accum_counts_launch(rt_accum *a, int32_t *d_counts, hipStream_t stream) {
 }
 
 // rt_accum_create and rt_accum_create_fast (`who` names the entry in messages).
-int accum_create(rt_scene *s, const rt_params *p, rt_accum **out, const std::string &who, bool fast) {
+int accum_create(rt_scene *s, const rt_params *p, rt_accum **out, const std::string &who, bool fast, bool moments = false) {
     if (!s || !p || !out) return rt_fail(RT_ERR_ARG, who + ": NULL argument");
     *out = nullptr;
     rt_accum *a = nullptr;
-    if (int rc = accum_new(s, p, who.c_str(), &a, fast)) return rc;
+    if (int rc = accum_new(s, p, who.c_str(), &a, fast, moments)) return rc;
     if (!s->dev[a->p.device]) {
         accum_release(a);
         return rt_fail(RT_ERR_ARG, who + ": scene not uploaded to device " + std::to_string(p->device));
@@ -2093,6 +2188,8 @@ int fast_launch(rt_accum *a, int from, int target, const int *items, long long n
     cp.n_items = n_items;
     cp.fast_c = a->fast_c;
     cp.fast_units = rtfu::units_of(from, target, a->fast_c);
+    cp.mom = a->mom;
+    cp.moments = a->moments;
     return launch(a->scene, &p, a->sums, stream, st, &cp);
 }
 
@@ -2132,6 +2229,24 @@ int rt_accum_create_fast(rt_scene *s, const rt_params *p, rt_accum **out) {
 }
 
 int32_t rt_accum_fast_chunk(const rt_accum *a) { return a ? a->fast_c : 0; }
+
+int rt_accum_create_fast_moments(rt_scene *s, const rt_params *p, rt_accum **out) {
+    return accum_create(s, p, out, "rt_accum_create_fast_moments", true, true);
+}
+
+int32_t rt_accum_has_moments(const rt_accum *a) { return a && a->has_moments ? 1 : 0; }
+
+int rt_accum_moments(rt_accum *a, float *out) {
+    if (!a || !out) return rt_fail(RT_ERR_ARG, "rt_accum_moments: NULL argument");
+    if (!a->has_moments) return rt_fail(RT_ERR_ARG, "rt_accum_moments: the accumulator keeps no moments (rt_accum_create_fast_moments)");
+    DeviceGuard guard(a->p.device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = accum_wait(a)) return rc;
+    HIP_TRY(hipMemcpy(out, a->moments, (size_t)a->n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+const float *rt_accum_device_moments(rt_accum *a) { return a && a->has_moments ? a->moments : nullptr; }
 
 int rt_accum_add(rt_accum *a, int32_t n_samples, void *stream, rt_stats *st) {
     if (!a) return rt_fail(RT_ERR_ARG, "rt_accum_add: NULL accumulator");
@@ -2179,18 +2294,22 @@ int rt_accum_mark(rt_accum *a, void *stream) {
     return RT_OK;
 }
 
-int rt_accum_select(rt_accum *a, const rt_select *sel, void *stream, int64_t *n_selected) {
+// rt_accum_select and, with `variance`, rt_accum_select_variance (`who` names the entry in messages).
+static int accum_select(rt_accum *a, const rt_select *sel, void *stream, int64_t *n_selected, const std::string &who,
+                        bool variance) {
     // every argument check comes before any device call
-    if (!sel) return rt_fail(RT_ERR_ARG, "rt_accum_select: NULL selection");
+    if (!sel) return rt_fail(RT_ERR_ARG, who + ": NULL selection");
     const rtsel::Rule rule{sel->target, sel->x0, sel->y0, sel->x1, sel->y1, sel->threshold};
     const int bad = rtsel::check_rule(rule, a ? a->scene->width : INT32_MAX, a ? a->scene->height : INT32_MAX);
-    if (bad == 2) return rt_fail(RT_ERR_LIMIT, "rt_accum_select: target must be < 2^20");
+    if (bad == 2) return rt_fail(RT_ERR_LIMIT, who + ": target must be < 2^20");
     if (bad == 1)
-        return rt_fail(RT_ERR_ARG, rule.target < 1 ? std::string("rt_accum_select: target must be >= 1")
-                                                   : "rt_accum_select: bad window [" + std::to_string(rule.x0) + ", " +
+        return rt_fail(RT_ERR_ARG, rule.target < 1 ? who + ": target must be >= 1"
+                                                   : who + ": bad window [" + std::to_string(rule.x0) + ", " +
                                                          std::to_string(rule.x1) + ") x [" + std::to_string(rule.y0) + ", " +
                                                          std::to_string(rule.y1) + ")");
-    if (!a) return rt_fail(RT_ERR_ARG, "rt_accum_select: NULL accumulator");
+    if (!a) return rt_fail(RT_ERR_ARG, who + ": NULL accumulator");
+    if (variance && !a->has_moments)
+        return rt_fail(RT_ERR_ARG, who + ": the accumulator keeps no moments (rt_accum_create_fast_moments)");
     a->sel_pending = false;
     DeviceGuard guard(a->p.device);
     if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
@@ -2208,15 +2327,16 @@ int rt_accum_select(rt_accum *a, const rt_select *sel, void *stream, int64_t *n_
     if (n > 0) {
         HIP_TRY(hipMemcpyAsync(a->sel_out, &so, sizeof so, hipMemcpyHostToDevice, a->stream));
         const uint8_t *mask = sel->mask ? a->sel_mask : nullptr;
-        const float *ms = a->has_mark ? a->mark_sums : nullptr;
-        const int32_t *mc = a->has_mark ? a->mark_counts : nullptr;
-        hipLaunchKernelGGL(rt_select_kernel<false>, dim3((unsigned)nb), dim3(256), 0, a->stream, a->geom, rule,
-                           (const uint4 *)a->chain, (const float *)a->sums, ms, mc, mask, a->sel_blocks, a->sel_list,
-                           (SelectOut *)a->sel_out);
+        // (the variance form reads the reported moments through the mark sums' argument, and no mark)
+        const float *ms = variance ? a->moments : a->has_mark ? a->mark_sums : nullptr;
+        const int32_t *mc = !variance && a->has_mark ? a->mark_counts : nullptr;
+        const auto count_kernel = variance ? &rt_select_kernel<false, true> : &rt_select_kernel<false>;
+        const auto write_kernel = variance ? &rt_select_kernel<true, true> : &rt_select_kernel<true>;
+        hipLaunchKernelGGL(count_kernel, dim3((unsigned)nb), dim3(256), 0, a->stream, a->geom, rule, (const uint4 *)a->chain,
+                           (const float *)a->sums, ms, mc, mask, a->sel_blocks, a->sel_list, (SelectOut *)a->sel_out);
         hipLaunchKernelGGL(rt_select_scan_kernel, dim3(1), dim3(256), 0, a->stream, a->sel_blocks, nb);
-        hipLaunchKernelGGL(rt_select_kernel<true>, dim3((unsigned)nb), dim3(256), 0, a->stream, a->geom, rule,
-                           (const uint4 *)a->chain, (const float *)a->sums, ms, mc, mask, a->sel_blocks, a->sel_list,
-                           (SelectOut *)a->sel_out);
+        hipLaunchKernelGGL(write_kernel, dim3((unsigned)nb), dim3(256), 0, a->stream, a->geom, rule, (const uint4 *)a->chain,
+                           (const float *)a->sums, ms, mc, mask, a->sel_blocks, a->sel_list, (SelectOut *)a->sel_out);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&so, a->sel_out, sizeof so, hipMemcpyDeviceToHost, a->stream));
         if (int rc = accum_wait(a)) return rc;
@@ -2232,6 +2352,14 @@ int rt_accum_select(rt_accum *a, const rt_select *sel, void *stream, int64_t *n_
     a->sel_pending = true;
     if (n_selected) *n_selected = a->sel_n;
     return RT_OK;
+}
+
+int rt_accum_select(rt_accum *a, const rt_select *sel, void *stream, int64_t *n_selected) {
+    return accum_select(a, sel, stream, n_selected, "rt_accum_select", false);
+}
+
+int rt_accum_select_variance(rt_accum *a, const rt_select *sel, void *stream, int64_t *n_selected) {
+    return accum_select(a, sel, stream, n_selected, "rt_accum_select_variance", true);
 }
 
 int rt_accum_selection(rt_accum *a, int32_t *out_pixels) {
@@ -2384,10 +2512,20 @@ int rt_accum_save(rt_accum *a, const char *path) {
         h.version = kFastAccumVersion;
         h.pad[0] = (uint32_t)a->fast_c;
     }
+    std::vector<uint32_t> mom;
+    if (a->has_moments) {   // (accum_records waited for the last pass)
+        std::memcpy(h.magic, kMomentAccumMagic, 8);
+        h.version = kMomentAccumVersion;
+        mom.resize((size_t)a->n_pixels * 8);
+        DeviceGuard guard(a->p.device);
+        if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+        if (a->n_pixels) HIP_TRY(hipMemcpy(mom.data(), a->mom, mom.size() * 4, hipMemcpyDeviceToHost));
+    }
     std::FILE *f = std::fopen(path, "wb");
     if (!f) return rt_fail(RT_ERR_IO, std::string("rt_accum_save: cannot write ") + path);
     bool ok = std::fwrite(&h, sizeof h, 1, f) == 1;
     ok = ok && (rec.empty() || std::fwrite(rec.data(), 4, rec.size(), f) == rec.size());
+    ok = ok && (mom.empty() || std::fwrite(mom.data(), 4, mom.size(), f) == mom.size());
     ok = (std::fclose(f) == 0) && ok;
     if (!ok) return rt_fail(RT_ERR_IO, std::string("rt_accum_save: short write to ") + path);
     return RT_OK;
@@ -2403,13 +2541,15 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
     AccumHeader h;
     std::vector<uint32_t> rec;
     int rc = RT_OK;
-    bool fast = false;   // (the magic says which kind the file holds)
+    bool fast = false, moments = false;   // (the magic says which kind the file holds)
+    std::vector<uint32_t> mom;
     if (std::fread(&h, sizeof h, 1, f) != 1) rc = rt_fail(RT_ERR_FORMAT, who + ": shorter than its header");
-    else if (!(fast = std::memcmp(h.magic, kFastAccumMagic, 8) == 0) && std::memcmp(h.magic, kAccumMagic, 8) != 0)
+    else if (!(fast = (moments = std::memcmp(h.magic, kMomentAccumMagic, 8) == 0) || std::memcmp(h.magic, kFastAccumMagic, 8) == 0) &&
+             std::memcmp(h.magic, kAccumMagic, 8) != 0)
         rc = rt_fail(RT_ERR_FORMAT, who + ": not an accumulator file (magic)");
-    else if (h.version != (fast ? kFastAccumVersion : kAccumVersion))
+    else if (h.version != (moments ? kMomentAccumVersion : fast ? kFastAccumVersion : kAccumVersion))
         rc = rt_fail(RT_ERR_FORMAT, who + ": version " + std::to_string(h.version) + ", this library reads " +
-                                        std::to_string(fast ? kFastAccumVersion : kAccumVersion));
+                                        std::to_string(moments ? kMomentAccumVersion : fast ? kFastAccumVersion : kAccumVersion));
     else if (fast && (h.pad[0] < 1u || h.pad[0] > (uint32_t)INT32_MAX))
         rc = rt_fail(RT_ERR_FORMAT, who + ": bad chunk size " + std::to_string(h.pad[0]));
     else if (h.n_pixels < 0 || h.n_pixels > INT32_MAX || h.samples < 0 || h.samples >= (1 << 20))
@@ -2419,14 +2559,19 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
     else {
         std::fseek(f, 0, SEEK_END);
         const long long len = (long long)std::ftell(f);
-        if (len != (long long)sizeof h + h.n_pixels * 32)
-            rc = rt_fail(RT_ERR_FORMAT, who + ": " + std::to_string(len) + " bytes, expected " +
-                                            std::to_string((long long)sizeof h + h.n_pixels * 32));
+        const long long want_len = (long long)sizeof h + h.n_pixels * (moments ? 64 : 32);
+        if (len != want_len)
+            rc = rt_fail(RT_ERR_FORMAT, who + ": " + std::to_string(len) + " bytes, expected " + std::to_string(want_len));
         else {
             std::fseek(f, (long)sizeof h, SEEK_SET);
             rec.resize((size_t)h.n_pixels * 8);
             if (!rec.empty() && std::fread(rec.data(), 4, rec.size(), f) != rec.size())
                 rc = rt_fail(RT_ERR_IO, who + ": read failed");
+            if (moments && rc == RT_OK) {
+                mom.resize((size_t)h.n_pixels * 8);
+                if (!mom.empty() && std::fread(mom.data(), 4, mom.size(), f) != mom.size())
+                    rc = rt_fail(RT_ERR_IO, who + ": read failed");
+            }
         }
     }
     std::fclose(f);
@@ -2451,7 +2596,7 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
     p.device = device;
     rt_accum *a = nullptr;
     if (fast) p.fast_chunk = (int)h.pad[0];
-    if (int rc2 = accum_new(s, &p, "rt_accum_load", &a, fast)) return rc2;
+    if (int rc2 = accum_new(s, &p, "rt_accum_load", &a, fast, moments)) return rc2;
     if (a->n_pixels != h.n_pixels) {
         const long long have = a->n_pixels;
         accum_release(a);
@@ -2469,6 +2614,11 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
         if (fast && !rtfu::open_words_fit(nx, a->fast_c, &rec[8 * k + 5])) {
             accum_release(a);
             return rt_fail(RT_ERR_FORMAT, who + ": record " + std::to_string(k) + " holds an open partial at a chunk boundary");
+        }
+        if (moments && !rtmo::record_words_fit(nx, a->fast_c, &mom[8 * k])) {
+            accum_release(a);
+            return rt_fail(RT_ERR_FORMAT, who + ": moment record " + std::to_string(k) +
+                                              " holds an open partial or pad words at a chunk boundary");
         }
         lo = std::min(lo, nx);
         hi = std::max(hi, nx);
@@ -2491,6 +2641,17 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
         }
         hipError_t e = hipMemcpy(a->chain, rec.data(), rec.size() * 4, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(a->sums, sums.data(), sums.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess && moments) {   // the moment records, and their reported values as the fold kernel writes them
+            for (long long k = 0; k < h.n_pixels; ++k) {
+                rtfu::Rec r;
+                r.next = (int)rec[8 * k + 1];
+                std::memcpy(r.total, &mom[8 * k], 12);
+                std::memcpy(r.open, &mom[8 * k + 3], 12);
+                rtfu::reported(r, a->fast_c, &sums[3 * k]);
+            }
+            e = hipMemcpy(a->mom, mom.data(), mom.size() * 4, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemcpy(a->moments, sums.data(), sums.size() * 4, hipMemcpyHostToDevice);
+        }
         if (e != hipSuccess) rc = rt_fail(RT_ERR_DEVICE, std::string("rt_accum_load: ") + hipGetErrorString(e));
     }
     if (rc) {
@@ -3032,6 +3193,78 @@ int rt_accum_frame_u8_guided(rt_accum *a, const rt_denoise_guided_params *params
         },
         [&](const int32_t *counts, int spp, int W, int H) {
             return denoise_guided_launch(&a->dn_ws, &a->dn_ws_bytes, a->sums, counts, spp, W, H, (const float *)a->gbuf, nullptr, dp,
+                                         a->dn_mean, nullptr, a->stream);
+        });
+}
+
+}  // extern "C"
+
+namespace {
+
+// rt_variance_kernel on the current device.
+int variance_launch(const float *d_sums, const float *d_moments, const int32_t *d_counts, int spp, long long n, const float *d_g,
+                    float *d_out, hipStream_t stream) {
+    if (n == 0) return RT_OK;
+    hipLaunchKernelGGL(rt_variance_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_sums, d_moments, d_counts,
+                       spp, n, (const float4 *)d_g, d_out);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// A moments accumulator's measured variance into a->var on a->stream (the current device is the
+// accumulator's): its own counts, and its shard's first-hit records, rendered on first use.
+int accum_variance_launch(rt_accum *a) {
+    if (int rc = accum_buffer(a->var, (size_t)a->n_pixels)) return rc;
+    if (int rc = accum_buffer(a->gbuf, (size_t)a->n_pixels * rtd::kGbufferQuads)) return rc;
+    if (!a->gbuf_ready) {
+        if (int rc = gbuffer_launch(a->scene->dev[a->p.device], a->geom, a->gbuf, a->stream)) return rc;
+        a->gbuf_ready = true;
+    }
+    const int32_t *counts = nullptr;
+    if (!accum_uniform(a)) {
+        if (int rc = accum_buffer(a->counts, (size_t)a->n_pixels)) return rc;
+        if (int rc = accum_counts_launch(a, a->counts, a->stream)) return rc;
+        counts = a->counts;
+    }
+    return variance_launch(a->sums, a->moments, counts, a->samples, a->n_pixels, (const float *)a->gbuf, a->var, a->stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_variance_from_moments_device(const float *d_sums, const float *d_moments, const int32_t *d_counts, int32_t spp,
+                                    int32_t width, int32_t height, const float *d_gbuffer, float *d_out, void *stream) {
+    if (int rc = rt_variance_check("rt_variance_from_moments_device", d_sums, d_moments, d_counts, spp, width, height, d_gbuffer, d_out))
+        return rc;
+    return variance_launch(d_sums, d_moments, d_counts, spp, (long long)width * height, d_gbuffer, d_out, (hipStream_t)stream);
+}
+
+int rt_accum_variance(rt_accum *a, float *out) {
+    if (!a || !out) return rt_fail(RT_ERR_ARG, "rt_accum_variance: NULL argument");
+    if (!a->has_moments) return rt_fail(RT_ERR_ARG, "rt_accum_variance: the accumulator keeps no moments (rt_accum_create_fast_moments)");
+    if (a->n_pixels == 0) return RT_OK;
+    DeviceGuard guard(a->p.device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = accum_variance_launch(a)) return rc;
+    if (int rc = accum_wait(a)) return rc;
+    HIP_TRY(hipMemcpy(out, a->var, (size_t)a->n_pixels * sizeof(float), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_accum_frame_u8_guided_measured(rt_accum *a, const rt_denoise_guided_params *params, uint8_t *out_rgb) {
+    if (a && !a->has_moments)
+        return rt_fail(RT_ERR_ARG, "rt_accum_frame_u8_guided_measured: the accumulator keeps no moments (rt_accum_create_fast_moments)");
+    rtdg::Params dp;
+    return accum_filtered_frame(
+        a, "rt_accum_frame_u8_guided_measured", "rt_denoise_guided_device", out_rgb,
+        [&](int spp, int W, int H) {
+            return rt_denoise_guided_check("rt_accum_frame_u8_guided_measured", a->sums, nullptr, spp, W, H, a->sums, params, a->sums,
+                                           &dp);
+        },
+        [&](const int32_t *counts, int spp, int W, int H) {   // (the G-buffer is rendered by now: the variance reuses it)
+            if (int rc = accum_variance_launch(a)) return rc;
+            return denoise_guided_launch(&a->dn_ws, &a->dn_ws_bytes, a->sums, counts, spp, W, H, (const float *)a->gbuf, a->var, dp,
                                          a->dn_mean, nullptr, a->stream);
         });
 }

@@ -20,6 +20,7 @@
 #include "rt_denoise.h"
 #include "rt_denoise_guided.h"
 #include "rt_json.h"
+#include "rt_moments.h"
 #include "rt_scene.h"
 #include "rt_select.h"
 #include "rt_vec.h"
@@ -953,6 +954,17 @@ int rt_denoise_guided(const float *sums, const int32_t *counts, int32_t spp, int
     return RT_OK;
 }
 
+// The measured variance on the host (rt_moments.h is its text): per pixel, from its sum, its
+// moment, its count and its first-hit record.
+int rt_variance_from_moments(const float *sums, const float *moments, const int32_t *counts, int32_t spp, int32_t width,
+                             int32_t height, const float *gbuffer, float *out) {
+    if (int rc = rt_variance_check("rt_variance_from_moments", sums, moments, counts, spp, width, height, gbuffer, out)) return rc;
+    const int64_t n = (int64_t)width * height;
+    for (int64_t p = 0; p < n; ++p)
+        out[p] = rtmo::variance_of_pixel(counts ? counts[p] : spp, sums + 3 * p, moments + 3 * p, gbuffer + 16 * p);
+    return RT_OK;
+}
+
 int rt_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t height) {
     if (!path || !rgb || width <= 0 || height <= 0) return rt_fail(RT_ERR_ARG, "rt_write_ppm: bad argument");
     std::FILE *f = std::fopen(path, "wb");
@@ -997,6 +1009,16 @@ int rt_denoise_guided_check(const char *who, const float *sums, const int32_t *c
     if (rtdg::resolve_params(p.iterations, p.sigma_var, p.sigma_plane, p.normal_power_log2, p.firefly, *resolved))
         return rt_fail(RT_ERR_ARG, w + ": iterations above " + std::to_string(rtdn::kMaxIterations) + ", normal_power_log2 above " +
                                        std::to_string(rtdn::kMaxNormalPowerLog2) + " or a non-finite sigma or firefly factor");
+    return RT_OK;
+}
+
+int rt_variance_check(const char *who, const float *sums, const float *moments, const int32_t *counts, int32_t spp, int32_t width,
+                      int32_t height, const float *gbuffer, const float *out) {
+    const std::string w = who;
+    if (!sums || !moments || !gbuffer || !out) return rt_fail(RT_ERR_ARG, w + ": NULL argument");
+    if (width <= 0 || height <= 0) return rt_fail(RT_ERR_ARG, w + ": bad frame size");
+    if (!counts && spp < 1) return rt_fail(RT_ERR_ARG, w + ": without counts, spp must be at least 1");
+    if ((int64_t)width * height > INT32_MAX) return rt_fail(RT_ERR_LIMIT, w + ": frames above 2^31 pixels are not supported");
     return RT_OK;
 }
 

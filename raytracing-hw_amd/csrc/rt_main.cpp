@@ -27,6 +27,16 @@
 //                       fast_chunk = c.  With RT_PASS_SPP and / or RT_ADAPT: the passes run on fast
 //                       accumulators (rt_accum_create_fast) with chunk size c; a checkpoint resumes
 //                       only into the kind and chunk size that wrote it.
+// Measured variance (per-sample second moments; unset, every byte written is the one above):
+//   RT_MOMENTS=1        needs RT_FAST and a pass mode (RT_PASS_SPP or RT_ADAPT): the passes run on
+//                       moments accumulators (rt_accum_create_fast_moments).  With RT_DENOISE_GUIDED
+//                       every frame written is filtered with the measured variance
+//                       (rt_accum_frame_u8_guided_measured; several GPUs: each shard's
+//                       rt_accum_variance gathered like its sums).  With RT_ADAPT the rounds select by
+//                       the relative standard error (rt_accum_select_variance) and set no mark.  A
+//                       checkpoint of such a run resumes only into such a run with the same chunk.
+//   RT_VARIANCE_OUT=path  (with RT_MOMENTS) the measured variance of the final frame as a
+//                       one-channel PFM ("Pf", scale -1: little-endian floats, bottom row first).
 // Denoising and feature images (rt_denoise*, rt_gbuffer; unset, the bytes are the ones above):
 //   RT_DENOISE=k        every frame the run writes (the one-shot frame, each pass's preview, the
 //                       adaptive result) passes through the edge-avoiding a-trous filter with k
@@ -73,15 +83,19 @@ static std::vector<float> frame_gbuffer(rt_scene *scene, int width, int height) 
 // defaults), or none.
 struct Denoise {
     bool on = false, guided = false;
+    bool measured = false;   // (RT_MOMENTS with the guided mode: the filter's variance input is the measured one)
     rt_denoise_params params{-1, 0.f, 0.f, 0};
     rt_denoise_guided_params guided_params{-1, 0.f, 0.f, 0, 0.f};
     std::vector<float> gbuffer;   // the frame's, rendered at the first frame that needs it
 
     int accum_frame(rt_accum *acc, uint8_t *rgb) const {
+        if (guided && measured) return rt_accum_frame_u8_guided_measured(acc, &guided_params, rgb);
         return guided ? rt_accum_frame_u8_guided(acc, &guided_params, rgb) : rt_accum_frame_u8_denoised(acc, &params, rgb);
     }
-    int frame(const float *sums, const int32_t *counts, int spp, int width, int height, uint8_t *rgb) const {
-        return guided ? rt_denoise_guided_frame_u8(sums, counts, spp, width, height, gbuffer.data(), nullptr, &guided_params, 0, rgb)
+    // (variance: the frame's measured variance, or NULL for the filter's own estimate)
+    int frame(const float *sums, const int32_t *counts, int spp, int width, int height, uint8_t *rgb,
+              const float *variance = nullptr) const {
+        return guided ? rt_denoise_guided_frame_u8(sums, counts, spp, width, height, gbuffer.data(), variance, &guided_params, 0, rgb)
                       : rt_denoise_frame_u8(sums, counts, spp, width, height, gbuffer.data(), &params, 0, rgb);
     }
 };
@@ -119,9 +133,11 @@ static void write_aovs(const std::string &prefix, const std::vector<float> &g, i
 
 // The frame in passes: device d renders shard (rank d, world n) through its own accumulator.
 // `adapt` (RT_ADAPT): its threshold; the passes are then those of adaptive rendering (above).
+// `moments` (RT_MOMENTS): on moments accumulators; `variance_out` (RT_VARIANCE_OUT): the PFM's path.
 static void render_passes(rt_scene *scene, int width, int height, int samples, int n_gpus, int pass_spp,
                           const char *ckpt, const std::string &output, const float *adapt = nullptr,
-                          const char *counts_out = nullptr, int fast_chunk = 0, Denoise *dn = nullptr) {
+                          const char *counts_out = nullptr, int fast_chunk = 0, Denoise *dn = nullptr,
+                          bool moments = false, const char *variance_out = nullptr) {
     const int n = n_gpus > 0 ? n_gpus : rt_device_count();
     if (n < 1) throw std::runtime_error("no HIP device");
     if (samples < 1) throw std::runtime_error("samples per pixel must be >= 1");
@@ -142,11 +158,13 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
         if (resume) {
             check(rt_accum_load(scene, r, file_of(r).c_str(), &acc[(size_t)r]));
             const int have = rt_accum_fast_chunk(acc[(size_t)r]);
-            if (have != fast_chunk)
+            const bool have_moments = rt_accum_has_moments(acc[(size_t)r]) != 0;
+            if (have != fast_chunk || have_moments != moments)
                 throw std::runtime_error("checkpoint " + file_of(r) + " holds " +
                                          (have ? "a fast accumulator with chunks of " + std::to_string(have) : std::string("a parity accumulator")) +
-                                         ", the run asks for " +
-                                         (fast_chunk ? "RT_FAST=" + std::to_string(fast_chunk) : std::string("parity passes (RT_FAST unset)")));
+                                         (have_moments ? " and moments" : "") + ", the run asks for " +
+                                         (fast_chunk ? "RT_FAST=" + std::to_string(fast_chunk) : std::string("parity passes (RT_FAST unset)")) +
+                                         (moments ? " with RT_MOMENTS" : have_moments ? " without RT_MOMENTS" : ""));
         } else {
             check(rt_scene_upload(scene, r));
             rt_params p{};
@@ -155,7 +173,9 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
             p.row_block = 8;
             p.device = r;
             p.fast_chunk = fast_chunk;
-            check(fast_chunk ? rt_accum_create_fast(scene, &p, &acc[(size_t)r]) : rt_accum_create(scene, &p, &acc[(size_t)r]));
+            check(moments      ? rt_accum_create_fast_moments(scene, &p, &acc[(size_t)r])
+                  : fast_chunk ? rt_accum_create_fast(scene, &p, &acc[(size_t)r])
+                               : rt_accum_create(scene, &p, &acc[(size_t)r]));
         }
     }
     int done = rt_accum_samples(acc[0]);
@@ -172,6 +192,18 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
     std::vector<int32_t> rows((size_t)height);
     std::vector<float> sums, spart;
     std::vector<int32_t> counts, cshard;
+    std::vector<float> variance, vpart;
+    auto gather_variance = [&]() {   // every shard's measured variance in frame order
+        variance.resize((size_t)width * height);
+        for (int r = 0; r < n; ++r) {
+            const int64_t k = rt_shard_rows(height, r, n, 8, rows.data());
+            if (k < 0) check((int)k);
+            vpart.resize((size_t)k * width);
+            check(rt_accum_variance(acc[(size_t)r], vpart.data()));
+            for (int64_t i = 0; i < k; ++i)
+                std::copy(vpart.begin() + i * width, vpart.begin() + (i + 1) * width, variance.begin() + (size_t)rows[(size_t)i] * width);
+        }
+    };
     auto write_frame = [&]() {
         if (dn && dn->on && n == 1) {   // the accumulator owns the whole frame: filtered where it lives
             check(dn->accum_frame(acc[0], rgb.data()));
@@ -197,7 +229,9 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
             }
             // (after rt_accum_sums has waited for every shard's pass: nothing else runs on device 0)
             if (dn->gbuffer.empty()) dn->gbuffer = frame_gbuffer(scene, width, height);
-            check(dn->frame(sums.data(), counts.data(), 0, width, height, rgb.data()));
+            if (dn->guided && dn->measured) gather_variance();
+            check(dn->frame(sums.data(), counts.data(), 0, width, height, rgb.data(),
+                            dn->guided && dn->measured ? variance.data() : nullptr));
             check(rt_write_ppm(output.c_str(), rgb.data(), width, height));
             return;
         }
@@ -216,6 +250,17 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
         if (ckpt)
             for (int r = 0; r < n; ++r) check(rt_accum_save(acc[(size_t)r], file_of(r).c_str()));
     };
+    auto write_variance = [&]() {   // RT_VARIANCE_OUT: one channel, little-endian floats, bottom row first
+        if (!variance_out) return;
+        gather_variance();
+        std::FILE *f = std::fopen(variance_out, "wb");
+        if (!f) throw std::runtime_error(std::string("RT_VARIANCE_OUT: cannot write ") + variance_out);
+        std::fprintf(f, "Pf\n%d %d\n-1.0\n", width, height);
+        bool ok = true;
+        for (int y = height - 1; y >= 0; --y)
+            ok = ok && std::fwrite(&variance[(size_t)y * width], sizeof(float), (size_t)width, f) == (size_t)width;
+        if (std::fclose(f) != 0 || !ok) throw std::runtime_error(std::string("RT_VARIANCE_OUT: short write to ") + variance_out);
+    };
     if (adapt) {
         const int k = pass_spp > 0 ? pass_spp : 16;
         auto add_all = [&](int m) {
@@ -224,7 +269,8 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
         };
         if (done == 0) {   // (a resumed run goes on with the rounds below; it has no mark: its first round selects by count alone)
             add_all(std::min(k, samples));
-            for (int r = 0; r < n; ++r) check(rt_accum_mark(acc[(size_t)r], nullptr));
+            if (!moments)   // (the variance rule reads no mark)
+                for (int r = 0; r < n; ++r) check(rt_accum_mark(acc[(size_t)r], nullptr));
             if (done < samples) add_all(std::min(k, samples - done));
             std::cout << "Progress: " << done << " / " << samples << " samples" << std::endl;
         }
@@ -235,12 +281,13 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
             int64_t total = 0;
             for (int r = 0; r < n; ++r) {
                 int64_t m = 0;
-                check(rt_accum_select(acc[(size_t)r], &sel, nullptr, &m));
+                check(moments ? rt_accum_select_variance(acc[(size_t)r], &sel, nullptr, &m)
+                              : rt_accum_select(acc[(size_t)r], &sel, nullptr, &m));
                 total += m;
             }
             if (total == 0) break;
             for (int r = 0; r < n; ++r) {
-                check(rt_accum_mark(acc[(size_t)r], nullptr));
+                if (!moments) check(rt_accum_mark(acc[(size_t)r], nullptr));
                 check(rt_accum_add_selected(acc[(size_t)r], nullptr, nullptr));
             }
             done = sel.target;
@@ -249,6 +296,7 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
         }
         write_frame();
         save_all();
+        write_variance();
         if (counts_out) {
             std::vector<int32_t> cpart;
             std::vector<uint8_t> pgm((size_t)width * height * 2);
@@ -283,6 +331,7 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
             for (int r = 0; r < n; ++r) check(rt_accum_save(acc[(size_t)r], file_of(r).c_str()));
         std::cout << "Progress: " << done << " / " << samples << " samples" << std::endl;
     }
+    write_variance();
 }
 
 static int int_arg(const char *s) { return std::stoi(std::string(s).substr(0, std::string(s).find(' '))); }
@@ -336,13 +385,31 @@ int main(int argc, char *argv[]) {
     const char *fast_env = std::getenv("RT_FAST");
     const int fast_chunk = fast_env && *fast_env ? std::atoi(fast_env) : 0;
     if (fast_env && *fast_env && fast_chunk < 1) throw std::runtime_error("RT_FAST must be >= 1");
+    const char *mom_env = std::getenv("RT_MOMENTS"), *var_out = std::getenv("RT_VARIANCE_OUT");
+    const bool moments = mom_env && *mom_env && std::atoi(mom_env) != 0;
+    if (moments && !fast_chunk) {
+        std::cerr << "rt_solution: RT_MOMENTS needs RT_FAST (only fast accumulators keep moments)" << std::endl;
+        rt_scene_free(scene);
+        return 1;
+    }
+    if (moments && !(pass_env && *pass_env) && !adaptive) {
+        std::cerr << "rt_solution: RT_MOMENTS needs a pass mode (RT_PASS_SPP or RT_ADAPT): moments live in accumulators" << std::endl;
+        rt_scene_free(scene);
+        return 1;
+    }
+    if (var_out && *var_out && !moments) {
+        std::cerr << "rt_solution: RT_VARIANCE_OUT needs RT_MOMENTS" << std::endl;
+        rt_scene_free(scene);
+        return 1;
+    }
+    dn.measured = moments;
     if ((pass_env && *pass_env) || (ckpt && *ckpt) || adaptive) {
         const int pass_spp = pass_env && *pass_env ? std::atoi(pass_env) : 0;
         if (pass_env && *pass_env && pass_spp < 1) throw std::runtime_error("RT_PASS_SPP must be >= 1");
         try {
             render_passes(scene, width, height, samples, n_gpus, pass_spp, ckpt && *ckpt ? ckpt : nullptr, output,
                           adaptive ? &adapt : nullptr, adaptive && counts_out && *counts_out ? counts_out : nullptr,
-                          fast_chunk, &dn);
+                          fast_chunk, &dn, moments, moments && var_out && *var_out ? var_out : nullptr);
             if (aov_out && *aov_out) {
                 if (dn.gbuffer.empty()) dn.gbuffer = frame_gbuffer(scene, width, height);
                 write_aovs(aov_out, dn.gbuffer, width, height);

@@ -54,6 +54,11 @@ struct MegaLaneT {
     unsigned long long work0;   // counting runs: traversal tests before this work unit (its cost)
     Rng rng;
     V3 sum;
+    // A moments pass only (rt_moments.h, rt_mega_kernel MOM): the running partial of the unit's
+    // squared sample colours, in registers.  Measured against LDS beside mega_lds_sum (3 KB more per
+    // block: one wave per SIMD fewer, +9.2% on a pass) and against adding in place in the partial
+    // buffer (+1.1%): +0.95%.  Dropped, like the fields above, where unused.
+    V3 sum2;
     Ray r;
     TS T;
     uint32_t wbase;   // threadIdx.x of the wave's lane 0 (uniform: an SGPR; RT_TID_REMAT)
@@ -306,6 +311,9 @@ enum QueueWord : int {
     kQueueParkList = 4,   // address of the park list (written when the workspace is made)
     kQueueResumeMap = 5,  // address of the resume launch's item -> slot map, 0 = slot order
     kChainWord = 16,      // address of the accumulator's chain buffer (its own 128-byte line)
+    kMomentWord = 17,     // a moments pass: address of the accumulator's moment records (the chain word's line)
+    kMomentPartWord = 18, // a moments pass: where the units' partials of squares start, 3 * n_items floats
+                          // into the partial buffer; unit q's at 3 * q
     kQueueWords = 32,
 };
 // The counter block (rt_wavefront.h Counters as 64-bit words, counters_flush): the render's at
@@ -358,6 +366,22 @@ __device__ __forceinline__ FastRec fast_rec(const uint4 *chain, long long p) {
     q.r.open[2] = __uint_as_float(b.w);
     return q;
 }
+// A moments accumulator's second record per pixel, in a buffer of its own (rt_moments.h): 32 bytes,
+// (total2 x, y, z, open2 x | open2 y, z, 0, 0); its `next` is the fast record's.
+__device__ __forceinline__ void moment_rec(const uint4 *mom, long long p, rtfu::Rec &r) {
+    const uint4 a = mom[2 * p], b = mom[2 * p + 1];
+    r.total[0] = __uint_as_float(a.x);
+    r.total[1] = __uint_as_float(a.y);
+    r.total[2] = __uint_as_float(a.z);
+    r.open[0] = __uint_as_float(a.w);
+    r.open[1] = __uint_as_float(b.x);
+    r.open[2] = __uint_as_float(b.y);
+}
+__device__ __forceinline__ void moment_rec_store(uint4 *mom, long long p, const rtfu::Rec &r) {
+    mom[2 * p] = make_uint4(__float_as_uint(r.total[0]), __float_as_uint(r.total[1]), __float_as_uint(r.total[2]),
+                            __float_as_uint(r.open[0]));
+    mom[2 * p + 1] = make_uint4(__float_as_uint(r.open[1]), __float_as_uint(r.open[2]), 0u, 0u);
+}
 __device__ __forceinline__ void fast_rec_store(uint4 *chain, long long p, const rtfu::Rec &r) {
     chain[2 * p] = make_uint4((uint32_t)p, (uint32_t)r.next, __float_as_uint(r.total[0]), __float_as_uint(r.total[1]));
     chain[2 * p + 1] = make_uint4(__float_as_uint(r.total[2]), __float_as_uint(r.open[0]), __float_as_uint(r.open[1]),
@@ -369,10 +393,13 @@ __device__ __forceinline__ void fast_rec_store(uint4 *chain, long long p, const 
 // from rt_fast_units.h; one that starts inside a chunk starts from the record's open partial.
 // Returns false, the lane left without a pixel, for a unit past the pixel's own (the launch has
 // the units of the pixel furthest behind): starting a sample there would never reach L.send.
-template <bool COUNT, class ML>
+// MOM (a moments pass): the unit's partial of squares starts from the moment record's open2 exactly
+// where the sum starts from `open` (`queue`: the queue block, for the moment records' address).
+template <bool COUNT, bool MOM = false, class ML>
 __device__ __forceinline__ bool mega_assign_fast_chain(ML &L, const DevScene &sc, const ShardGeom &g, long long q,
                                                        long long n_list, const int *order, int cs, int spp,
-                                                       const NodeRec &root, Counters &cnt, const uint4 *chain) {
+                                                       const NodeRec &root, Counters &cnt, const uint4 *chain,
+                                                       const unsigned long long *queue = nullptr) {
     const int k = (int)(q / n_list);
     const long long i = q - (long long)k * n_list;
     const int p = order ? order[i] : (int)i;
@@ -390,6 +417,14 @@ __device__ __forceinline__ bool mega_assign_fast_chain(ML &L, const DevScene &sc
     L.send = u.s1;
     const bool cont = rtfu::unit_continues(rec.r.next, cs, k);
     lane_sum_set(L, cont ? V3{rec.r.open[0], rec.r.open[1], rec.r.open[2]} : V3{0.f, 0.f, 0.f});
+    if constexpr (MOM) {
+        L.sum2 = V3{0.f, 0.f, 0.f};
+        if (cont) {
+            rtfu::Rec m;
+            moment_rec((const uint4 *)queue[kMomentWord], p, m);
+            L.sum2 = V3{m.open[0], m.open[1], m.open[2]};
+        }
+    }
     L.work0 = cnt.aabb + cnt.tri + cnt.laabb + cnt.ltri;
     int px, py;
     shard_xy(g, p, px, py);
@@ -437,7 +472,9 @@ __device__ void spec_job_end(ML &L, const DevScene &sc, const ShardGeom &g, cons
 // its next sample.
 // `G`: how the pass fetches (rt_path.h SHADE_TABLES / SHADE_GATHER_HOLD), chosen per kernel
 // (rt_device.hip RT_PLAIN_SHADE_GATHER, RT_SPEC_SHADE_GATHER).
-template <bool COUNT, bool FAST = false, bool CHAIN = false, int G = SHADE_TABLES, class Stack, class ML>
+// `MOM` (FAST only, a moments pass): the sample's squared colour is added to the unit's second
+// partial (L.sum2), written at the unit's end to the squares' part of the partial buffer.
+template <bool COUNT, bool FAST = false, bool CHAIN = false, int G = SHADE_TABLES, bool MOM = false, class Stack, class ML>
 __device__ __forceinline__ void mega_shade(ML &L, const DevScene &sc, const ShardGeom &g, const WfState &st,
                                            int spp, float *out, unsigned *cost, const NodeRec &root, Stack &stk,
                                            Counters &cnt, bool tail = false, bool park = false,
@@ -492,13 +529,26 @@ __device__ __forceinline__ void mega_shade(ML &L, const DevScene &sc, const Shar
         spec_job_end<CHAIN>(L, sc, g, st, spp, out, root, fold_path(P, c.nv, shaded), c, queue);
         return;
     }
-    const V3 sm = rtv::add(lane_sum(L), fold_path(P, c.nv, !FAST && shaded));
+    V3 sm;
+    if constexpr (MOM) {   // (q = x * x, one multiply per channel; both partials in sample order)
+        const V3 x = fold_path(P, c.nv, !FAST && shaded);
+        sm = rtv::add(lane_sum(L), x);
+        L.sum2 = rtv::add(L.sum2, rtv::mulv(x, x));
+    } else {
+        sm = rtv::add(lane_sum(L), fold_path(P, c.nv, !FAST && shaded));
+    }
     lane_sum_set(L, sm);
     if (++c.s == (FAST ? L.send : spp)) {
         const long long o = FAST ? L.dst : L.pix;
         out[3 * o + 0] = sm.x;
         out[3 * o + 1] = sm.y;
         out[3 * o + 2] = sm.z;
+        if constexpr (MOM) {   // (the squares' part of the partial buffer: its address in the queue block)
+            float *out2 = (float *)queue[kMomentPartWord];
+            out2[3 * o + 0] = L.sum2.x;
+            out2[3 * o + 1] = L.sum2.y;
+            out2[3 * o + 2] = L.sum2.z;
+        }
         if (COUNT && cost) cost[L.pix] = (unsigned)(cnt.aabb + cnt.tri + cnt.laabb + cnt.ltri - L.work0);
         // (accumulator: the record of the pixel's next pass; the lane's RNG is at the state its
         // last sample ended in)
@@ -649,7 +699,7 @@ __device__ __forceinline__ void mega_shade_split(ML &L, const DevScene &sc, cons
 // One iteration of a wave's main loop for one lane, given the wave's decision: shade the
 // READY lanes this iteration (shade_now), or step the traversing lanes.
 template <bool COUNT, class Stack, class Nodes, bool FAST = false, bool LSPLIT = false, bool CHAIN = false,
-          int G = SHADE_TABLES, class ML>
+          int G = SHADE_TABLES, bool MOM = false, class ML>
 __device__ __forceinline__ void mega_iterate(ML &L, bool shade_now, const DevScene &sc, const ShardGeom &g,
                                              const WfState &st, int spp, float *out, unsigned *cost,
                                              const NodeRec &root, Stack &stk, const Nodes &nodes, Counters &cnt,
@@ -668,7 +718,7 @@ __device__ __forceinline__ void mega_iterate(ML &L, bool shade_now, const DevSce
     }
     if (shade_now) {
         if (L.state == M_READY)
-            mega_shade<COUNT, FAST, CHAIN, G>(L, sc, g, st, spp, out, cost, root, stk, cnt, tail, park, queue);
+            mega_shade<COUNT, FAST, CHAIN, G, MOM>(L, sc, g, st, spp, out, cost, root, stk, cnt, tail, park, queue);
     } else if (L.state == M_TRAV) {
         if (trav_step<COUNT>(sc, L.r, L.T, stk, nodes, cnt)) L.state = M_READY;
     }

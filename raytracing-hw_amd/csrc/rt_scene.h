@@ -54,6 +54,9 @@ struct Params;
 int rt_denoise_guided_check(const char *who, const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
                             const float *gbuffer, const rt_denoise_guided_params *params, const float *out_mean,
                             rtdg::Params *resolved);
+// the same for rt_variance_from_moments and its device form (rt_moments.h), which have no parameters
+int rt_variance_check(const char *who, const float *sums, const float *moments, const int32_t *counts, int32_t spp, int32_t width,
+                      int32_t height, const float *gbuffer, const float *out);
 
 // row partition helper (rt_host.cpp)
 int64_t rt_shard_rows_impl(int32_t height, int32_t rank, int32_t world, int32_t row_block, int32_t *rows_out);
