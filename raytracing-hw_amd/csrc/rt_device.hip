@@ -26,7 +26,9 @@
 // the words of the queue block the host and the kernels share, and rt_mega_prof.h holds the
 // diagnostics build's counters and report (included under RT_MEGA_PROF only).  The whole-frame
 // render (rt_render_frame) takes its devices, row partition and buffer layout from
-// rt_frame_plan.h (host only as well).
+// rt_frame_plan.h (host only as well).  The accumulator (rt_accum_*) takes its kinds, parameter
+// checks, host state and passes from rt_accum_plan.h and its checkpoint file from
+// rt_accum_file.h (both host only).
 //
 // Concurrency: one render per (scene, device) may be in flight at a time (the pixel queue,
 // counters, vertex records and order buffers of a device copy are shared by its launches);
@@ -55,6 +57,8 @@
 #include "rt_launch_plan.h"
 #include "rt_select.h"
 #include "rt_moments.h"
+#include "rt_accum_plan.h"
+#include "rt_accum_file.h"
 #include "rt_frame_plan.h"
 #include "rt_gbuffer.h"
 #include "rt_denoise.h"
@@ -1801,42 +1805,32 @@ int rt_render(rt_scene *s, const rt_params *p, float *out, rt_stats *st) {
 // rt_accum_* (include/rt_hw.h): the per-pixel chain state of one shard on one device, kept
 // between passes (rt_mega.h, chain buffer).  The accumulator owns the chain buffer (32 B per
 // shard pixel) and the float sums its passes write; a pass is launch() with a ChainPass.
-struct rt_accum {
+// Host only, tested without a device: the kinds, parameter checks, host state (rtap::State) and
+// passes in rt_accum_plan.h, the checkpoint file in rt_accum_file.h.
+struct rt_accum : rtap::State {
     rt_scene *scene = nullptr;
     rt_params p{};            // rank, world, row_block, device, flags (normalised)
     long long n_pixels = 0;
     int rows = 0;
     ShardGeom geom{};         // the shard (shard_of)
-    int samples = 0;          // samples done
+    rtap::Kind kind = rtap::Kind::Parity;   // a fast kind's chain buffer holds fast records (rt_mega.h FastRec)
     uint4 *chain = nullptr;   // n_pixels Parked records
     float *sums = nullptr;    // n_pixels x 3
     uint8_t *rgb = nullptr;   // n_pixels x 3, made by the first rt_accum_frame_u8
     hipStream_t stream = nullptr;   // the last pass's stream (host reads wait for it)
-    // Per-pixel sample counts (subset passes): `samples` is the largest count, `min_samples` the
-    // smallest; they are equal until a subset pass leaves some pixels behind.
-    int min_samples = 0;
-    // rt_accum_mark's copy of the sums and counts (made on first use); none after create / load
+    // rt_accum_mark's copy of the sums and counts (made on first use)
     float *mark_sums = nullptr;
     int32_t *mark_counts = nullptr;
-    bool has_mark = false;
-    // rt_accum_select's pending list (shard pixels, ascending; made on first use) and what the
-    // selection kernel reduced with it; dropped by every pass
+    // rt_accum_select's pending list (shard pixels, ascending; made on first use) and its kernel's buffers
     int *sel_list = nullptr;
     unsigned *sel_blocks = nullptr;        // per block of rt_select_kernel: selected count, then list offset
     unsigned long long *sel_out = nullptr; // SelectOut
     uint8_t *sel_mask = nullptr;           // device copy of rt_select.mask
     int32_t *counts = nullptr;             // n_pixels, for the count-aware finish
-    bool sel_pending = false;
-    long long sel_n = 0;
-    unsigned long long sel_samples = 0;
-    int sel_target = 0, sel_min = 0, sel_max = 0, sel_from = 0;
-    // A fast accumulator (rt_accum_create_fast): its chunk size, fixed for its life; 0 = parity.
-    // Its chain buffer then holds fast records (rt_mega.h FastRec).
-    int fast_c = 0;
-    // A moments accumulator (rt_accum_create_fast_moments, rt_moments.h): a fast one that also keeps
-    // per pixel the moment record (32 bytes, rt_mega.h moment_rec) and the reported moment
-    // (n_pixels x 3); both made at creation.  `var`: the measured variance, made on first use.
-    bool has_moments = false;
+    // A moments accumulator (rt_moments.h) also keeps per pixel the moment record (32 bytes,
+    // rt_mega.h moment_rec) and the reported moment (n_pixels x 3); both made at creation.
+    // `var`: the measured variance, made on first use.
+    bool has_moments() const { return kind == rtap::Kind::Moments; }
     uint4 *mom = nullptr;
     float *moments = nullptr;
     float *var = nullptr;
@@ -1999,77 +1993,6 @@ __global__ void __launch_bounds__(256) rt_fast_chain_init_kernel(long long n, ui
 
 namespace {
 
-// The checkpoint file (rt_accum_save): this header, then n_pixels records of 8 words in the
-// chain buffer's layout (pixel, next sample, engine state | cache flag << 31, cached value |
-// sum x, y, z, 0).  Little-endian, as the devices and their hosts are.
-constexpr char kAccumMagic[8] = {'R', 'T', 'A', 'C', 'C', 'U', 'M', '\0'};
-constexpr uint32_t kAccumVersion = 1;
-// A fast accumulator's file: its own magic (version 1), the same header with the chunk size in
-// pad[0], and fast records (pixel, next sample, total x, y | total z, open x, y, z) verbatim.
-constexpr char kFastAccumMagic[8] = {'R', 'T', 'F', 'A', 'C', 'C', 'U', 'M'};
-constexpr uint32_t kFastAccumVersion = 1;
-// A moments accumulator's file: its own magic (version 1), the fast file's header and records, then
-// the moment records (total2 x, y, z, open2 x | open2 y, z, 0, 0) verbatim.
-constexpr char kMomentAccumMagic[8] = {'R', 'T', 'M', 'A', 'C', 'C', 'U', 'M'};
-constexpr uint32_t kMomentAccumVersion = 1;
-struct AccumHeader {
-    char magic[8];
-    uint32_t version;
-    int32_t width, height, ray_depth;
-    int32_t rank, world, row_block;
-    uint32_t n_tris, n_nodes, n_lights;
-    int64_t n_pixels;
-    int32_t samples, reserved;
-    float cam[14];   // cam_pos, cam_axes, tan_half_fov
-    uint32_t pad[2];
-};
-static_assert(sizeof(AccumHeader) == 128, "rt_accum file header is 128 bytes");
-
-void accum_header_fill(const rt_scene *s, AccumHeader &h) {
-    std::memset(&h, 0, sizeof h);
-    std::memcpy(h.magic, kAccumMagic, 8);
-    h.version = kAccumVersion;
-    h.width = s->width;
-    h.height = s->height;
-    h.ray_depth = s->ray_depth;
-    h.n_tris = (uint32_t)(s->tri.size() / 12);
-    h.n_nodes = (uint32_t)(s->node.size() / 8);
-    h.n_lights = (uint32_t)(s->light.size() / 16);
-    std::memcpy(h.cam, s->cam_pos, 12);
-    std::memcpy(h.cam + 3, s->cam_axes, 36);
-    std::memcpy(h.cam + 12, s->tan_half_fov, 8);
-}
-
-// What an accumulator renders with: a parity render on the lane-resident kernel.
-int accum_check_params(const rt_params *p, const char *who) {
-    if (int rc = check_flags(p, who)) return rc;
-    const std::string w = who;
-    if (p->flags & RT_FLAG_FAST)
-        return rt_fail(RT_ERR_ARG, w + ": fast mode has no accumulator here (a one-shot fast sum is defined per (spp, fast_chunk)); "
-                                       "use rt_accum_create_fast");
-    if (p->flags & RT_FLAG_LIGHT_SPLIT) return rt_fail(RT_ERR_ARG, w + ": the light-split kernel has no accumulator");
-    if (p->flags & RT_FLAG_KERNEL_TIMES) return rt_fail(RT_ERR_ARG, w + ": RT_FLAG_KERNEL_TIMES is a wavefront option; accumulators run on kernel 0");
-    if (p->count != 0) return rt_fail(RT_ERR_ARG, w + ": counting renders have no accumulator (count must be 0)");
-    if (p->kernel != RT_KERNEL_LANE) return rt_fail(RT_ERR_ARG, w + ": accumulators run on the lane-resident kernel only (kernel 0)");
-    if (rtp::order_flags_conflict(p->flags))
-        return rt_fail(RT_ERR_ARG, w + ": RT_FLAG_NATURAL_ORDER and RT_FLAG_HEAVY_ORDER exclude each other");
-    return RT_OK;
-}
-
-// What a fast accumulator renders with: fast units on the lane-resident kernel.  The order flags
-// and RT_FLAG_NO_RUNAHEAD are accepted and ignored (fast units are never ordered and have no
-// chain to run ahead of); RT_FLAG_FAST may be set or not.
-int accum_check_params_fast(const rt_params *p, const char *who) {
-    if (int rc = check_flags(p, who)) return rc;
-    const std::string w = who;
-    if (p->count != 0) return rt_fail(RT_ERR_ARG, w + ": counting renders have no accumulator (count must be 0)");
-    if (p->kernel != RT_KERNEL_LANE) return rt_fail(RT_ERR_ARG, w + ": accumulators run on the lane-resident kernel only (kernel 0)");
-    if (p->flags & RT_FLAG_LIGHT_SPLIT) return rt_fail(RT_ERR_ARG, w + ": the light-split kernel has no accumulator");
-    if (p->flags & RT_FLAG_KERNEL_TIMES) return rt_fail(RT_ERR_ARG, w + ": RT_FLAG_KERNEL_TIMES is a wavefront option; accumulators run on kernel 0");
-    if (p->fast_chunk < 0) return rt_fail(RT_ERR_ARG, w + ": fast_chunk must be >= 0");
-    return RT_OK;
-}
-
 void accum_release(rt_accum *a) {
     if (!a) return;
     if (a->chain || a->sums || a->rgb) {
@@ -2082,27 +2005,22 @@ void accum_release(rt_accum *a) {
     delete a;
 }
 
-// Host-side part of create / load: parameters and shard, no device call.
-// `fast`: a fast accumulator (p->fast_chunk its chunk size, 0 = 2); `moments`: one with moments.
-int accum_new(rt_scene *s, const rt_params *p, const char *who, rt_accum **out, bool fast = false, bool moments = false) {
-    if (int rc = fast ? accum_check_params_fast(p, who) : accum_check_params(p, who)) return rc;
+// Host-side part of create / load: parameters and shard, no device call (a fast kind's p->fast_chunk: 0 = 2).
+int accum_new(rt_scene *s, const rt_params *p, const char *who, rt_accum **out, rtap::Kind kind) {
+    if (int rc = check_flags(p, who)) return rc;
+    if (const rtp::Refusal r = rtap::check_params(kind, p->flags, p->count, p->kernel, p->fast_chunk, who)) return rt_fail(r.code, r.msg);
     if (p->device < 0 || p->device >= kRtMaxDevices) return rt_fail(RT_ERR_ARG, std::string(who) + ": bad device " + std::to_string(p->device));
     Shard sh;
     if (int rc = shard_of(s, p, who, sh)) return rc;
     rt_accum *a = new rt_accum();
-    a->scene = s;
+    a->scene = s, a->kind = kind;
     a->p = *p;
-    a->p.spp = 0;
-    a->p.world = sh.world;
-    a->p.row_block = sh.row_block;
-    a->rows = sh.rows;
-    a->n_pixels = sh.n_pixels;
-    a->geom = sh.g;
-    if (fast) {   // (what its passes render with: fast units, no order, the chunk size as it is)
+    a->p.spp = 0, a->p.world = sh.world, a->p.row_block = sh.row_block;
+    a->rows = sh.rows, a->n_pixels = sh.n_pixels, a->geom = sh.g;
+    if (rtap::info(kind).fast) {   // (what its passes render with: fast units, no order, the chunk size as it is)
         a->fast_c = p->fast_chunk > 0 ? p->fast_chunk : 2;
         a->p.flags = RT_FLAG_FAST;
         a->p.fast_chunk = a->fast_c;
-        a->has_moments = moments;
     }
     *out = a;
     return RT_OK;
@@ -2115,7 +2033,7 @@ int accum_alloc(rt_accum *a) {
     const size_t n = (size_t)std::max<long long>(a->n_pixels, 1);
     HIP_TRY(hipMalloc((void **)&a->chain, n * 32));
     HIP_TRY(hipMalloc((void **)&a->sums, n * 3 * sizeof(float)));
-    if (a->has_moments) {   // (zero words: no samples, total2 and open2 +0.f)
+    if (a->has_moments()) {   // (zero words: no samples, total2 and open2 +0.f)
         HIP_TRY(hipMalloc((void **)&a->mom, n * 32));
         HIP_TRY(hipMalloc((void **)&a->moments, n * 3 * sizeof(float)));
         HIP_TRY(hipMemset(a->mom, 0, n * 32));
@@ -2136,8 +2054,6 @@ int accum_buffer(T *&p, size_t count) {
     return RT_OK;
 }
 
-bool accum_uniform(const rt_accum *a) { return a->min_samples == a->samples; }
-
 // The sample-count map into a->counts, on the accumulator's stream.
 int accum_counts_launch(rt_accum *a, int32_t *d_counts, hipStream_t stream) {
     if (a->n_pixels == 0) return RT_OK;
@@ -2147,12 +2063,34 @@ int accum_counts_launch(rt_accum *a, int32_t *d_counts, hipStream_t stream) {
     return RT_OK;
 }
 
-// rt_accum_create and rt_accum_create_fast (`who` names the entry in messages).
-int accum_create(rt_scene *s, const rt_params *p, rt_accum **out, const std::string &who, bool fast, bool moments = false) {
+// The counts a frame divides by: null while every pixel holds a->samples, else the map in a->counts, on a->stream.
+int accum_counts_if_mixed(rt_accum *a, const int32_t **counts) {
+    *counts = nullptr;
+    if (a->uniform()) return RT_OK;
+    if (int rc = accum_buffer(a->counts, (size_t)a->n_pixels)) return rc;
+    if (int rc = accum_counts_launch(a, a->counts, a->stream)) return rc;
+    *counts = a->counts;
+    return RT_OK;
+}
+
+// The host-copy entries: on the accumulator's device, prepare() (what the entry queues first; it
+// may make the buffer), the wait for the stream, then `bytes` of the buffer `src` to `out`.
+template <class T, class Prepare = int (*)()>
+int accum_read_back(rt_accum *a, T *rt_accum::*src, size_t bytes, void *out, Prepare prepare = [] { return (int)RT_OK; }) {
+    DeviceGuard guard(a->p.device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = prepare()) return rc;
+    if (int rc = accum_wait(a)) return rc;
+    if (bytes) HIP_TRY(hipMemcpy(out, a->*src, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// rt_accum_create and its fast forms (`who` names the entry in messages).
+int accum_create(rt_scene *s, const rt_params *p, rt_accum **out, const std::string &who, rtap::Kind kind) {
     if (!s || !p || !out) return rt_fail(RT_ERR_ARG, who + ": NULL argument");
     *out = nullptr;
     rt_accum *a = nullptr;
-    if (int rc = accum_new(s, p, who.c_str(), &a, fast, moments)) return rc;
+    if (int rc = accum_new(s, p, who.c_str(), &a, kind)) return rc;
     if (!s->dev[a->p.device]) {
         accum_release(a);
         return rt_fail(RT_ERR_ARG, who + ": scene not uploaded to device " + std::to_string(p->device));
@@ -2161,7 +2099,7 @@ int accum_create(rt_scene *s, const rt_params *p, rt_accum **out, const std::str
     if (rc == RT_OK && a->n_pixels > 0) {
         DeviceGuard guard(a->p.device);
         const dim3 blocks((unsigned)((a->n_pixels + 255) / 256));
-        if (fast)
+        if (a->fast_c)
             hipLaunchKernelGGL(rt_fast_chain_init_kernel, blocks, dim3(256), 0, nullptr, a->n_pixels, a->chain, a->sums);
         else
             hipLaunchKernelGGL(rt_chain_init_kernel, blocks, dim3(256), 0, nullptr, s->dev[a->p.device]->ds, a->geom, a->chain,
@@ -2178,41 +2116,33 @@ int accum_create(rt_scene *s, const rt_params *p, rt_accum **out, const std::str
     return RT_OK;
 }
 
-// One launch of a fast accumulator's pass: the items (null: every pixel) raised to `target`, the
-// one furthest behind standing at `from` (its units are the launch's units per item).
-int fast_launch(rt_accum *a, int from, int target, const int *items, long long n_items, hipStream_t stream, rt_stats *st) {
+// A planned pass (rt_accum_plan.h) on `stream`: the one place that makes an accumulator's ChainPass.
+// A parity pass is one launch to the target, and `st` is that launch's.  A fast pass runs as the
+// launches next_launch cuts it into; `st` sums their times, with the pass's pixel and sample totals.
+int accum_pass(rt_accum *a, const rtap::Pass &ps, hipStream_t stream, rt_stats *st) {
+    a->stream = stream;
     rt_params p = a->p;
-    p.spp = target;
-    ChainPass cp{a->chain, target - from};
-    cp.items = items;
-    cp.n_items = n_items;
-    cp.fast_c = a->fast_c;
-    cp.fast_units = rtfu::units_of(from, target, a->fast_c);
-    cp.mom = a->mom;
-    cp.moments = a->moments;
-    return launch(a->scene, &p, a->sums, stream, st, &cp);
-}
-
-// A fast accumulator's pass from `from` (the smallest count among its items) to `target`: one
-// launch carries at most kFastMaxChunks units per item, so a longer pass runs as successive
-// complete passes (render + fold) to chunk boundaries on the way; same bits, the records carry
-// everything.  `st` sums the launches' times.
-int fast_pass(rt_accum *a, int from, int target, const int *items, long long n_items, hipStream_t stream, rt_stats *st) {
+    p.spp = ps.target;
+    ChainPass cp{a->chain, ps.n};
+    cp.items = ps.items ? a->sel_list : nullptr, cp.n_items = ps.n_items, cp.samples = ps.items ? ps.samples : 0;
+    if (!a->fast_c) return launch(a->scene, &p, a->sums, stream, st, &cp);
+    cp.fast_c = a->fast_c, cp.mom = a->mom, cp.moments = a->moments;
     rt_stats total{};
-    const int c = a->fast_c;
-    while (from < target) {
-        int to = target;
-        if (rtfu::units_of(from, target, c) > rtp::kFastMaxChunks)
-            to = (int)(((long long)(from / c) + rtp::kFastMaxChunks) * c);   // the end of the launch's last whole chunk
+    for (int from = ps.from; from < ps.target;) {
+        const int to = rtap::next_launch(from, ps.target, a->fast_c);
+        p.spp = to, cp.n = to - from;
+        cp.fast_units = rtfu::units_of(from, to, a->fast_c);   // (of the item furthest behind)
         rt_stats one{};
-        if (int rc = fast_launch(a, from, to, items, n_items, stream, st ? &one : nullptr)) return rc;
-        total.render_ms += one.render_ms;
-        total.schedule |= one.schedule;
-        total.pixels = one.pixels;
-        total.devices = one.devices;
+        if (int rc = launch(a->scene, &p, a->sums, stream, st ? &one : nullptr, &cp)) return rc;
+        total.render_ms += one.render_ms, total.schedule |= one.schedule;
+        total.pixels = one.pixels, total.devices = one.devices;
         from = to;   // (items that stood at or past `to` were not touched and stay ahead of it)
     }
-    if (st) *st = total;
+    if (st) {
+        *st = total;
+        if (ps.items) st->pixels = (uint64_t)ps.n_items;
+        st->samples = ps.samples;
+    }
     return RT_OK;
 }
 
@@ -2221,59 +2151,35 @@ int fast_pass(rt_accum *a, int from, int target, const int *items, long long n_i
 extern "C" {
 
 int rt_accum_create(rt_scene *s, const rt_params *p, rt_accum **out) {
-    return accum_create(s, p, out, "rt_accum_create", false);
+    return accum_create(s, p, out, "rt_accum_create", rtap::Kind::Parity);
 }
 
 int rt_accum_create_fast(rt_scene *s, const rt_params *p, rt_accum **out) {
-    return accum_create(s, p, out, "rt_accum_create_fast", true);
+    return accum_create(s, p, out, "rt_accum_create_fast", rtap::Kind::Fast);
 }
 
 int32_t rt_accum_fast_chunk(const rt_accum *a) { return a ? a->fast_c : 0; }
 
 int rt_accum_create_fast_moments(rt_scene *s, const rt_params *p, rt_accum **out) {
-    return accum_create(s, p, out, "rt_accum_create_fast_moments", true, true);
+    return accum_create(s, p, out, "rt_accum_create_fast_moments", rtap::Kind::Moments);
 }
 
-int32_t rt_accum_has_moments(const rt_accum *a) { return a && a->has_moments ? 1 : 0; }
+int32_t rt_accum_has_moments(const rt_accum *a) { return a && a->has_moments() ? 1 : 0; }
 
 int rt_accum_moments(rt_accum *a, float *out) {
     if (!a || !out) return rt_fail(RT_ERR_ARG, "rt_accum_moments: NULL argument");
-    if (!a->has_moments) return rt_fail(RT_ERR_ARG, "rt_accum_moments: the accumulator keeps no moments (rt_accum_create_fast_moments)");
-    DeviceGuard guard(a->p.device);
-    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
-    if (int rc = accum_wait(a)) return rc;
-    HIP_TRY(hipMemcpy(out, a->moments, (size_t)a->n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return RT_OK;
+    if (!a->has_moments()) return rt_fail(RT_ERR_ARG, "rt_accum_moments: the accumulator keeps no moments (rt_accum_create_fast_moments)");
+    return accum_read_back(a, &rt_accum::moments, (size_t)a->n_pixels * 3 * sizeof(float), out);
 }
 
-const float *rt_accum_device_moments(rt_accum *a) { return a && a->has_moments ? a->moments : nullptr; }
+const float *rt_accum_device_moments(rt_accum *a) { return a && a->has_moments() ? a->moments : nullptr; }
 
 int rt_accum_add(rt_accum *a, int32_t n_samples, void *stream, rt_stats *st) {
     if (!a) return rt_fail(RT_ERR_ARG, "rt_accum_add: NULL accumulator");
-    if (n_samples < 1) return rt_fail(RT_ERR_ARG, "rt_accum_add: n_samples must be >= 1");
-    if ((long long)a->samples + n_samples >= (1 << 20))
-        return rt_fail(RT_ERR_LIMIT, "rt_accum_add: total samples per pixel must be < 2^20");
-    if (!accum_uniform(a))
-        return rt_fail(RT_ERR_ARG, "rt_accum_add: the pixels hold between " + std::to_string(a->min_samples) + " and " +
-                                       std::to_string(a->samples) + " samples; level them first: rt_accum_select with target = " +
-                                       std::to_string(a->samples) + " and no threshold, then rt_accum_add_selected");
-    a->sel_pending = false;   // (the pass changes the records the list was made from)
-    if (a->fast_c) {
-        a->stream = (hipStream_t)stream;
-        if (int rc = fast_pass(a, a->samples, a->samples + n_samples, nullptr, 0, (hipStream_t)stream, st)) return rc;
-        if (st) st->samples = (uint64_t)a->n_pixels * (uint64_t)n_samples;
-        a->samples += n_samples;
-        a->min_samples = a->samples;
-        return RT_OK;
-    }
-    rt_params p = a->p;
-    p.spp = a->samples + n_samples;   // the absolute sample this pass ends at
-    const ChainPass cp{a->chain, n_samples};
-    a->stream = (hipStream_t)stream;
-    int rc = launch(a->scene, &p, a->sums, (hipStream_t)stream, st, &cp);
-    if (rc) return rc;
-    a->samples += n_samples;
-    a->min_samples = a->samples;
+    const rtap::Pass ps = rtap::plan_add(*a, n_samples, a->n_pixels);
+    if (ps.refused) return rt_fail(ps.refused.code, ps.refused.msg);
+    if (int rc = accum_pass(a, ps, (hipStream_t)stream, st)) return rc;
+    rtap::commit_add(*a, ps);
     return RT_OK;
 }
 
@@ -2308,7 +2214,7 @@ static int accum_select(rt_accum *a, const rt_select *sel, void *stream, int64_t
                                                          std::to_string(rule.x1) + ") x [" + std::to_string(rule.y0) + ", " +
                                                          std::to_string(rule.y1) + ")");
     if (!a) return rt_fail(RT_ERR_ARG, who + ": NULL accumulator");
-    if (variance && !a->has_moments)
+    if (variance && !a->has_moments())
         return rt_fail(RT_ERR_ARG, who + ": the accumulator keeps no moments (rt_accum_create_fast_moments)");
     a->sel_pending = false;
     DeviceGuard guard(a->p.device);
@@ -2365,60 +2271,31 @@ int rt_accum_select_variance(rt_accum *a, const rt_select *sel, void *stream, in
 int rt_accum_selection(rt_accum *a, int32_t *out_pixels) {
     if (!a || !out_pixels) return rt_fail(RT_ERR_ARG, "rt_accum_selection: NULL argument");
     if (!a->sel_pending) return rt_fail(RT_ERR_ARG, "rt_accum_selection: no pending selection (rt_accum_select first)");
-    DeviceGuard guard(a->p.device);
-    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
-    if (int rc = accum_wait(a)) return rc;
-    if (a->sel_n) HIP_TRY(hipMemcpy(out_pixels, a->sel_list, (size_t)a->sel_n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return accum_read_back(a, &rt_accum::sel_list, (size_t)a->sel_n * sizeof(int32_t), out_pixels);
 }
 
 int rt_accum_add_selected(rt_accum *a, void *stream, rt_stats *st) {
     if (!a) return rt_fail(RT_ERR_ARG, "rt_accum_add_selected: NULL accumulator");
-    if (!a->sel_pending)
-        return rt_fail(RT_ERR_ARG, "rt_accum_add_selected: no pending selection (rt_accum_select first; every pass "
-                                   "drops it)");
-    a->sel_pending = false;
-    if (a->sel_n == 0) {   // nothing to raise: no launch
+    const rtap::Pass ps = rtap::plan_add_selected(*a);
+    if (ps.refused) return rt_fail(ps.refused.code, ps.refused.msg);
+    if (!ps.launch) {   // nothing to raise
         if (st) {
             std::memset(st, 0, sizeof *st);
             st->devices = 1;
         }
         return RT_OK;
     }
-    if (a->fast_c) {   // (sel_from: the listed pixel furthest behind; below the target by the rule)
-        a->stream = (hipStream_t)stream;
-        if (int rc = fast_pass(a, a->sel_from, a->sel_target, a->sel_list, a->sel_n, (hipStream_t)stream, st)) return rc;
-        if (st) {
-            st->pixels = (uint64_t)a->sel_n;
-            st->samples = a->sel_samples;
-        }
-        a->samples = a->sel_max;
-        a->min_samples = a->sel_min;
-        return RT_OK;
-    }
-    rt_params p = a->p;
-    p.spp = a->sel_target;   // the absolute sample every listed pixel ends at
-    ChainPass cp{a->chain, 1};
-    cp.items = a->sel_list;
-    cp.n_items = a->sel_n;
-    cp.samples = a->sel_samples;
-    a->stream = (hipStream_t)stream;
-    int rc = launch(a->scene, &p, a->sums, (hipStream_t)stream, st, &cp);
-    if (rc) return rc;
-    a->samples = a->sel_max;
-    a->min_samples = a->sel_min;
+    if (int rc = accum_pass(a, ps, (hipStream_t)stream, st)) return rc;
+    rtap::commit_selected(*a);
     return RT_OK;
 }
 
 int rt_accum_counts(rt_accum *a, int32_t *out) {
     if (!a || !out) return rt_fail(RT_ERR_ARG, "rt_accum_counts: NULL argument");
-    DeviceGuard guard(a->p.device);
-    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
-    if (int rc = accum_buffer(a->counts, (size_t)a->n_pixels)) return rc;
-    if (int rc = accum_counts_launch(a, a->counts, a->stream)) return rc;
-    if (int rc = accum_wait(a)) return rc;
-    if (a->n_pixels) HIP_TRY(hipMemcpy(out, a->counts, (size_t)a->n_pixels * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return accum_read_back(a, &rt_accum::counts, (size_t)a->n_pixels * sizeof(int32_t), out, [&] {
+        if (int rc = accum_buffer(a->counts, (size_t)a->n_pixels)) return rc;
+        return accum_counts_launch(a, a->counts, a->stream);
+    });
 }
 
 int rt_accum_counts_device(rt_accum *a, int32_t *d_out, void *stream) {
@@ -2439,11 +2316,7 @@ int32_t rt_accum_samples(const rt_accum *a) { return a ? a->samples : 0; }
 
 int rt_accum_sums(rt_accum *a, float *out_sum) {
     if (!a || !out_sum) return rt_fail(RT_ERR_ARG, "rt_accum_sums: NULL argument");
-    DeviceGuard guard(a->p.device);
-    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
-    if (int rc = accum_wait(a)) return rc;
-    HIP_TRY(hipMemcpy(out_sum, a->sums, (size_t)a->n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return accum_read_back(a, &rt_accum::sums, (size_t)a->n_pixels * 3 * sizeof(float), out_sum);
 }
 
 const float *rt_accum_device_sums(rt_accum *a) { return a ? a->sums : nullptr; }
@@ -2452,29 +2325,19 @@ int rt_accum_frame_u8(rt_accum *a, uint8_t *out_rgb) {
     if (!a || !out_rgb) return rt_fail(RT_ERR_ARG, "rt_accum_frame_u8: NULL argument");
     if (a->samples < 1) return rt_fail(RT_ERR_ARG, "rt_accum_frame_u8: no samples yet");
     if (a->n_pixels == 0) return RT_OK;
-    DeviceGuard guard(a->p.device);
-    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
-    if (!a->rgb) HIP_TRY(hipMalloc((void **)&a->rgb, (size_t)a->n_pixels * 3));
-    if (accum_uniform(a)) {
-        if (int rc = rt_tonemap_u8_device(a->sums, a->scene->width, a->rows, a->samples, a->rgb, a->stream)) return rc;
-    } else {   // every pixel divided by its own count
-        if (int rc = accum_buffer(a->counts, (size_t)a->n_pixels)) return rc;
-        if (int rc = accum_counts_launch(a, a->counts, a->stream)) return rc;
-        if (int rc = rt_tonemap_u8_counts_device(a->sums, a->counts, a->scene->width, a->rows, a->rgb, a->stream)) return rc;
-    }
-    if (int rc = accum_wait(a)) return rc;
-    HIP_TRY(hipMemcpy(out_rgb, a->rgb, (size_t)a->n_pixels * 3, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return accum_read_back(a, &rt_accum::rgb, (size_t)a->n_pixels * 3, out_rgb, [&] {
+        if (int rc = accum_buffer(a->rgb, (size_t)a->n_pixels * 3)) return rc;
+        const int32_t *counts = nullptr;   // (mixed counts: every pixel divided by its own)
+        if (int rc = accum_counts_if_mixed(a, &counts)) return rc;
+        return counts ? rt_tonemap_u8_counts_device(a->sums, counts, a->scene->width, a->rows, a->rgb, a->stream)
+                      : rt_tonemap_u8_device(a->sums, a->scene->width, a->rows, a->samples, a->rgb, a->stream);
+    });
 }
 
 // Host copy of the chain buffer (after the last pass).
 static int accum_records(rt_accum *a, std::vector<uint32_t> &rec) {
     rec.resize((size_t)a->n_pixels * 8);
-    DeviceGuard guard(a->p.device);
-    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
-    if (int rc = accum_wait(a)) return rc;
-    if (a->n_pixels) HIP_TRY(hipMemcpy(rec.data(), a->chain, rec.size() * 4, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return accum_read_back(a, &rt_accum::chain, rec.size() * 4, rec.data());
 }
 
 int rt_accum_state(rt_accum *a, uint32_t *out) {
@@ -2482,12 +2345,11 @@ int rt_accum_state(rt_accum *a, uint32_t *out) {
     std::vector<uint32_t> rec;
     if (int rc = accum_records(a, rec)) return rc;
     for (long long k = 0; k < a->n_pixels; ++k) {
+        out[4 * k + 0] = rec[8 * k + 1];
         if (a->fast_c) {   // (rt_mega.h FastRec: next sample, the open partial's three words)
-            out[4 * k + 0] = rec[8 * k + 1];
             std::memcpy(out + 4 * k + 1, &rec[8 * k + 5], 12);
             continue;
         }
-        out[4 * k + 0] = rec[8 * k + 1];
         out[4 * k + 1] = rec[8 * k + 2] & 0x7fffffffu;   // (rt_mega.h rng_word_pack)
         out[4 * k + 2] = rec[8 * k + 2] >> 31;
         out[4 * k + 3] = rec[8 * k + 3];
@@ -2495,37 +2357,29 @@ int rt_accum_state(rt_accum *a, uint32_t *out) {
     return RT_OK;
 }
 
+// What a checkpoint header records of the scene (rt_accum_file.h).
+static rtaf::SceneFacts accum_scene_facts(const rt_scene *s) {
+    rtaf::SceneFacts f{s->width, s->height, s->ray_depth, (uint32_t)(s->tri.size() / 12), (uint32_t)(s->node.size() / 8),
+                       (uint32_t)(s->light.size() / 16), {}};
+    std::memcpy(f.cam, s->cam_pos, 12), std::memcpy(f.cam + 3, s->cam_axes, 36), std::memcpy(f.cam + 12, s->tan_half_fov, 8);
+    return f;
+}
+
 int rt_accum_save(rt_accum *a, const char *path) {
     if (!a || !path) return rt_fail(RT_ERR_ARG, "rt_accum_save: NULL argument");
-    std::vector<uint32_t> rec;
+    std::vector<uint32_t> rec, mom;
     if (int rc = accum_records(a, rec)) return rc;
-    AccumHeader h;
-    accum_header_fill(a->scene, h);
-    h.rank = a->p.rank;
-    h.world = a->p.world;
-    h.row_block = a->p.row_block;
-    h.n_pixels = a->n_pixels;
-    h.samples = a->samples;
-    h.reserved = accum_uniform(a) ? 0 : 1;   // 1: per-pixel counts, `samples` is the largest
-    if (a->fast_c) {
-        std::memcpy(h.magic, kFastAccumMagic, 8);
-        h.version = kFastAccumVersion;
-        h.pad[0] = (uint32_t)a->fast_c;
-    }
-    std::vector<uint32_t> mom;
-    if (a->has_moments) {   // (accum_records waited for the last pass)
-        std::memcpy(h.magic, kMomentAccumMagic, 8);
-        h.version = kMomentAccumVersion;
+    if (a->has_moments()) {
         mom.resize((size_t)a->n_pixels * 8);
-        DeviceGuard guard(a->p.device);
-        if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
-        if (a->n_pixels) HIP_TRY(hipMemcpy(mom.data(), a->mom, mom.size() * 4, hipMemcpyDeviceToHost));
+        if (int rc = accum_read_back(a, &rt_accum::mom, mom.size() * 4, mom.data())) return rc;
     }
+    auto h = rtaf::header_of(accum_scene_facts(a->scene), a->kind);
+    h.rank = a->p.rank, h.world = a->p.world, h.row_block = a->p.row_block;
+    h.n_pixels = a->n_pixels, h.samples = a->samples, h.pad[0] = (uint32_t)a->fast_c;
+    h.reserved = a->uniform() ? 0 : 1;   // 1: per-pixel counts, `samples` is the largest
     std::FILE *f = std::fopen(path, "wb");
     if (!f) return rt_fail(RT_ERR_IO, std::string("rt_accum_save: cannot write ") + path);
-    bool ok = std::fwrite(&h, sizeof h, 1, f) == 1;
-    ok = ok && (rec.empty() || std::fwrite(rec.data(), 4, rec.size(), f) == rec.size());
-    ok = ok && (mom.empty() || std::fwrite(mom.data(), 4, mom.size(), f) == mom.size());
+    bool ok = rtaf::write(f, h, rec, mom);
     ok = (std::fclose(f) == 0) && ok;
     if (!ok) return rt_fail(RT_ERR_IO, std::string("rt_accum_save: short write to ") + path);
     return RT_OK;
@@ -2534,123 +2388,30 @@ int rt_accum_save(rt_accum *a, const char *path) {
 int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out) {
     if (!s || !path || !out) return rt_fail(RT_ERR_ARG, "rt_accum_load: NULL argument");
     *out = nullptr;
-    // the file is read and checked whole before any device call
+    // the file is read and checked whole before any device call; between its header and its
+    // records, the shard the header names must be one of this scene with as many pixels
     const std::string who = std::string("rt_accum_load: ") + path;
-    std::FILE *f = std::fopen(path, "rb");
-    if (!f) return rt_fail(RT_ERR_IO, who + ": cannot open");
-    AccumHeader h;
-    std::vector<uint32_t> rec;
-    int rc = RT_OK;
-    bool fast = false, moments = false;   // (the magic says which kind the file holds)
-    std::vector<uint32_t> mom;
-    if (std::fread(&h, sizeof h, 1, f) != 1) rc = rt_fail(RT_ERR_FORMAT, who + ": shorter than its header");
-    else if (!(fast = (moments = std::memcmp(h.magic, kMomentAccumMagic, 8) == 0) || std::memcmp(h.magic, kFastAccumMagic, 8) == 0) &&
-             std::memcmp(h.magic, kAccumMagic, 8) != 0)
-        rc = rt_fail(RT_ERR_FORMAT, who + ": not an accumulator file (magic)");
-    else if (h.version != (moments ? kMomentAccumVersion : fast ? kFastAccumVersion : kAccumVersion))
-        rc = rt_fail(RT_ERR_FORMAT, who + ": version " + std::to_string(h.version) + ", this library reads " +
-                                        std::to_string(moments ? kMomentAccumVersion : fast ? kFastAccumVersion : kAccumVersion));
-    else if (fast && (h.pad[0] < 1u || h.pad[0] > (uint32_t)INT32_MAX))
-        rc = rt_fail(RT_ERR_FORMAT, who + ": bad chunk size " + std::to_string(h.pad[0]));
-    else if (h.n_pixels < 0 || h.n_pixels > INT32_MAX || h.samples < 0 || h.samples >= (1 << 20))
-        rc = rt_fail(RT_ERR_FORMAT, who + ": bad pixel or sample count");
-    else if (h.reserved != 0 && h.reserved != 1)
-        rc = rt_fail(RT_ERR_FORMAT, who + ": bad count form " + std::to_string(h.reserved) + " (0 uniform, 1 per pixel)");
-    else {
-        std::fseek(f, 0, SEEK_END);
-        const long long len = (long long)std::ftell(f);
-        const long long want_len = (long long)sizeof h + h.n_pixels * (moments ? 64 : 32);
-        if (len != want_len)
-            rc = rt_fail(RT_ERR_FORMAT, who + ": " + std::to_string(len) + " bytes, expected " + std::to_string(want_len));
-        else {
-            std::fseek(f, (long)sizeof h, SEEK_SET);
-            rec.resize((size_t)h.n_pixels * 8);
-            if (!rec.empty() && std::fread(rec.data(), 4, rec.size(), f) != rec.size())
-                rc = rt_fail(RT_ERR_IO, who + ": read failed");
-            if (moments && rc == RT_OK) {
-                mom.resize((size_t)h.n_pixels * 8);
-                if (!mom.empty() && std::fread(mom.data(), 4, mom.size(), f) != mom.size())
-                    rc = rt_fail(RT_ERR_IO, who + ": read failed");
-            }
-        }
-    }
-    std::fclose(f);
-    if (rc) return rc;
-    AccumHeader want;
-    accum_header_fill(s, want);
-    if (h.width != want.width || h.height != want.height || h.ray_depth != want.ray_depth)
-        return rt_fail(RT_ERR_ARG, who + ": made for a " + std::to_string(h.width) + " x " + std::to_string(h.height) +
-                                       " frame at ray depth " + std::to_string(h.ray_depth) + ", the scene is " +
-                                       std::to_string(want.width) + " x " + std::to_string(want.height) + " at " +
-                                       std::to_string(want.ray_depth));
-    if (h.n_tris != want.n_tris || h.n_nodes != want.n_nodes || h.n_lights != want.n_lights ||
-        std::memcmp(h.cam, want.cam, sizeof h.cam) != 0)
-        return rt_fail(RT_ERR_ARG, who + ": made for another scene or camera");
-    if (h.world < 1 || h.rank < 0 || h.rank >= h.world || h.row_block < 1)
-        return rt_fail(RT_ERR_ARG, who + ": bad shard (rank " + std::to_string(h.rank) + ", world " + std::to_string(h.world) +
-                                       ", row_block " + std::to_string(h.row_block) + ")");
-    rt_params p{};
-    p.rank = h.rank;
-    p.world = h.world;
-    p.row_block = h.row_block;
-    p.device = device;
     rt_accum *a = nullptr;
-    if (fast) p.fast_chunk = (int)h.pad[0];
-    if (int rc2 = accum_new(s, &p, "rt_accum_load", &a, fast, moments)) return rc2;
-    if (a->n_pixels != h.n_pixels) {
-        const long long have = a->n_pixels;
-        accum_release(a);
-        return rt_fail(RT_ERR_ARG, who + ": " + std::to_string(h.n_pixels) + " pixels, the shard (rank " + std::to_string(h.rank) +
-                                       ", world " + std::to_string(h.world) + ") of this scene has " + std::to_string(have));
-    }
-    // (per-pixel counts, reserved = 1: any next sample up to the header's; else all equal to it)
-    uint32_t lo = (uint32_t)h.samples, hi = h.reserved && h.n_pixels ? 0u : (uint32_t)h.samples;
-    for (long long k = 0; k < h.n_pixels; ++k) {
-        const uint32_t nx = rec[8 * k + 1];
-        if (rec[8 * k] != (uint32_t)k || (h.reserved ? nx > (uint32_t)h.samples : nx != (uint32_t)h.samples)) {
-            accum_release(a);
-            return rt_fail(RT_ERR_FORMAT, who + ": record " + std::to_string(k) + " does not belong to this file");
-        }
-        if (fast && !rtfu::open_words_fit(nx, a->fast_c, &rec[8 * k + 5])) {
-            accum_release(a);
-            return rt_fail(RT_ERR_FORMAT, who + ": record " + std::to_string(k) + " holds an open partial at a chunk boundary");
-        }
-        if (moments && !rtmo::record_words_fit(nx, a->fast_c, &mom[8 * k])) {
-            accum_release(a);
-            return rt_fail(RT_ERR_FORMAT, who + ": moment record " + std::to_string(k) +
-                                              " holds an open partial or pad words at a chunk boundary");
-        }
-        lo = std::min(lo, nx);
-        hi = std::max(hi, nx);
-    }
-    rc = ensure_device_scene(s, device);   // (the file fits the scene: first device call)
+    const rtaf::File f = rtaf::read(path, accum_scene_facts(s), who, [&](const rtaf::File &file) -> rtp::Refusal {
+        rt_params p{};
+        p.rank = file.h.rank, p.world = file.h.world, p.row_block = file.h.row_block;
+        p.device = device, p.fast_chunk = file.fast_c();
+        if (int rc = accum_new(s, &p, "rt_accum_load", &a, file.kind)) return {rc, rt_last_error()};
+        if (a->n_pixels != file.h.n_pixels)
+            return {RT_ERR_ARG, who + ": " + std::to_string(file.h.n_pixels) + " pixels, the shard (rank " + std::to_string(file.h.rank) +
+                                    ", world " + std::to_string(file.h.world) + ") of this scene has " + std::to_string(a->n_pixels)};
+        return {};
+    });
+    int rc = f.refused ? rt_fail(f.refused.code, f.refused.msg) : RT_OK;
+    if (rc == RT_OK) rc = ensure_device_scene(s, device);   // (the file fits the scene: first device call)
     if (rc == RT_OK) rc = accum_alloc(a);
-    if (rc == RT_OK && a->n_pixels > 0) {
+    if (rc == RT_OK && a->n_pixels > 0) {   // the records, and their reported values as the fold kernels write them
         DeviceGuard guard(device);
-        std::vector<float> sums((size_t)h.n_pixels * 3);
-        for (long long k = 0; k < h.n_pixels; ++k) {
-            if (fast) {   // the reported sum of the record (rt_fast_units.h), as the fold kernel writes it
-                rtfu::Rec r;
-                r.next = (int)rec[8 * k + 1];
-                std::memcpy(r.total, &rec[8 * k + 2], 12);
-                std::memcpy(r.open, &rec[8 * k + 5], 12);
-                rtfu::reported(r, a->fast_c, &sums[3 * k]);
-            } else {
-                std::memcpy(&sums[3 * k], &rec[8 * k + 4], 12);
-            }
-        }
-        hipError_t e = hipMemcpy(a->chain, rec.data(), rec.size() * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(a->sums, sums.data(), sums.size() * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && moments) {   // the moment records, and their reported values as the fold kernel writes them
-            for (long long k = 0; k < h.n_pixels; ++k) {
-                rtfu::Rec r;
-                r.next = (int)rec[8 * k + 1];
-                std::memcpy(r.total, &mom[8 * k], 12);
-                std::memcpy(r.open, &mom[8 * k + 3], 12);
-                rtfu::reported(r, a->fast_c, &sums[3 * k]);
-            }
-            e = hipMemcpy(a->mom, mom.data(), mom.size() * 4, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(a->moments, sums.data(), sums.size() * 4, hipMemcpyHostToDevice);
+        hipError_t e = hipMemcpy(a->chain, f.rec.data(), f.rec.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(a->sums, f.sums.data(), f.sums.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess && a->has_moments()) {
+            e = hipMemcpy(a->mom, f.mom.data(), f.mom.size() * 4, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemcpy(a->moments, f.moments.data(), f.moments.size() * 4, hipMemcpyHostToDevice);
         }
         if (e != hipSuccess) rc = rt_fail(RT_ERR_DEVICE, std::string("rt_accum_load: ") + hipGetErrorString(e));
     }
@@ -2658,8 +2419,8 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
         accum_release(a);
         return rc;
     }
-    a->samples = (int)hi;   // (no mark, no pending selection)
-    a->min_samples = (int)lo;
+    a->samples = f.hi;   // (no mark, no pending selection)
+    a->min_samples = f.lo;
     *out = a;
     return RT_OK;
 }
@@ -3005,6 +2766,16 @@ std::mutex g_dn_mu;
 void *g_dn_ws[kRtMaxDevices] = {};
 size_t g_dn_ws_bytes[kRtMaxDevices] = {};
 
+// The shard's first-hit records in a->gbuf on a->stream, rendered on first use (they depend on the
+// scene alone; the current device is the accumulator's).
+int accum_ensure_gbuffer(rt_accum *a) {
+    if (int rc = accum_buffer(a->gbuf, (size_t)a->n_pixels * rtd::kGbufferQuads)) return rc;
+    if (a->gbuf_ready) return RT_OK;
+    if (int rc = gbuffer_launch(a->scene->dev[a->p.device], a->geom, a->gbuf, a->stream)) return rc;
+    a->gbuf_ready = true;   // (set only once the records' launch was accepted: a call that fails before keeps it unset)
+    return RT_OK;
+}
+
 // rt_accum_frame_u8_denoised / rt_accum_frame_u8_guided: the accumulator's frame through a filter
 // in front of the finish.  check(spp, W, H) resolves the parameters before anything is allocated
 // or launched; launch(counts, spp, W, H) filters a->sums into a->dn_mean on a->stream.
@@ -3022,19 +2793,11 @@ int accum_filtered_frame(rt_accum *a, const std::string &who, const char *frame_
     // the parameters first: a refused call allocates and launches nothing
     const int spp = a->samples;
     if (int rc = check(spp, W, H)) return rc;
-    if (int rc = accum_buffer(a->gbuf, (size_t)a->n_pixels * rtd::kGbufferQuads)) return rc;
     if (int rc = accum_buffer(a->dn_mean, (size_t)a->n_pixels * 3)) return rc;
     if (int rc = accum_buffer(a->rgb, (size_t)a->n_pixels * 3)) return rc;
-    if (!a->gbuf_ready) {   // (set only once the records' launch was accepted: a call that fails before keeps it unset)
-        if (int rc = gbuffer_launch(a->scene->dev[a->p.device], a->geom, a->gbuf, a->stream)) return rc;
-        a->gbuf_ready = true;
-    }
-    const int32_t *counts = nullptr;
-    if (!accum_uniform(a)) {   // every pixel divided by its own count
-        if (int rc = accum_buffer(a->counts, (size_t)a->n_pixels)) return rc;
-        if (int rc = accum_counts_launch(a, a->counts, a->stream)) return rc;
-        counts = a->counts;
-    }
+    if (int rc = accum_ensure_gbuffer(a)) return rc;
+    const int32_t *counts = nullptr;   // (mixed counts: every pixel divided by its own)
+    if (int rc = accum_counts_if_mixed(a, &counts)) return rc;
     if (int rc = launch(counts, spp, W, H)) return rc;
     if (int rc = rt_tonemap_u8_device(a->dn_mean, W, H, 1, a->rgb, a->stream)) return rc;
     if (int rc = accum_wait(a)) return rc;
@@ -3215,17 +2978,9 @@ int variance_launch(const float *d_sums, const float *d_moments, const int32_t *
 // accumulator's): its own counts, and its shard's first-hit records, rendered on first use.
 int accum_variance_launch(rt_accum *a) {
     if (int rc = accum_buffer(a->var, (size_t)a->n_pixels)) return rc;
-    if (int rc = accum_buffer(a->gbuf, (size_t)a->n_pixels * rtd::kGbufferQuads)) return rc;
-    if (!a->gbuf_ready) {
-        if (int rc = gbuffer_launch(a->scene->dev[a->p.device], a->geom, a->gbuf, a->stream)) return rc;
-        a->gbuf_ready = true;
-    }
+    if (int rc = accum_ensure_gbuffer(a)) return rc;
     const int32_t *counts = nullptr;
-    if (!accum_uniform(a)) {
-        if (int rc = accum_buffer(a->counts, (size_t)a->n_pixels)) return rc;
-        if (int rc = accum_counts_launch(a, a->counts, a->stream)) return rc;
-        counts = a->counts;
-    }
+    if (int rc = accum_counts_if_mixed(a, &counts)) return rc;
     return variance_launch(a->sums, a->moments, counts, a->samples, a->n_pixels, (const float *)a->gbuf, a->var, a->stream);
 }
 
@@ -3242,18 +2997,13 @@ int rt_variance_from_moments_device(const float *d_sums, const float *d_moments,
 
 int rt_accum_variance(rt_accum *a, float *out) {
     if (!a || !out) return rt_fail(RT_ERR_ARG, "rt_accum_variance: NULL argument");
-    if (!a->has_moments) return rt_fail(RT_ERR_ARG, "rt_accum_variance: the accumulator keeps no moments (rt_accum_create_fast_moments)");
+    if (!a->has_moments()) return rt_fail(RT_ERR_ARG, "rt_accum_variance: the accumulator keeps no moments (rt_accum_create_fast_moments)");
     if (a->n_pixels == 0) return RT_OK;
-    DeviceGuard guard(a->p.device);
-    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
-    if (int rc = accum_variance_launch(a)) return rc;
-    if (int rc = accum_wait(a)) return rc;
-    HIP_TRY(hipMemcpy(out, a->var, (size_t)a->n_pixels * sizeof(float), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return accum_read_back(a, &rt_accum::var, (size_t)a->n_pixels * sizeof(float), out, [&] { return accum_variance_launch(a); });
 }
 
 int rt_accum_frame_u8_guided_measured(rt_accum *a, const rt_denoise_guided_params *params, uint8_t *out_rgb) {
-    if (a && !a->has_moments)
+    if (a && !a->has_moments())
         return rt_fail(RT_ERR_ARG, "rt_accum_frame_u8_guided_measured: the accumulator keeps no moments (rt_accum_create_fast_moments)");
     rtdg::Params dp;
     return accum_filtered_frame(
