@@ -2,8 +2,8 @@
 //
 // rt_denoise / rt_denoise_device (include/rt_hw.h has the rules in full) filter a whole frame of
 // sums, guided by its first-hit records (rt_gbuffer.h).  The per-pixel text of the three steps
-// (prepare, one level, resolve) lives here and is shared by the device kernels (rt_device.hip
-// rt_denoise_*_kernel) and the host function (rt_host.cpp rt_denoise), the way rt_select.h and
+// (prepare, one level, resolve) lives here and is shared by the device kernels
+// (rt_denoise_device.h) and the host function (rt_host.cpp rt_denoise), the way rt_select.h and
 // rt_fast_units.h are shared.  Only f32 +, -, *, /, comparisons and selects, in the order written;
 // the falloffs are rational, 1 / (1 + x), so there is no exp to differ between libraries.  Every
 // translation unit that includes this is built with -ffp-contract=off, and the device build with
@@ -98,15 +98,57 @@ inline Level level_of(const Params &p, int k) {
 // The B3-spline weight by |offset|: 3/8, 1/4, 1/16 (their products are exact).
 RT_HD float spline(int d) { return d == 0 ? 0.375f : ((d == 1 || d == -1) ? 0.25f : 0.0625f); }
 
+// What the centre contributes to a tap's normal and plane terms.
+struct Geo {
+    Q np, pp;
+    float plane_den;
+    int normal_power_log2;
+};
+template <class Src>
+RT_HD Geo geo_of(const Src &src, int x, int y, float sigma_plane, int normal_power_log2) {
+    const Q np = src.nt(x, y);
+    return Geo{np, src.pp(x, y), sigma_plane * np.w, normal_power_log2};
+}
+RT_HD float normal_term(const Geo &c, const Q &nq) {
+    float nd = (c.np.x * nq.x + c.np.y * nq.y) + c.np.z * nq.z;
+    nd = nd > 0.f ? nd : 0.f;
+    for (int i = 0; i < c.normal_power_log2; ++i) nd = nd * nd;
+    return nd;
+}
+RT_HD float plane_term(const Geo &c, const Q &pq) {
+    const float ex = pq.x - c.pp.x, ey = pq.y - c.pp.y, ez = pq.z - c.pp.z;
+    const float pd = (c.np.x * ex + c.np.y * ey) + c.np.z * ez;
+    const float pr = pd / c.plane_den;
+    return 1.f / (1.f + pr * pr);
+}
+// The colour term of tap q at a centre c of kind `kind`: 1 for a centre that is being filled.
+RT_HD float color_term(uint32_t kind, const Q &c, const Q &q, float color_den) {
+    float wc = 1.f;
+    if (kind == kValid) {
+        const float lx = q.x - c.x, ly = q.y - c.y, lz = q.z - c.z;
+        const float d2 = (lx * lx + ly * ly) + lz * lz;
+        wc = 1.f / (1.f + d2 / color_den);
+    }
+    return wc;
+}
+// A tap's weight: the spline weight h and the three terms, multiplied in this order.
+RT_HD float tap_weight(float h, float nd, float wp, float wc) {
+    float w = h * nd;
+    w = w * wp;
+    w = w * wc;
+    return w;
+}
+
 // One level at centre (x, y) of a W x H frame.  src.a / src.nt / src.pp(qx, qy) read the three
 // packed words of a tap (global memory, LDS or a host array: the same text runs over each).
+// (rt_denoise_guided.h's level is a loop of its own over the same weight functions: one loop for
+// both, with a flag for the variance, made this mode's five levels 4% slower)
 template <class Src>
 RT_HD Q level_pixel(const Src &src, int x, int y, int W, int H, const Level &lv) {
     const Q c = src.a(x, y);
     const uint32_t kind = rtm::f2u(c.w);
     if (kind == kPass) return c;
-    const Q np = src.nt(x, y), ppx = src.pp(x, y);
-    const float plane_den = lv.sigma_plane * np.w;
+    const Geo gc = geo_of(src, x, y, lv.sigma_plane, lv.normal_power_log2);
     float sw = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
     for (int dy = -2; dy <= 2; ++dy)
         for (int dx = -2; dx <= 2; ++dx) {
@@ -116,22 +158,7 @@ RT_HD Q level_pixel(const Src &src, int x, int y, int W, int H, const Level &lv)
             if (rtm::f2u(q.w) != kValid) continue;
             const Q nq = src.nt(qx, qy), pq = src.pp(qx, qy);
             const float h = spline(dx) * spline(dy);
-            float nd = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
-            nd = nd > 0.f ? nd : 0.f;
-            for (int i = 0; i < lv.normal_power_log2; ++i) nd = nd * nd;
-            const float ex = pq.x - ppx.x, ey = pq.y - ppx.y, ez = pq.z - ppx.z;
-            const float pd = (np.x * ex + np.y * ey) + np.z * ez;
-            const float pr = pd / plane_den;
-            const float wp = 1.f / (1.f + pr * pr);
-            float wc = 1.f;
-            if (kind == kValid) {
-                const float lx = q.x - c.x, ly = q.y - c.y, lz = q.z - c.z;
-                const float d2 = (lx * lx + ly * ly) + lz * lz;
-                wc = 1.f / (1.f + d2 / lv.color_den);
-            }
-            float w = h * nd;
-            w = w * wp;
-            w = w * wc;
+            const float w = tap_weight(h, normal_term(gc, nq), plane_term(gc, pq), color_term(kind, c, q, lv.color_den));
             if (!(w > 0.f)) continue;   // (zero and NaN weights: perpendicular faces, a centre at t = 0)
             sw = sw + w;
             sx = sx + w * q.x;

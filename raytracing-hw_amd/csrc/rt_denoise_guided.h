@@ -5,20 +5,24 @@
 // radiance is not albedo-modulated pass through, a firefly clamp runs before the filter, and the
 // colour falloff is measured in standard deviations of a per-pixel variance that is filtered along
 // with the colour.  The per-pixel text of the clamp, the variance estimate and the guided level
-// lives here, shared by the device kernels (rt_device.hip rt_denoise_guided_*_kernel) and the host
-// function (rt_host.cpp rt_denoise_guided); prepare and resolve reuse rt_denoise.h.  The same
-// arithmetic rules hold: f32 +, -, *, /, comparisons and selects in the order written, no
-// contraction, correctly rounded division.
+// lives here, shared by the device kernels (rt_denoise_device.h) and the host function (rt_host.cpp
+// rt_denoise_guided); prepare, the terms and the product of a tap's weight, and resolve are
+// rt_denoise.h's.  The same arithmetic rules hold: f32 +, -, *, /, comparisons and selects in the
+// order written, no contraction, correctly rounded division.
 #pragma once
 #include "rt_denoise.h"
 
 namespace rtdg {
 
+using rtdn::Geo;
 using rtdn::Q;
 using rtdn::finite;
+using rtdn::geo_of;
 using rtdn::kFill;
 using rtdn::kPass;
 using rtdn::kValid;
+using rtdn::normal_term;
+using rtdn::plane_term;
 
 // Defaults.  sigma_var 2 and firefly 8, with the 5 x 5 clamp window and the 7 x 7 variance window,
 // come from a coarse sweep on three small fixtures (sigma_var in {1, 2, 4}, firefly in {off, 2, 4,
@@ -59,30 +63,6 @@ RT_HD void prepare_pixel(const float *S, int n, const Q *g, Q &a, Q &nt, Q &pp) 
 }
 
 RT_HD float lum(const Q &L) { return (0.2126f * L.x + 0.7152f * L.y) + 0.0722f * L.z; }
-
-// What the centre contributes to geo(p, q) = nd * wp, rt_denoise's normal and plane terms.
-struct Geo {
-    Q np, pp;
-    float plane_den;
-    int normal_power_log2;
-};
-template <class Src>
-RT_HD Geo geo_of(const Src &src, int x, int y, float sigma_plane, int normal_power_log2) {
-    const Q np = src.nt(x, y);
-    return Geo{np, src.pp(x, y), sigma_plane * np.w, normal_power_log2};
-}
-RT_HD float normal_term(const Geo &c, const Q &nq) {
-    float nd = (c.np.x * nq.x + c.np.y * nq.y) + c.np.z * nq.z;
-    nd = nd > 0.f ? nd : 0.f;
-    for (int i = 0; i < c.normal_power_log2; ++i) nd = nd * nd;
-    return nd;
-}
-RT_HD float plane_term(const Geo &c, const Q &pq) {
-    const float ex = pq.x - c.pp.x, ey = pq.y - c.pp.y, ez = pq.z - c.pp.z;
-    const float pd = (c.np.x * ex + c.np.y * ey) + c.np.z * ez;
-    const float pr = pd / c.plane_den;
-    return 1.f / (1.f + pr * pr);
-}
 
 // The firefly clamp at (x, y): the pixel's (L, kind) with L scaled down to `firefly` times the
 // geometry-weighted mean luminance of its 5 x 5 neighbours (centre skipped).
@@ -200,15 +180,7 @@ RT_HD Pixel level_pixel(const Src &src, int x, int y, int W, int H, const Level 
             const float h = rtdn::spline(dx) * rtdn::spline(dy);
             const float nd = normal_term(gc, src.nt(qx, qy));
             const float wp = plane_term(gc, src.pp(qx, qy));
-            float wc = 1.f;
-            if (kind == kValid) {
-                const float lx = q.x - c.x, ly = q.y - c.y, lz = q.z - c.z;
-                const float d2 = (lx * lx + ly * ly) + lz * lz;
-                wc = 1.f / (1.f + d2 / color_den);
-            }
-            float w = h * nd;
-            w = w * wp;
-            w = w * wc;
+            const float w = rtdn::tap_weight(h, nd, wp, rtdn::color_term(kind, c, q, color_den));
             if (!(w > 0.f)) continue;
             sw = sw + w;
             sx = sx + w * q.x;

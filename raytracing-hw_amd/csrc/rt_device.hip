@@ -15,8 +15,9 @@
 //   rt_gbuffer_kernel       first-hit feature records from the pixel-centre rays (rt_gbuffer.h)
 //   rt_denoise_{prepare,level,resolve}_kernel  the edge-avoiding a-trous filter of a frame,
 //                           guided by those records (rt_denoise.h)
-//   rt_denoise_guided_{prepare,clamp,variance,given,level,varout}_kernel  its variance-guided
-//                           mode with a firefly clamp (rt_denoise_guided.h)
+//   rt_denoise_guided_{window,given,level,varout}_kernel  its variance-guided mode with a
+//                           firefly clamp (rt_denoise_guided.h)
+//                           (these three groups and their launch functions: rt_denoise_device.h)
 // Every schedule writes the per-pixel float RGB sum (sample_canvas, scene.cpp:20,42) of the
 // owned rows; the bits do not depend on the kernel, the launch shape, the pixel order or the
 // partition.
@@ -2430,335 +2431,9 @@ void rt_accum_free(rt_accum *a) { accum_release(a); }
 }  // extern "C"
 
 // ------------------------------------------------------------------------ feature buffer, denoiser
-// rt_gbuffer* (include/rt_hw.h, rt_gbuffer.h): one lane per shard pixel, in the shape of
-// rt_rays_kernel; the pixel-centre ray, its closest hit and the hit's attributes, written as four
-// 16-byte stores per record.
-__global__ void __launch_bounds__(256) rt_gbuffer_kernel(DevScene sc, ShardGeom g, float4 *out) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= g.n_pixels) return;
-    int px, py;
-    rtd::shard_xy(g, p, px, py);
-    const rtd::GRecord r = rtd::gbuffer_pixel(sc, px, py);
-#pragma unroll
-    for (int k = 0; k < rtd::kGbufferQuads; ++k) out[rtd::kGbufferQuads * p + k] = r.q[k];
-}
-
-// rt_denoise_device (include/rt_hw.h, rt_denoise.h): prepare packs what a tap needs into three
-// 16-byte words per pixel, (L, kind), (N, t) and (P, 0); each level reads one (L, kind) buffer and
-// writes the other; resolve remodulates.  Every kernel maps consecutive lanes to consecutive x.
-__global__ void __launch_bounds__(256) rt_denoise_prepare_kernel(const float *__restrict__ sums, const int32_t *__restrict__ counts,
-                                                                  int spp, long long n, const rtdn::Q *__restrict__ g,
-                                                                  rtdn::Q *__restrict__ a, rtdn::Q *__restrict__ nt,
-                                                                  rtdn::Q *__restrict__ pp) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const rtdn::Q rec[4] = {g[4 * p], g[4 * p + 1], g[4 * p + 2], g[4 * p + 3]};
-    const float S[3] = {sums[3 * p], sums[3 * p + 1], sums[3 * p + 2]};
-    rtdn::Q qa, qn, qp;
-    rtdn::prepare_pixel(S, counts ? counts[p] : spp, rec, qa, qn, qp);
-    a[p] = qa;
-    nt[p] = qn;
-    pp[p] = qp;
-}
-
-// The level kernel's tile: kDnTileW x kDnTileH pixels per 256-thread block, tiles numbered row-major
-// in a one-dimensional grid.  STAGE (strides 1 and 2): the tile and its halo of 2 * stride pixels
-// are staged in LDS first, 3 x 16 B per pixel (stride 2: 40 x 16 pixels, 30 KB); at stride >= 4 the
-// halo outgrows the tile and the taps read through L2 (STAGE = 0: plain loads, any stride).
-// Measured against plain loads at strides 1 and 2 on the 1080p headline frame, two alternating
-// runs each (profiles/denoise_passes.jsonl): 5 iterations 0.753-0.759 ms staged
-// against 0.833-0.836 ms plain.
-constexpr int kDnTileW = 32, kDnTileH = 8;
-
-struct DnTileSrc {
-    const rtdn::Q *A, *NT, *PP;   // LDS
-    int x0, y0, tw;               // frame coordinates of the staged tile's corner, its width
-    __device__ __forceinline__ int at(int x, int y) const { return (y - y0) * tw + (x - x0); }
-    __device__ __forceinline__ rtdn::Q a(int x, int y) const { return A[at(x, y)]; }
-    __device__ __forceinline__ rtdn::Q nt(int x, int y) const { return NT[at(x, y)]; }
-    __device__ __forceinline__ rtdn::Q pp(int x, int y) const { return PP[at(x, y)]; }
-};
-
-template <int STAGE>
-__global__ void __launch_bounds__(256) rt_denoise_level_kernel(const rtdn::Q *__restrict__ a_in, const rtdn::Q *__restrict__ nt,
-                                                                const rtdn::Q *__restrict__ pp, rtdn::Q *__restrict__ a_out,
-                                                                int W, int H, int tiles_x, rtdn::Level lv) {
-    const int ty = (int)(blockIdx.x / (unsigned)tiles_x), tx = (int)(blockIdx.x - (unsigned)ty * (unsigned)tiles_x);
-    const int lx = (int)threadIdx.x % kDnTileW, ly = (int)threadIdx.x / kDnTileW;
-    const int x = tx * kDnTileW + lx, y = ty * kDnTileH + ly;
-    if constexpr (STAGE > 0) {
-        constexpr int halo = 2 * STAGE, tw = kDnTileW + 2 * halo, th = kDnTileH + 2 * halo;
-        __shared__ rtdn::Q tile[3][tw * th];
-        const int x0 = tx * kDnTileW - halo, y0 = ty * kDnTileH - halo;
-        for (int k = (int)threadIdx.x; k < tw * th; k += 256) {
-            const int gy = y0 + k / tw, gx = x0 + k % tw;
-            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {   // (a slot outside the frame is never read: level_pixel skips the tap)
-                const long long q = (long long)gy * W + gx;
-                tile[0][k] = a_in[q];
-                tile[1][k] = nt[q];
-                tile[2][k] = pp[q];
-            }
-        }
-        __syncthreads();
-        if (x < W && y < H)
-            a_out[(long long)y * W + x] = rtdn::level_pixel(DnTileSrc{tile[0], tile[1], tile[2], x0, y0, tw}, x, y, W, H, lv);
-    } else {
-        if (x < W && y < H) a_out[(long long)y * W + x] = rtdn::level_pixel(rtdn::PlainSrc{a_in, nt, pp, W}, x, y, W, H, lv);
-    }
-}
-
-// a == nullptr (iterations = 0): every pixel's own mean.
-__global__ void __launch_bounds__(256) rt_denoise_resolve_kernel(const float *__restrict__ sums, const int32_t *__restrict__ counts,
-                                                                  int spp, long long n, const rtdn::Q *__restrict__ g,
-                                                                  const rtdn::Q *__restrict__ a, float *__restrict__ out) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const float S[3] = {sums[3 * p], sums[3 * p + 1], sums[3 * p + 2]};
-    const int cnt = counts ? counts[p] : spp;
-    float m[3];
-    if (a) {
-        const rtdn::Q rec[4] = {g[4 * p], g[4 * p + 1], g[4 * p + 2], g[4 * p + 3]};
-        rtdn::resolve_pixel(S, cnt, rec, a[p], m);
-    } else {
-        const rtdn::Q none{0.f, 0.f, 0.f, rtm::u2f(rtdn::kPass)};
-        rtdn::resolve_pixel(S, cnt, nullptr, none, m);
-    }
-    out[3 * p] = m[0];
-    out[3 * p + 1] = m[1];
-    out[3 * p + 2] = m[2];
-}
-
-// rt_denoise_guided_device (include/rt_hw.h, rt_denoise_guided.h): the variance-guided mode.  The
-// three packed words per pixel are rt_denoise_device's and the variance is a float of its own per
-// pixel; the clamp writes the other (L, kind) buffer, the variance kernel the first V buffer, and
-// each level reads one (L, kind) and V buffer and writes the other pair.  The windowed kernels use
-// the level kernel's 32 x 8 tile and stage it with a halo of REACH pixels in LDS wherever the halo is
-// smaller than the tile: the clamp (2: 36 x 12 pixels x 48 B, 20.3 KB), the variance estimate (3:
-// 38 x 14 x 48 B, 24.9 KB), the levels at strides 1 and 2 (2 and 4: 36 x 12 and 40 x 16 pixels x
-// 52 B, 21.9 and 32.5 KB); the levels at strides >= 4 read through L2.  Measured against plain
-// loads in all of them on the 1080p headline frame, two alternating runs each
-// (profiles/denoise_guided_passes.jsonl): 5 iterations 1.19 ms staged against
-// 1.60 ms plain.
-__global__ void __launch_bounds__(256) rt_denoise_guided_prepare_kernel(const float *__restrict__ sums,
-                                                                         const int32_t *__restrict__ counts, int spp, long long n,
-                                                                         const rtdn::Q *__restrict__ g, rtdn::Q *__restrict__ a,
-                                                                         rtdn::Q *__restrict__ nt, rtdn::Q *__restrict__ pp) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const rtdn::Q rec[4] = {g[4 * p], g[4 * p + 1], g[4 * p + 2], g[4 * p + 3]};
-    const float S[3] = {sums[3 * p], sums[3 * p + 1], sums[3 * p + 2]};
-    rtdn::Q qa, qn, qp;
-    rtdg::prepare_pixel(S, counts ? counts[p] : spp, rec, qa, qn, qp);
-    a[p] = qa;
-    nt[p] = qn;
-    pp[p] = qp;
-}
-
-struct DgTileSrc {
-    const rtdn::Q *A, *NT, *PP;   // LDS
-    const float *V;               // LDS (the level kernel only)
-    int x0, y0, tw;
-    __device__ __forceinline__ int at(int x, int y) const { return (y - y0) * tw + (x - x0); }
-    __device__ __forceinline__ rtdn::Q a(int x, int y) const { return A[at(x, y)]; }
-    __device__ __forceinline__ rtdn::Q nt(int x, int y) const { return NT[at(x, y)]; }
-    __device__ __forceinline__ rtdn::Q pp(int x, int y) const { return PP[at(x, y)]; }
-    __device__ __forceinline__ float v(int x, int y) const { return V[at(x, y)]; }
-};
-
-// Stages the tile at (tx, ty) with a halo of REACH pixels: slot k of tile[0..2] (and tv, where
-// v_in is given) is frame pixel (x0 + k % tw, y0 + k / tw).  A slot outside the frame is never
-// read: every window skips such a tap.
-template <int REACH>
-__device__ __forceinline__ void dg_stage(rtdn::Q (*tile)[(kDnTileW + 2 * REACH) * (kDnTileH + 2 * REACH)], float *tv,
-                                         const rtdn::Q *__restrict__ a_in, const rtdn::Q *__restrict__ nt,
-                                         const rtdn::Q *__restrict__ pp, const float *__restrict__ v_in, int x0, int y0, int W, int H) {
-    constexpr int tw = kDnTileW + 2 * REACH, th = kDnTileH + 2 * REACH;
-    for (int k = (int)threadIdx.x; k < tw * th; k += 256) {
-        const int gy = y0 + k / tw, gx = x0 + k % tw;
-        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
-            const long long q = (long long)gy * W + gx;
-            tile[0][k] = a_in[q];
-            tile[1][k] = nt[q];
-            tile[2][k] = pp[q];
-            if (tv) tv[k] = v_in[q];
-        }
-    }
-    __syncthreads();
-}
-
-__global__ void __launch_bounds__(256) rt_denoise_guided_clamp_kernel(const rtdn::Q *__restrict__ a_in, const rtdn::Q *__restrict__ nt,
-                                                                       const rtdn::Q *__restrict__ pp, rtdn::Q *__restrict__ a_out,
-                                                                       int W, int H, int tiles_x, rtdg::Params dp) {
-    constexpr int reach = rtdg::kClampReach, tw = kDnTileW + 2 * reach, th = kDnTileH + 2 * reach;
-    const int ty = (int)(blockIdx.x / (unsigned)tiles_x), tx = (int)(blockIdx.x - (unsigned)ty * (unsigned)tiles_x);
-    const int lx = (int)threadIdx.x % kDnTileW, ly = (int)threadIdx.x / kDnTileW;
-    const int x = tx * kDnTileW + lx, y = ty * kDnTileH + ly;
-    __shared__ rtdn::Q tile[3][tw * th];
-    const int x0 = tx * kDnTileW - reach, y0 = ty * kDnTileH - reach;
-    dg_stage<reach>(tile, nullptr, a_in, nt, pp, nullptr, x0, y0, W, H);
-    if (x < W && y < H)
-        a_out[(long long)y * W + x] = rtdg::clamp_pixel(DgTileSrc{tile[0], tile[1], tile[2], nullptr, x0, y0, tw}, x, y, W, H, dp);
-}
-
-__global__ void __launch_bounds__(256) rt_denoise_guided_variance_kernel(const rtdn::Q *__restrict__ a_in,
-                                                                          const rtdn::Q *__restrict__ nt,
-                                                                          const rtdn::Q *__restrict__ pp, float *__restrict__ v_out,
-                                                                          int W, int H, int tiles_x, rtdg::Params dp) {
-    constexpr int reach = rtdg::kVarianceReach, tw = kDnTileW + 2 * reach, th = kDnTileH + 2 * reach;
-    const int ty = (int)(blockIdx.x / (unsigned)tiles_x), tx = (int)(blockIdx.x - (unsigned)ty * (unsigned)tiles_x);
-    const int lx = (int)threadIdx.x % kDnTileW, ly = (int)threadIdx.x / kDnTileW;
-    const int x = tx * kDnTileW + lx, y = ty * kDnTileH + ly;
-    __shared__ rtdn::Q tile[3][tw * th];
-    const int x0 = tx * kDnTileW - reach, y0 = ty * kDnTileH - reach;
-    dg_stage<reach>(tile, nullptr, a_in, nt, pp, nullptr, x0, y0, W, H);
-    if (x < W && y < H)
-        v_out[(long long)y * W + x] = rtdg::variance_pixel(DgTileSrc{tile[0], tile[1], tile[2], nullptr, x0, y0, tw}, x, y, W, H, dp);
-}
-
-// The caller's variance in place of the estimate.
-__global__ void __launch_bounds__(256) rt_denoise_guided_given_kernel(const rtdn::Q *__restrict__ a, const float *__restrict__ variance,
-                                                                       long long n, float *__restrict__ v_out) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n) v_out[p] = rtdg::given_variance(rtm::f2u(a[p].w), variance[p]);
-}
-
-template <int STAGE>
-__global__ void __launch_bounds__(256) rt_denoise_guided_level_kernel(const rtdn::Q *__restrict__ a_in, const float *__restrict__ v_in,
-                                                                       const rtdn::Q *__restrict__ nt, const rtdn::Q *__restrict__ pp,
-                                                                       rtdn::Q *__restrict__ a_out, float *__restrict__ v_out, int W,
-                                                                       int H, int tiles_x, rtdg::Level lv) {
-    const int ty = (int)(blockIdx.x / (unsigned)tiles_x), tx = (int)(blockIdx.x - (unsigned)ty * (unsigned)tiles_x);
-    const int lx = (int)threadIdx.x % kDnTileW, ly = (int)threadIdx.x / kDnTileW;
-    const int x = tx * kDnTileW + lx, y = ty * kDnTileH + ly;
-    rtdg::Pixel r;
-    if constexpr (STAGE > 0) {
-        constexpr int reach = 2 * STAGE, tw = kDnTileW + 2 * reach, th = kDnTileH + 2 * reach;
-        __shared__ rtdn::Q tile[3][tw * th];
-        __shared__ float tv[tw * th];
-        const int x0 = tx * kDnTileW - reach, y0 = ty * kDnTileH - reach;
-        dg_stage<reach>(tile, tv, a_in, nt, pp, v_in, x0, y0, W, H);
-        if (x >= W || y >= H) return;
-        r = rtdg::level_pixel(DgTileSrc{tile[0], tile[1], tile[2], tv, x0, y0, tw}, x, y, W, H, lv);
-    } else {
-        if (x >= W || y >= H) return;
-        r = rtdg::level_pixel(rtdg::PlainSrc{a_in, nt, pp, v_in, W}, x, y, W, H, lv);
-    }
-    a_out[(long long)y * W + x] = r.a;
-    v_out[(long long)y * W + x] = r.v;
-}
-
-// a == nullptr (iterations = 0): zeros.
-__global__ void __launch_bounds__(256) rt_denoise_guided_varout_kernel(const rtdn::Q *__restrict__ a, const float *__restrict__ v,
-                                                                        long long n, float *__restrict__ out) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n) out[p] = a ? rtdg::resolve_variance(a[p], v[p]) : 0.f;
-}
+#include "rt_denoise_device.h"   // the kernels and their launch functions
 
 namespace {
-
-// The G-buffer of a shard into device memory (the current device is the scene copy's).
-int gbuffer_launch(rt_device_scene *d, const ShardGeom &g, float4 *d_out, hipStream_t stream) {
-    if (g.n_pixels == 0) return RT_OK;
-    hipLaunchKernelGGL(rt_gbuffer_kernel, dim3((unsigned)((g.n_pixels + 255) / 256)), dim3(256), 0, stream, d->ds, g, d_out);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
-
-// The filter on the current device.  `ws` / `ws_bytes`: the scratch of the call's owner (an
-// accumulator, or the device's cache below), grown here on first use; 64 B per pixel: the two
-// (L, kind) buffers, (N, t) and (P, 0).
-int denoise_launch(void **ws, size_t *ws_bytes, const float *d_sums, const int32_t *d_counts, int spp, int W, int H,
-                   const float *d_g, const rtdn::Params &dp, float *d_out, hipStream_t stream) {
-    const long long n = (long long)W * H;
-    const dim3 flat((unsigned)((n + 255) / 256));
-    const rtdn::Q *g = (const rtdn::Q *)d_g;
-    if (dp.iterations == 0) {
-        hipLaunchKernelGGL(rt_denoise_resolve_kernel, flat, dim3(256), 0, stream, d_sums, d_counts, spp, n, g,
-                           (const rtdn::Q *)nullptr, d_out);
-        HIP_TRY(hipGetLastError());
-        return RT_OK;
-    }
-    HIP_TRY(grow(ws, ws_bytes, (size_t)n * 4 * sizeof(rtdn::Q)));
-    rtdn::Q *a[2] = {(rtdn::Q *)*ws, (rtdn::Q *)*ws + n};
-    rtdn::Q *nt = (rtdn::Q *)*ws + 2 * n, *pp = (rtdn::Q *)*ws + 3 * n;
-    hipLaunchKernelGGL(rt_denoise_prepare_kernel, flat, dim3(256), 0, stream, d_sums, d_counts, spp, n, g, a[0], nt, pp);
-    const int tiles_x = (W + kDnTileW - 1) / kDnTileW, tiles_y = (H + kDnTileH - 1) / kDnTileH;
-    const dim3 tiles((unsigned)((long long)tiles_x * tiles_y));   // (below 2^31: the frame is)
-    for (int k = 0; k < dp.iterations; ++k) {
-        const rtdn::Level lv = rtdn::level_of(dp, k);
-        const rtdn::Q *in = a[k & 1];
-        rtdn::Q *out = a[(k + 1) & 1];
-        if (lv.stride == 1)
-            hipLaunchKernelGGL(rt_denoise_level_kernel<1>, tiles, dim3(256), 0, stream, in, nt, pp, out, W, H, tiles_x, lv);
-        else if (lv.stride == 2)
-            hipLaunchKernelGGL(rt_denoise_level_kernel<2>, tiles, dim3(256), 0, stream, in, nt, pp, out, W, H, tiles_x, lv);
-        else
-            hipLaunchKernelGGL(rt_denoise_level_kernel<0>, tiles, dim3(256), 0, stream, in, nt, pp, out, W, H, tiles_x, lv);
-    }
-    hipLaunchKernelGGL(rt_denoise_resolve_kernel, flat, dim3(256), 0, stream, d_sums, d_counts, spp, n, g,
-                       (const rtdn::Q *)a[dp.iterations & 1], d_out);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
-
-// The variance-guided mode on the current device, on the same scratch rules; 72 B per pixel:
-// denoise_launch's 64 and the two variance buffers (d_var / d_out_var: the caller's variance, the
-// filtered variance out, or NULL).
-int denoise_guided_launch(void **ws, size_t *ws_bytes, const float *d_sums, const int32_t *d_counts, int spp, int W, int H,
-                          const float *d_g, const float *d_var, const rtdg::Params &dp, float *d_out, float *d_out_var,
-                          hipStream_t stream) {
-    const long long n = (long long)W * H;
-    const dim3 flat((unsigned)((n + 255) / 256));
-    const rtdn::Q *g = (const rtdn::Q *)d_g;
-    if (dp.iterations == 0) {
-        hipLaunchKernelGGL(rt_denoise_resolve_kernel, flat, dim3(256), 0, stream, d_sums, d_counts, spp, n, g,
-                           (const rtdn::Q *)nullptr, d_out);
-        if (d_out_var)
-            hipLaunchKernelGGL(rt_denoise_guided_varout_kernel, flat, dim3(256), 0, stream, (const rtdn::Q *)nullptr,
-                               (const float *)nullptr, n, d_out_var);
-        HIP_TRY(hipGetLastError());
-        return RT_OK;
-    }
-    HIP_TRY(grow(ws, ws_bytes, (size_t)n * (4 * sizeof(rtdn::Q) + 2 * sizeof(float))));
-    rtdn::Q *a[2] = {(rtdn::Q *)*ws, (rtdn::Q *)*ws + n};
-    rtdn::Q *nt = (rtdn::Q *)*ws + 2 * n, *pp = (rtdn::Q *)*ws + 3 * n;
-    float *v[2] = {(float *)((rtdn::Q *)*ws + 4 * n), (float *)((rtdn::Q *)*ws + 4 * n) + n};
-    hipLaunchKernelGGL(rt_denoise_guided_prepare_kernel, flat, dim3(256), 0, stream, d_sums, d_counts, spp, n, g, a[0], nt, pp);
-    const int tiles_x = (W + kDnTileW - 1) / kDnTileW, tiles_y = (H + kDnTileH - 1) / kDnTileH;
-    const dim3 tiles((unsigned)((long long)tiles_x * tiles_y));
-    int cur = 0;   // the buffers that hold (L, kind) and V
-    if (!(dp.firefly < 0.f)) {
-        hipLaunchKernelGGL(rt_denoise_guided_clamp_kernel, tiles, dim3(256), 0, stream, (const rtdn::Q *)a[0], (const rtdn::Q *)nt,
-                           (const rtdn::Q *)pp, a[1], W, H, tiles_x, dp);
-        cur = 1;
-    }
-    if (d_var)
-        hipLaunchKernelGGL(rt_denoise_guided_given_kernel, flat, dim3(256), 0, stream, (const rtdn::Q *)a[cur], d_var, n, v[cur]);
-    else
-        hipLaunchKernelGGL(rt_denoise_guided_variance_kernel, tiles, dim3(256), 0, stream, (const rtdn::Q *)a[cur], (const rtdn::Q *)nt,
-                           (const rtdn::Q *)pp, v[cur], W, H, tiles_x, dp);
-    for (int k = 0; k < dp.iterations; ++k, cur ^= 1) {
-        const rtdg::Level lv = rtdg::level_of(dp, k);
-        const rtdn::Q *in = a[cur], *cnt = nt, *cpp = pp;
-        const float *vin = v[cur];
-        if (lv.stride == 1)
-            hipLaunchKernelGGL(rt_denoise_guided_level_kernel<1>, tiles, dim3(256), 0, stream, in, vin, cnt, cpp, a[cur ^ 1], v[cur ^ 1],
-                               W, H, tiles_x, lv);
-        else if (lv.stride == 2)
-            hipLaunchKernelGGL(rt_denoise_guided_level_kernel<2>, tiles, dim3(256), 0, stream, in, vin, cnt, cpp, a[cur ^ 1], v[cur ^ 1],
-                               W, H, tiles_x, lv);
-        else
-            hipLaunchKernelGGL(rt_denoise_guided_level_kernel<0>, tiles, dim3(256), 0, stream, in, vin, cnt, cpp, a[cur ^ 1], v[cur ^ 1],
-                               W, H, tiles_x, lv);
-    }
-    hipLaunchKernelGGL(rt_denoise_resolve_kernel, flat, dim3(256), 0, stream, d_sums, d_counts, spp, n, g, (const rtdn::Q *)a[cur],
-                       d_out);
-    if (d_out_var)
-        hipLaunchKernelGGL(rt_denoise_guided_varout_kernel, flat, dim3(256), 0, stream, (const rtdn::Q *)a[cur], (const float *)v[cur],
-                           n, d_out_var);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
 
 // rt_denoise_device's and rt_denoise_guided_device's scratch, per device, from the first call on
 // (only grows).
@@ -2963,16 +2638,6 @@ int rt_accum_frame_u8_guided(rt_accum *a, const rt_denoise_guided_params *params
 }  // extern "C"
 
 namespace {
-
-// rt_variance_kernel on the current device.
-int variance_launch(const float *d_sums, const float *d_moments, const int32_t *d_counts, int spp, long long n, const float *d_g,
-                    float *d_out, hipStream_t stream) {
-    if (n == 0) return RT_OK;
-    hipLaunchKernelGGL(rt_variance_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_sums, d_moments, d_counts,
-                       spp, n, (const float4 *)d_g, d_out);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
 
 // A moments accumulator's measured variance into a->var on a->stream (the current device is the
 // accumulator's): its own counts, and its shard's first-hit records, rendered on first use.

@@ -981,13 +981,19 @@ int32_t rt_abi_version(void) { return RT_ABI_VERSION; }
 
 }  // extern "C"
 
-int rt_denoise_check(const char *who, const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
-                     const float *gbuffer, const rt_denoise_params *params, const float *out_mean, rtdn::Params *resolved) {
-    const std::string w = who;
-    if (!sums || !gbuffer || !out_mean) return rt_fail(RT_ERR_ARG, w + ": NULL argument");
+// What the three checks below refuse alike, in this order.
+static int frame_check(const std::string &w, bool null_argument, const int32_t *counts, int32_t spp, int32_t width, int32_t height) {
+    if (null_argument) return rt_fail(RT_ERR_ARG, w + ": NULL argument");
     if (width <= 0 || height <= 0) return rt_fail(RT_ERR_ARG, w + ": bad frame size");
     if (!counts && spp < 1) return rt_fail(RT_ERR_ARG, w + ": without counts, spp must be at least 1");
     if ((int64_t)width * height > INT32_MAX) return rt_fail(RT_ERR_LIMIT, w + ": frames above 2^31 pixels are not supported");
+    return RT_OK;
+}
+
+int rt_denoise_check(const char *who, const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
+                     const float *gbuffer, const rt_denoise_params *params, const float *out_mean, rtdn::Params *resolved) {
+    const std::string w = who;
+    if (int rc = frame_check(w, !sums || !gbuffer || !out_mean, counts, spp, width, height)) return rc;
     const rt_denoise_params none{-1, 0.f, 0.f, 0};
     const rt_denoise_params &p = params ? *params : none;
     if (rtdn::resolve_params(p.iterations, p.sigma_color, p.sigma_plane, p.normal_power_log2, *resolved))
@@ -1000,10 +1006,7 @@ int rt_denoise_guided_check(const char *who, const float *sums, const int32_t *c
                             const float *gbuffer, const rt_denoise_guided_params *params, const float *out_mean,
                             rtdg::Params *resolved) {
     const std::string w = who;
-    if (!sums || !gbuffer || !out_mean) return rt_fail(RT_ERR_ARG, w + ": NULL argument");
-    if (width <= 0 || height <= 0) return rt_fail(RT_ERR_ARG, w + ": bad frame size");
-    if (!counts && spp < 1) return rt_fail(RT_ERR_ARG, w + ": without counts, spp must be at least 1");
-    if ((int64_t)width * height > INT32_MAX) return rt_fail(RT_ERR_LIMIT, w + ": frames above 2^31 pixels are not supported");
+    if (int rc = frame_check(w, !sums || !gbuffer || !out_mean, counts, spp, width, height)) return rc;
     const rt_denoise_guided_params none{-1, 0.f, 0.f, 0, 0.f};
     const rt_denoise_guided_params &p = params ? *params : none;
     if (rtdg::resolve_params(p.iterations, p.sigma_var, p.sigma_plane, p.normal_power_log2, p.firefly, *resolved))
@@ -1014,12 +1017,7 @@ int rt_denoise_guided_check(const char *who, const float *sums, const int32_t *c
 
 int rt_variance_check(const char *who, const float *sums, const float *moments, const int32_t *counts, int32_t spp, int32_t width,
                       int32_t height, const float *gbuffer, const float *out) {
-    const std::string w = who;
-    if (!sums || !moments || !gbuffer || !out) return rt_fail(RT_ERR_ARG, w + ": NULL argument");
-    if (width <= 0 || height <= 0) return rt_fail(RT_ERR_ARG, w + ": bad frame size");
-    if (!counts && spp < 1) return rt_fail(RT_ERR_ARG, w + ": without counts, spp must be at least 1");
-    if ((int64_t)width * height > INT32_MAX) return rt_fail(RT_ERR_LIMIT, w + ": frames above 2^31 pixels are not supported");
-    return RT_OK;
+    return frame_check(who, !sums || !moments || !gbuffer || !out, counts, spp, width, height);
 }
 
 int64_t rt_shard_rows_impl(int32_t height, int32_t rank, int32_t world, int32_t row_block, int32_t *rows_out) {

@@ -20,11 +20,11 @@ def same_bits(a, b):
 
 @pytest.fixture(scope="module")
 def frames():
-    return {(w, h): synthetic(w, h) for w, h in [(37, 23), (70, 45)]}
+    return {(w, h): synthetic(w, h) for w, h in [(5, 3), (32, 8), (37, 23), (70, 45)]}
 
 
 @pytest.mark.parametrize("iterations", [1, 2, 3, 4, 5, 6])
-@pytest.mark.parametrize("w,h", [(37, 23), (70, 45)])
+@pytest.mark.parametrize("w,h", [(5, 3), (32, 8), (37, 23), (70, 45)])
 def test_host_function_is_the_specification(rt, frames, w, h, iterations):
     """Division is correctly rounded on both sides and nothing is contracted: no tolerance."""
     sums, counts, rec, _ = frames[w, h]

@@ -108,9 +108,10 @@ def device_denoise(gpu, sums, counts, spp, rec, **params):
     return d_o.cpu().numpy()
 
 
-# 20 x 7: inside one 32 x 8 tile; 33 x 17: one column past a tile, smaller than the stride-16 reach;
+# 5 x 3: smaller than every window; 20 x 7: inside one 32 x 8 tile; 32 x 8: exactly one tile, every
+# halo slot outside the frame; 33 x 17: one column past a tile, smaller than the stride-16 reach;
 # 70 x 45: straddles tiles in both axes
-@pytest.mark.parametrize("which", [(20, 7), (33, 17), (70, 45), "real"])
+@pytest.mark.parametrize("which", [(5, 3), (20, 7), (32, 8), (33, 17), (70, 45), "real"])
 def test_device_filter_matches_the_host_function(gpu, which):
     """Iterations 0 .. 6 cover the staged levels (strides 1 and 2) and the levels that read
     through L2 (strides 4 to 32); the second run reuses the cached scratch."""

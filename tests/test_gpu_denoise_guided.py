@@ -62,7 +62,7 @@ def check_device(gpu, sums, counts_or_spp, rec, variance=None, runs=1, **params)
 
 # 5 x 3: smaller than every window; 20 x 7: inside one 32 x 8 tile; 33 x 17: one column past a tile;
 # 70 x 45: straddles tiles in both axes
-@pytest.mark.parametrize("which", [(5, 3), (20, 7), (33, 17), (70, 45), "real"])
+@pytest.mark.parametrize("which", [(5, 3), (20, 7), (32, 8), (33, 17), (70, 45), "real"])
 def test_device_filter_matches_the_host_function(gpu, which):
     """Iterations 0 .. 6 cover the staged levels (strides 1 and 2) and the levels that read through
     L2; the second run reuses the scratch."""
