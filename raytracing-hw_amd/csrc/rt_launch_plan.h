@@ -141,6 +141,7 @@ struct PlanIn {
     // units_of; the host keeps it at or below kFastMaxChunks by splitting the pass).
     bool fast_accum = false;
     int fast_units = 0;
+    bool moments = false;   // that accumulator keeps second moments (rt_accum_create_fast_moments)
 };
 
 // The two order flags exclude each other (shared with the accumulator's parameter check).
@@ -159,12 +160,41 @@ inline Refusal plan_check(const PlanIn &in) {
     return {};
 }
 
-// The rt_mega_kernel instantiation (rt_device.hip mega_kernel_of).  `chain`: a pass of an
+// The rt_mega_kernel instantiation (rt_mega_device.h mega_kernel_of).  `chain`: a pass of an
 // accumulator, on the plain or the runahead kernel (parity), or with `fast` the pass of a fast
-// accumulator (PlanIn.fast_accum); rt_accum_* refuse the other modes.
+// accumulator (PlanIn.fast_accum), with `mom` one that keeps second moments; rt_accum_* refuse
+// the other modes.
 struct Variant {
-    bool count = false, fast = false, lsplit = false, spec = false, chain = false;
+    bool count = false, fast = false, lsplit = false, spec = false, chain = false, mom = false;
 };
+// The eleven instantiations that exist, in the order of the device listing: the kernel table is
+// generated from these lines (rt_mega_device.h), and a variant that is not among them has no
+// kernel (variant_index < 0: launch() refuses it).  A new instantiation is one line here plus
+// what its MegaCfg reads.
+constexpr Variant kVariants[] = {
+    // count, fast, lsplit, spec, chain, mom
+    {true, true, false, false, false, false},    // RT_FLAG_FAST with counters; the order pre-pass (launch_order)
+    {false, false, false, true, true, false},    // a parity accumulator's pass on a small shard or subset; its hand-off relaunch
+    {false, false, false, true, false, false},   // the runahead kernel: a parity render of a small shard; the hand-off relaunch
+    {false, true, false, false, false, false},   // RT_FLAG_FAST
+    {true, false, true, false, false, false},    // RT_FLAG_LIGHT_SPLIT with counters
+    {false, false, true, false, false, false},   // RT_FLAG_LIGHT_SPLIT
+    {false, false, false, false, false, false},  // the plain kernel: a parity render of a large shard
+    {true, false, false, false, false, false},   // a parity render with counters
+    {false, false, false, false, true, false},   // a parity accumulator's pass on a large shard
+    {false, true, false, false, true, false},    // a fast accumulator's pass (rt_accum_create_fast)
+    {false, true, false, false, true, true},     // a moments accumulator's pass (rt_accum_create_fast_moments)
+};
+constexpr int kNumVariants = (int)(sizeof kVariants / sizeof kVariants[0]);
+constexpr int variant_bits(const Variant &v) {
+    return v.count | v.fast << 1 | v.lsplit << 2 | v.spec << 3 | v.chain << 4 | v.mom << 5;
+}
+// The entry of kVariants that is v, or -1.
+constexpr int variant_index(const Variant &v) {
+    for (int i = 0; i < kNumVariants; ++i)
+        if (variant_bits(kVariants[i]) == variant_bits(v)) return i;
+    return -1;
+}
 
 struct Schedule {
     Refusal refused;
@@ -172,6 +202,7 @@ struct Schedule {
     Variant v;
     uint64_t sched = 0;      // rt_stats.schedule (RT_SCHED_*)
     bool handoff = false;    // the plain kernel parks its tail and a runahead launch resumes it
+    int mode = 0;            // the kernel's last argument: mode_pack's word, a fast pass's units per item
     bool ordered = false;    // the heaviest-first pixel order is built (launch_order)
     int cs = 0, chunks = 1;  // fast mode: samples per work unit, units per pixel
     long long n_items = 0;   // queue items: pixels x chunks
@@ -203,6 +234,7 @@ inline Schedule plan_schedule(const PlanIn &in) {
     v.fast = fast_pass || (in.flags & RT_FLAG_FAST) != 0;
     v.lsplit = !v.fast && (in.flags & RT_FLAG_LIGHT_SPLIT) != 0;
     v.chain = in.pass_spp > 0;
+    v.mom = fast_pass && in.moments;
     // fast mode (RT_FLAG_FAST): work units of `cs` samples, Philox seed per sample, at most
     // kFastMaxChunks units per pixel (partials: pixels x chunks x 12 B)
     if (fast_pass) {
@@ -232,6 +264,7 @@ inline Schedule plan_schedule(const PlanIn &in) {
     s.handoff = parity && !v.spec && kClaimStride == 1;
     s.sched = v.fast ? RT_SCHED_FAST : v.lsplit ? RT_SCHED_LIGHT_SPLIT : v.spec ? RT_SCHED_RUNAHEAD : RT_SCHED_LANE;
     if (s.handoff) s.sched |= RT_SCHED_RUNAHEAD;
+    s.mode = v.fast && v.chain ? s.chunks : mode_pack(s.handoff ? kHandoffBelow : 0, 0);
     // (a pass is ordered by the rule on its own samples)
     s.ordered = !v.fast && !subset && !(in.flags & RT_FLAG_NATURAL_ORDER) &&
                 (s.stats_spp >= kOrderMinSpp || (in.flags & RT_FLAG_HEAVY_ORDER));
@@ -249,6 +282,7 @@ struct Grid {
     // waves, the park-list slots dealt at its start and how many of them each wave takes
     // (resume_deal, as at the kernel's resume site).
     long long blocks2 = 0, waves2 = 0, dealt = 0, per2 = 0;
+    int mode2 = 0;          // the relaunch's `mode` argument
     bool spread2 = false;   // the parked pixels are dealt heaviest first (else in slot order)
 };
 
@@ -270,6 +304,7 @@ inline Grid plan_grid(const Schedule &s, long long variant_blocks) {
         const Deal deal = resume_deal(g.slots, kHandoffPct, g.waves2);
         g.dealt = deal.dealt;
         g.per2 = deal.per;
+        g.mode2 = mode_pack(0, kHandoffPct);
         // (with the pixel order's estimates at hand; the order buffer holds n_pixels per array)
         g.spread2 = kHandoffSpread && s.ordered && g.slots <= s.n_pixels;
     }

@@ -1,5 +1,5 @@
 // rt_mega_prof.h — the diagnostics build of the lane-resident kernel (make prof, RT_MEGA_PROF).
-// Included by rt_device.hip only, under the macro, ahead of rt_mega_kernel: the device globals
+// Included by rt_mega_device.h only, under the macro, ahead of rt_mega_kernel: the device globals
 // the kernel's #ifdef RT_MEGA_PROF lines add to, TbAcc, and the host side's two calls,
 // mega_prof_reset before a lane-resident launch and mega_prof_report after it.
 #pragma once

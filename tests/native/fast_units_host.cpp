@@ -5,7 +5,7 @@
 #include <cstring>
 
 #include "../../raytracing-hw_amd/csrc/rt_fast_units.h"
-#include "../../raytracing-hw_amd/csrc/rt_launch_plan.h"
+#include "plan_io.h"
 
 extern "C" {
 
@@ -43,81 +43,7 @@ int fu_open_words_fit(unsigned next, int c, const unsigned *open_words) { return
 
 int fu_max_chunks() { return rtp::kFastMaxChunks; }
 
-// plan_host.cpp's input with the fields that came later, and its output.
-struct fu_in {
-    int flags, kernel, count, fast_chunk, spp, pass_spp;
-    long long n_pixels;
-    int ray_depth, n_nodes;
-    long long spec_blocks, variant_blocks, subset_items;
-    int fast_accum, fast_units;
-};
-
-struct fu_out {
-    int err, lane;
-    int v_count, v_fast, v_lsplit, v_spec, v_chain;
-    unsigned long long sched;
-    int handoff, ordered, cs, chunks;
-    long long n_items;
-    int round_min, stats_spp;
-    long long blocks, slots, groups, per;
-    long long blocks2, waves2, dealt, per2;
-    int spread2;
-    char msg[192];
-};
-
-int fu_plan(const fu_in *i, fu_out *o) {
-    std::memset(o, 0, sizeof *o);
-    rtp::PlanIn in;
-    in.flags = i->flags;
-    in.kernel = i->kernel;
-    in.count = i->count;
-    in.fast_chunk = i->fast_chunk;
-    in.spp = i->spp;
-    in.pass_spp = i->pass_spp;
-    in.n_pixels = i->n_pixels;
-    in.ray_depth = i->ray_depth;
-    in.n_nodes = i->n_nodes;
-    in.spec_blocks = i->spec_blocks;
-    in.subset_items = i->subset_items;
-    in.fast_accum = i->fast_accum != 0;
-    in.fast_units = i->fast_units;
-    const rtp::Schedule s = rtp::plan_schedule(in);
-    if (s.refused) {
-        o->err = s.refused.code;
-        std::strncpy(o->msg, s.refused.msg.c_str(), sizeof o->msg - 1);
-        return o->err;
-    }
-    o->lane = s.lane;
-    o->v_count = s.v.count;
-    o->v_fast = s.v.fast;
-    o->v_lsplit = s.v.lsplit;
-    o->v_spec = s.v.spec;
-    o->v_chain = s.v.chain;
-    o->sched = s.sched;
-    o->handoff = s.handoff;
-    o->ordered = s.ordered;
-    o->cs = s.cs;
-    o->chunks = s.chunks;
-    o->n_items = s.n_items;
-    o->round_min = s.round_min;
-    o->stats_spp = s.stats_spp;
-    if (!s.lane) return RT_OK;
-    const rtp::Grid g = rtp::plan_grid(s, i->variant_blocks);
-    if (g.refused) {
-        o->err = g.refused.code;
-        std::strncpy(o->msg, g.refused.msg.c_str(), sizeof o->msg - 1);
-        return o->err;
-    }
-    o->blocks = g.blocks;
-    o->slots = g.slots;
-    o->groups = g.groups;
-    o->per = g.per;
-    o->blocks2 = g.blocks2;
-    o->waves2 = g.waves2;
-    o->dealt = g.dealt;
-    o->per2 = g.per2;
-    o->spread2 = g.spread2;
-    return RT_OK;
-}
+// The launch plan (plan_io.h), for the fast-pass fields.
+int fu_plan(const plan_in *i, plan_out *o) { return plan_fill(i, o); }
 
 }  // extern "C"

@@ -16,8 +16,8 @@
 #include <limits>
 #include <vector>
 
-#include "../../raytracing-hw_amd/csrc/rt_launch_plan.h"
 #include "../../raytracing-hw_amd/csrc/rt_select.h"
+#include "plan_io.h"
 
 extern "C" {
 
@@ -67,69 +67,8 @@ long long sh_select(const sh_rule *r, int width, int height, int rank, int world
     return n;
 }
 
-// The launch plan with the subset field (plan_host.cpp's ph_in / ph_out, plus subset_items).
-struct sh_plan_in {
-    int flags, kernel, count, fast_chunk, spp, pass_spp;
-    long long n_pixels;
-    int ray_depth, n_nodes;
-    long long spec_blocks, variant_blocks, subset_items;
-};
-struct sh_plan_out {
-    int err, lane;
-    int v_count, v_fast, v_lsplit, v_spec, v_chain;
-    unsigned long long sched;
-    int handoff, ordered, cs, chunks;
-    long long n_items;
-    int round_min, stats_spp;
-    long long blocks, slots, groups, per;
-    long long blocks2, waves2, dealt, per2;
-    int spread2;
-};
-
-int sh_plan(const sh_plan_in *i, sh_plan_out *o) {
-    std::memset(o, 0, sizeof *o);
-    rtp::PlanIn in;
-    in.flags = i->flags;
-    in.kernel = i->kernel;
-    in.count = i->count;
-    in.fast_chunk = i->fast_chunk;
-    in.spp = i->spp;
-    in.pass_spp = i->pass_spp;
-    in.n_pixels = i->n_pixels;
-    in.ray_depth = i->ray_depth;
-    in.n_nodes = i->n_nodes;
-    in.spec_blocks = i->spec_blocks;
-    in.subset_items = i->subset_items;
-    const rtp::Schedule s = rtp::plan_schedule(in);
-    if (s.refused) return o->err = s.refused.code;
-    o->lane = s.lane;
-    o->v_count = s.v.count;
-    o->v_fast = s.v.fast;
-    o->v_lsplit = s.v.lsplit;
-    o->v_spec = s.v.spec;
-    o->v_chain = s.v.chain;
-    o->sched = s.sched;
-    o->handoff = s.handoff;
-    o->ordered = s.ordered;
-    o->cs = s.cs;
-    o->chunks = s.chunks;
-    o->n_items = s.n_items;
-    o->round_min = s.round_min;
-    o->stats_spp = s.stats_spp;
-    if (!s.lane) return RT_OK;
-    const rtp::Grid g = rtp::plan_grid(s, i->variant_blocks);
-    if (g.refused) return o->err = g.refused.code;
-    o->blocks = g.blocks;
-    o->slots = g.slots;
-    o->groups = g.groups;
-    o->per = g.per;
-    o->blocks2 = g.blocks2;
-    o->waves2 = g.waves2;
-    o->dealt = g.dealt;
-    o->per2 = g.per2;
-    o->spread2 = g.spread2;
-    return RT_OK;
-}
+// The launch plan (plan_io.h), for the subset fields.
+int sh_plan(const plan_in *i, plan_out *o) { return plan_fill(i, o); }
 
 }  // extern "C"
 
@@ -177,8 +116,8 @@ int main(int argc, char **argv) {
         std::fwrite(&hi, 4, 1, out);
         if (k) std::fwrite(list.data(), 4, (size_t)k, out);
         // the plan's subset rule on this case's numbers, for the sanitizers' benefit
-        sh_plan_in pi{0, 0, 0, 0, r.target, 1, (long long)n, 8, 100, 1024, 1024, k};
-        sh_plan_out po;
+        plan_in pi{0, 0, 0, 0, r.target, 1, (long long)n, 8, 100, 1024, 1024, k, 0, 0, 0};
+        plan_out po;
         if (k > 0 && n > 0 && (sh_plan(&pi, &po) != 0 || po.n_items != k || po.ordered)) return 5;
     }
     std::fclose(in);

@@ -13,7 +13,8 @@ import pytest
 
 import rtref
 from test_accum import _header, _load
-from test_launch_plan import In as PlanIn, Out as PlanOut, PLAIN_BLOCKS, SPEC_BLOCKS, HD, SRC as PLAN_SRC
+from plan_util import PlanIn, PlanOut
+from test_launch_plan import PLAIN_BLOCKS, SPEC_BLOCKS, HD, SRC as PLAN_SRC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "fast_units_host.cpp")
@@ -28,8 +29,7 @@ CHUNKS = (1, 2, 3, 8)
 N_MAX = 20
 
 
-class FuIn(ctypes.Structure):
-    _fields_ = PlanIn._fields_ + [("subset_items", ctypes.c_longlong), ("fast_accum", ctypes.c_int), ("fast_units", ctypes.c_int)]
+FuIn = PlanIn   # (one pair of structures for every plan shim: plan_util.py)
 
 
 @pytest.fixture(scope="module")

@@ -56,7 +56,8 @@ def _check_variants(gpu, scene, s, ref, cnt, tag, light_split=True):
         assert _counters(st) == cnt, (tag, kw)
         assert st["schedule"] == sched, (tag, kw)
     for kw, sched in [(dict(), gpu.SCHED_RUNAHEAD), (dict(runahead=False), gpu.SCHED_LANE),
-                      (dict(kernel=4), gpu.SCHED_WAVEFRONT)]:
+                      (dict(kernel=4), gpu.SCHED_WAVEFRONT)] + \
+                     ([(dict(light_split=True), gpu.SCHED_LIGHT_SPLIT)] if light_split else []):
         out, st = scene.render_sums(s, **kw)
         _same(out, ref, f"{tag} {kw}")
         assert st["schedule"] == sched, (tag, kw)

@@ -10,6 +10,8 @@ from fractions import Fraction
 
 import pytest
 
+from plan_util import PlanIn as In, PlanOut as Out
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "plan_host.cpp")
 PLAIN_BLOCKS, SPEC_BLOCKS = 1280, 1024
@@ -17,21 +19,6 @@ LANE, RUNAHEAD, FAST, LIGHT_SPLIT, WAVEFRONT = 1, 2, 4, 8, 16          # RT_SCHE
 F_FAST, F_LSPLIT, F_NATURAL, F_NO_RUNAHEAD, F_HEAVY = 2, 4, 8, 16, 32   # RT_FLAG_*
 ERR_ARG, ERR_LIMIT = -1, -5
 HD = 1920 * 1080
-
-
-class In(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in ("flags", "kernel", "count", "fast_chunk", "spp", "pass_spp")] + \
-               [("n_pixels", ctypes.c_longlong), ("ray_depth", ctypes.c_int), ("n_nodes", ctypes.c_int),
-                ("spec_blocks", ctypes.c_longlong), ("variant_blocks", ctypes.c_longlong)]
-
-
-class Out(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in ("err", "lane", "v_count", "v_fast", "v_lsplit", "v_spec", "v_chain")] + \
-               [("sched", ctypes.c_ulonglong)] + \
-               [(n, ctypes.c_int) for n in ("handoff", "ordered", "cs", "chunks")] + \
-               [("n_items", ctypes.c_longlong), ("round_min", ctypes.c_int), ("stats_spp", ctypes.c_int)] + \
-               [(n, ctypes.c_longlong) for n in ("blocks", "slots", "groups", "per", "blocks2", "waves2", "dealt", "per2")] + \
-               [("spread2", ctypes.c_int), ("msg", ctypes.c_char * 192)]
 
 
 @pytest.fixture(scope="module")
@@ -217,3 +204,54 @@ def test_limits_just_inside(ph):
     # 2^32 / (256 * 15 * 32) = 34952.5 blocks
     assert ph(n_pixels=40000 * 256, ray_depth=15, variant_blocks=34952).err == 0
     assert ph(n_pixels=40000 * 256, ray_depth=15, variant_blocks=34953).err == ERR_LIMIT
+
+
+# ---------------------------------------------------------------- the variant table
+# rt_launch_plan.h kVariants, in its order: (count, fast, lsplit, spec, chain, mom)
+VARIANTS = [(1, 1, 0, 0, 0, 0), (0, 0, 0, 1, 1, 0), (0, 0, 0, 1, 0, 0), (0, 1, 0, 0, 0, 0), (1, 0, 1, 0, 0, 0), (0, 0, 1, 0, 0, 0),
+            (0, 0, 0, 0, 0, 0), (1, 0, 0, 0, 0, 0), (0, 0, 0, 0, 1, 0), (0, 1, 0, 0, 1, 0), (0, 1, 0, 0, 1, 1)]
+
+
+def sweep():
+    """What rt_render* and rt_accum_* admit, on both sides of the runahead boundary."""
+    for n_pixels in (1024 * 512, 1024 * 513):
+        for flags in (0, F_FAST, F_LSPLIT, F_NO_RUNAHEAD):
+            for count in (0, 1):
+                yield dict(n_pixels=n_pixels, spp=8, flags=flags, count=count)
+        for flags in (0, F_NO_RUNAHEAD):
+            for subset_items in (0, 100):
+                yield dict(n_pixels=n_pixels, spp=8, pass_spp=4, flags=flags, subset_items=subset_items)
+                for moments in (0, 1):
+                    yield dict(n_pixels=n_pixels, spp=8, pass_spp=4, flags=flags, subset_items=subset_items, fast_accum=1,
+                               fast_chunk=2, fast_units=2, moments=moments)
+
+
+def test_every_admitted_plan_has_a_kernel_and_every_kernel_a_plan(ph):
+    reached, n = set(), 0
+    for kw in sweep():
+        o = ph(**kw)
+        assert o.err == 0 and o.lane == 1 and o.variant_index >= 0, kw
+        assert VARIANTS[o.variant_index] == (o.v_count, o.v_fast, o.v_lsplit, o.v_spec, o.v_chain, o.v_mom), kw
+        reached.add(o.variant_index)
+        n += 1
+    assert n == 40 and reached == set(range(11))
+
+
+def test_mom_only_on_a_fast_accumulators_pass_that_asks(ph):
+    for fast_accum in (0, 1):
+        for pass_spp in (0, 4):
+            for moments in (0, 1):
+                for flags in (0, F_FAST):
+                    o = ph(spp=8, pass_spp=pass_spp, flags=flags, fast_accum=fast_accum, fast_chunk=2, fast_units=2, moments=moments)
+                    assert o.err == 0 and o.v_mom == int(fast_accum and pass_spp > 0 and moments)
+
+
+def test_mode_words_of_the_launch_and_the_relaunch(ph):
+    pack = ph.lib.ph_mode_pack
+    o = ph(HD)   # the headline frame: the plain kernel parks below 56, the relaunch deals 100%
+    assert o.handoff == 1 and o.mode == pack(56, 0) and o.mode2 == pack(0, 100)
+    o = ph(HD // 8)   # an 8-way shard: the runahead kernel, no hand-off
+    assert (o.v_spec, o.handoff, o.mode, o.mode2) == (1, 0, 0, 0)
+    o = ph(spp=9, pass_spp=1, fast_chunk=3, fast_accum=1, fast_units=3)   # a fast pass: the units per item
+    assert (o.v_fast, o.v_chain, o.mode, o.mode2) == (1, 1, 3, 0)
+

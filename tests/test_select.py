@@ -18,7 +18,8 @@ import pytest
 
 import rtref
 from test_accum import _header, _load, _records
-from test_launch_plan import In as PlanIn, Out as PlanOut, PLAIN_BLOCKS, SPEC_BLOCKS, HD, SRC as PLAN_SRC
+from plan_util import PlanIn, PlanOut
+from test_launch_plan import PLAIN_BLOCKS, SPEC_BLOCKS, HD, SRC as PLAN_SRC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "select_host.cpp")
@@ -35,14 +36,7 @@ class Rule(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("target", "x0", "y0", "x1", "y1")] + [("threshold", ctypes.c_float)]
 
 
-class SubsetIn(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in ("flags", "kernel", "count", "fast_chunk", "spp", "pass_spp")] + \
-               [("n_pixels", ctypes.c_longlong), ("ray_depth", ctypes.c_int), ("n_nodes", ctypes.c_int),
-                ("spec_blocks", ctypes.c_longlong), ("variant_blocks", ctypes.c_longlong), ("subset_items", ctypes.c_longlong)]
-
-
-class SubsetOut(ctypes.Structure):
-    _fields_ = [f for f in PlanOut._fields_ if f[0] != "msg"]
+SubsetIn, SubsetOut = PlanIn, PlanOut   # (one pair of structures for every plan shim: plan_util.py)
 
 
 @pytest.fixture(scope="module")
