@@ -1,14 +1,10 @@
 // rt_accum_file.h — an accumulator's checkpoint file (rt_accum_save / rt_accum_load), host only.
 //
 // The file: AccumHeader, then n_pixels records of 8 words in the chain buffer's layout, then (a
-// moments file) n_pixels moment records of 8 words.  Little-endian, as the devices and their
-// hosts are.  The magic (rt_accum_plan.h kKinds, version 1 each) says which kind it holds:
-//   parity   records (pixel, next sample, engine state | cache flag << 31, cached value | sum x,
-//            y, z, 0);
-//   fast     the chunk size in pad[0], fast records (pixel, next sample, total x, y | total z,
-//            open x, y, z) verbatim;
-//   moments  the fast file's header and records, then the moment records (total2 x, y, z,
-//            open2 x | open2 y, z, 0, 0) verbatim.
+// moments file) n_pixels moment records of 8 words, all verbatim (rt_records.h: parity, fast and
+// moment records).  Little-endian, as the devices and their hosts are.  The magic
+// (rt_accum_plan.h kKinds, version 1 each) says which kind it holds; a fast kind's chunk size is
+// in pad[0].
 // write() is the writer; read() checks a file whole against the scene and rebuilds what the fold
 // kernels report for its records, before any device call (tests/test_accum_plan.py).
 #pragma once
@@ -20,7 +16,7 @@
 #include <vector>
 
 #include "rt_accum_plan.h"
-#include "rt_moments.h"
+#include "rt_records.h"
 
 namespace rtaf {
 
@@ -77,15 +73,6 @@ struct File {
     std::vector<float> sums, moments;   // n_pixels x 3: the records' reported sums (and moments), as the fold kernels write them
     int fast_c() const { return rtap::info(kind).fast ? (int)h.pad[0] : 0; }
 };
-
-// The reported value of a fast or moment record (rt_fast_units.h): `total` and `open` words.
-inline void reported_of(uint32_t next, const uint32_t *total, const uint32_t *open, int c, float *out) {
-    rtfu::Rec r;
-    r.next = (int)next;
-    std::memcpy(r.total, total, 12);
-    std::memcpy(r.open, open, 12);
-    rtfu::reported(r, c, out);
-}
 
 // Reads `path` and checks it whole; `who` opens every message.  In this order: the file and its
 // header, the header against the scene, the header's shard fields, `shard` (if given: the
@@ -151,20 +138,27 @@ inline File read(const char *path, const SceneFacts &scene, const std::string &w
     f.sums.resize((size_t)h.n_pixels * 3);
     if (moments) f.moments.resize((size_t)h.n_pixels * 3);
     for (long long k = 0; k < h.n_pixels; ++k) {
-        const uint32_t *rec = &f.rec[8 * k], nx = rec[1];
-        if (rec[0] != (uint32_t)k || (h.reserved ? nx > (uint32_t)h.samples : nx != (uint32_t)h.samples))
+        const uint32_t *rec = &f.rec[rtrec::kWords * k], nx = rec[rtrec::kNext];
+        const uint32_t *mom = moments ? &f.mom[rtrec::kWords * k] : nullptr;
+        if (rec[rtrec::kPixel] != (uint32_t)k || (h.reserved ? nx > (uint32_t)h.samples : nx != (uint32_t)h.samples))
             f.refused = {RT_ERR_FORMAT, who + ": record " + std::to_string(k) + " does not belong to this file"};
-        else if (fast && !rtfu::open_words_fit(nx, c, rec + 5))
+        else if (fast && !rtrec::open_words_fit(nx, c, rec))
             f.refused = {RT_ERR_FORMAT, who + ": record " + std::to_string(k) + " holds an open partial at a chunk boundary"};
-        else if (moments && !rtmo::record_words_fit(nx, c, &f.mom[8 * k]))
+        else if (moments && !rtrec::record_words_fit(nx, c, mom))
             f.refused = {RT_ERR_FORMAT, who + ": moment record " + std::to_string(k) +
                                             " holds an open partial or pad words at a chunk boundary"};
         if (f.refused) return f;
-        lo =std::min(lo, nx);
+        lo = std::min(lo, nx);
         hi = std::max(hi, nx);
-        if (fast) reported_of(nx, rec + 2, rec + 5, c, &f.sums[3 * k]);
-        else std::memcpy(&f.sums[3 * k], rec + 4, 12);
-        if (moments) reported_of(nx, &f.mom[8 * k], &f.mom[8 * k + 3], c, &f.moments[3 * k]);
+        // the reported values (rt_fast_units.h reported; a parity record's sum as it is)
+        if (fast) rtfu::reported(rtrec::fast_unpack(rec).r, c, &f.sums[3 * k]);
+        else std::memcpy(&f.sums[3 * k], rtrec::parity_unpack(rec).sum, 12);
+        if (moments) {
+            rtfu::Rec m;
+            m.next = (int)nx;
+            rtrec::moment_unpack(mom, m);
+            rtfu::reported(m, c, &f.moments[3 * k]);
+        }
     }
     f.lo = (int)lo;
     f.hi = (int)hi;

@@ -1,9 +1,10 @@
-// rt_denoise_device.h — the device half of the feature buffer and the frame denoiser: the kernels
-// and their launch functions.  Included by rt_device.hip in the middle of the file (after the
-// scene, grow, HIP_TRY and rt_variance_kernel, which it uses), so the build stays one translation
-// unit.  The per-pixel text is rt_gbuffer.h, rt_denoise.h and rt_denoise_guided.h; the entries of
-// include/rt_hw.h that call the launch functions, the accumulator's frames and the per-device
-// scratch cache stay in rt_device.hip.
+// rt_denoise_device.h — the device half of the feature buffer and the frame denoiser: the kernels,
+// their launch functions, the per-device scratch cache and the entries of include/rt_hw.h that
+// call them (rt_gbuffer*, rt_denoise_*, rt_variance_from_moments_device).  Included by
+// rt_device.hip after the scene, grow, HIP_TRY, shard_of, ensure_device_scene and the tonemap
+// entries, which it uses, so the build stays one translation unit.  The per-pixel text is
+// rt_gbuffer.h, rt_denoise.h and rt_denoise_guided.h; the accumulator's frames are
+// rt_accum_device.h's.
 
 // rt_gbuffer* (include/rt_hw.h, rt_gbuffer.h): one lane per shard pixel, in the shape of
 // rt_rays_kernel; the pixel-centre ray, its closest hit and the hit's attributes, written as four
@@ -206,7 +207,7 @@ int gbuffer_launch(rt_device_scene *d, const ShardGeom &g, float4 *d_out, hipStr
 }
 
 // What the two modes' launch functions share.  `ws` / `ws_bytes`: the scratch of the call's owner
-// (an accumulator, or the device's cache in rt_device.hip), grown on first use; 64 B per pixel: the
+// (an accumulator, or the device's cache g_dn_ws below), grown on first use; 64 B per pixel: the
 // two (L, kind) buffers, (N, t) and (P, 0); 72 B in the guided mode, with its two variance buffers.
 struct DnFrame {
     const float *sums;
@@ -289,6 +290,24 @@ int denoise_guided_launch(void **ws, size_t *ws_bytes, const float *d_sums, cons
     return f.resolve(f.a[cur], f.v[cur], d_out, d_out_var);
 }
 
+}  // namespace
+
+// The measured variance (rt_moments.h variance_of_pixel): one thread per pixel, consecutive lanes
+// on consecutive pixels; counts or, when null, `spp` for every pixel.
+__global__ void __launch_bounds__(256) rt_variance_kernel(const float *__restrict__ sums, const float *__restrict__ moments,
+                                                           const int32_t *__restrict__ counts, int spp, long long n,
+                                                           const float4 *__restrict__ g, float *__restrict__ out) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const float4 g1 = g[rtd::kGbufferQuads * p + 1];
+    const float S[3] = {sums[3 * p], sums[3 * p + 1], sums[3 * p + 2]};
+    const float Q[3] = {moments[3 * p], moments[3 * p + 1], moments[3 * p + 2]};
+    const float al[3] = {g1.x, g1.y, g1.z};
+    out[p] = rtmo::variance_of_mean(counts ? counts[p] : spp, S, Q, al, __float_as_int(g1.w) >= 0);
+}
+
+namespace {
+
 // rt_variance_kernel on the current device.
 int variance_launch(const float *d_sums, const float *d_moments, const int32_t *d_counts, int spp, long long n, const float *d_g,
                     float *d_out, hipStream_t stream) {
@@ -299,4 +318,146 @@ int variance_launch(const float *d_sums, const float *d_moments, const int32_t *
     return RT_OK;
 }
 
+// rt_denoise_device's and rt_denoise_guided_device's scratch, per device, from the first call on
+// (only grows).
+std::mutex g_dn_mu;
+void *g_dn_ws[kRtMaxDevices] = {};
+size_t g_dn_ws_bytes[kRtMaxDevices] = {};
+
+// rt_denoise_frame_u8 / rt_denoise_guided_frame_u8: host arrays to `device`, filtered there by
+// launch(d_sums, d_counts, d_gbuffer, d_variance, d_mean) under the device cache's lock, finished
+// at spp = 1, the bytes copied back.  variance may be NULL.
+template <class Launch>
+int denoise_frame_bytes(const std::string &who, const float *sums, const int32_t *counts, int32_t width, int32_t height,
+                        const float *gbuffer, const float *variance, int32_t device, uint8_t *out_rgb, Launch launch) {
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev || device >= kRtMaxDevices)
+        return rt_fail(RT_ERR_DEVICE, "no HIP device " + std::to_string(device));
+    DeviceGuard guard(device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    // one staging allocation: sums, mean, G-buffer, counts, variance, bytes (each part 256-byte aligned)
+    const size_t n = (size_t)width * height;
+    const size_t o_mean = rtp::align_up(n * 12), o_g = o_mean + rtp::align_up(n * 12), o_cnt = o_g + n * 64,
+                 o_var = o_cnt + rtp::align_up(n * 4), o_rgb = o_var + (variance ? rtp::align_up(n * 4) : 0), total = o_rgb + n * 3;
+    uint8_t *buf = nullptr;
+    HIP_TRY(hipMalloc((void **)&buf, total));
+    int32_t *d_counts = counts ? (int32_t *)(buf + o_cnt) : nullptr;
+    float *d_var = variance ? (float *)(buf + o_var) : nullptr;
+    hipError_t e = hipMemcpy(buf, sums, n * 12, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + o_g, gbuffer, n * 64, hipMemcpyHostToDevice);
+    if (e == hipSuccess && counts) e = hipMemcpy(d_counts, counts, n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && variance) e = hipMemcpy(d_var, variance, n * 4, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? RT_OK : rt_fail(RT_ERR_DEVICE, who + " copy: " + hipGetErrorString(e));
+    if (rc == RT_OK) {
+        std::lock_guard<std::mutex> lock(g_dn_mu);
+        rc = launch((const float *)buf, (const int32_t *)d_counts, (const float *)(buf + o_g), (const float *)d_var,
+                    (float *)(buf + o_mean));
+    }
+    if (rc == RT_OK) rc = rt_tonemap_u8_device((const float *)(buf + o_mean), width, height, 1, buf + o_rgb, nullptr);
+    if (rc == RT_OK) {
+        e = hipMemcpy(out_rgb, buf + o_rgb, n * 3, hipMemcpyDeviceToHost);   // (waits for the default stream)
+        if (e != hipSuccess) rc = rt_fail(RT_ERR_DEVICE, who + " copy: " + hipGetErrorString(e));
+    }
+    (void)hipFree(buf);
+    return rc;
+}
+
 }  // namespace
+
+extern "C" {
+
+int rt_gbuffer_device(rt_scene *s, const rt_params *p, float *d_out, void *stream) {
+    if (!s || !p || !d_out) return rt_fail(RT_ERR_ARG, "rt_gbuffer_device: NULL argument");
+    Shard sh;
+    if (int rc = shard_of(s, p, "rt_gbuffer_device", sh)) return rc;
+    if (p->device < 0 || p->device >= kRtMaxDevices || !s->dev[p->device])
+        return rt_fail(RT_ERR_ARG, "rt_gbuffer_device: scene not uploaded to device " + std::to_string(p->device));
+    rt_device_scene *d = s->dev[p->device];
+    DeviceGuard guard(d->device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    return gbuffer_launch(d, sh.g, (float4 *)d_out, (hipStream_t)stream);
+}
+
+int rt_gbuffer(rt_scene *s, const rt_params *p, float *out) {
+    if (!s || !p || !out) return rt_fail(RT_ERR_ARG, "rt_gbuffer: NULL argument");
+    Shard sh;
+    if (int rc = shard_of(s, p, "rt_gbuffer", sh)) return rc;
+    if (int rc = ensure_device_scene(s, p->device)) return rc;
+    rt_device_scene *d = s->dev[p->device];
+    DeviceGuard guard(d->device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    const size_t bytes = (size_t)sh.n_pixels * RT_GBUFFER_WORDS * sizeof(float);
+    float4 *d_out = nullptr;
+    HIP_TRY(hipMalloc((void **)&d_out, bytes ? bytes : 64));
+    int rc = gbuffer_launch(d, sh.g, d_out, nullptr);
+    if (rc == RT_OK && bytes) {
+        const hipError_t e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = rt_fail(RT_ERR_DEVICE, std::string("rt_gbuffer copy: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(d_out);
+    return rc;
+}
+
+int rt_denoise_device(const float *d_sums, const int32_t *d_counts, int32_t spp, int32_t width, int32_t height,
+                      const float *d_gbuffer, const rt_denoise_params *params, float *d_out_mean, void *stream) {
+    rtdn::Params dp;
+    if (int rc = rt_denoise_check("rt_denoise_device", d_sums, d_counts, spp, width, height, d_gbuffer, params, d_out_mean, &dp))
+        return rc;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= kRtMaxDevices) return rt_fail(RT_ERR_DEVICE, "rt_denoise_device: device id");
+    std::lock_guard<std::mutex> lock(g_dn_mu);
+    return denoise_launch(&g_dn_ws[dev], &g_dn_ws_bytes[dev], d_sums, d_counts, spp, width, height, d_gbuffer, dp, d_out_mean,
+                          (hipStream_t)stream);
+}
+
+int rt_denoise_frame_u8(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height, const float *gbuffer,
+                        const rt_denoise_params *params, int32_t device, uint8_t *out_rgb) {
+    if (!out_rgb) return rt_fail(RT_ERR_ARG, "rt_denoise_frame_u8: NULL argument");
+    rtdn::Params dp;
+    if (int rc = rt_denoise_check("rt_denoise_frame_u8", sums, counts, spp, width, height, gbuffer, params, sums, &dp)) return rc;
+    return denoise_frame_bytes("rt_denoise_frame_u8", sums, counts, width, height, gbuffer, nullptr, device, out_rgb,
+                               [&](const float *d_sums, const int32_t *d_counts, const float *d_g, const float *, float *d_mean) {
+                                   return denoise_launch(&g_dn_ws[device], &g_dn_ws_bytes[device], d_sums, d_counts, spp, width, height,
+                                                         d_g, dp, d_mean, nullptr);
+                               });
+}
+
+int rt_denoise_guided_device(const float *d_sums, const int32_t *d_counts, int32_t spp, int32_t width, int32_t height,
+                             const float *d_gbuffer, const float *d_variance, const rt_denoise_guided_params *params,
+                             float *d_out_mean, float *d_out_variance, void *stream) {
+    rtdg::Params dp;
+    if (int rc = rt_denoise_guided_check("rt_denoise_guided_device", d_sums, d_counts, spp, width, height, d_gbuffer, params,
+                                         d_out_mean, &dp))
+        return rc;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= kRtMaxDevices) return rt_fail(RT_ERR_DEVICE, "rt_denoise_guided_device: device id");
+    std::lock_guard<std::mutex> lock(g_dn_mu);
+    return denoise_guided_launch(&g_dn_ws[dev], &g_dn_ws_bytes[dev], d_sums, d_counts, spp, width, height, d_gbuffer, d_variance, dp,
+                                 d_out_mean, d_out_variance, (hipStream_t)stream);
+}
+
+int rt_denoise_guided_frame_u8(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
+                               const float *gbuffer, const float *variance, const rt_denoise_guided_params *params, int32_t device,
+                               uint8_t *out_rgb) {
+    if (!out_rgb) return rt_fail(RT_ERR_ARG, "rt_denoise_guided_frame_u8: NULL argument");
+    rtdg::Params dp;
+    if (int rc = rt_denoise_guided_check("rt_denoise_guided_frame_u8", sums, counts, spp, width, height, gbuffer, params, sums, &dp))
+        return rc;
+    return denoise_frame_bytes("rt_denoise_guided_frame_u8", sums, counts, width, height, gbuffer, variance, device, out_rgb,
+                               [&](const float *d_sums, const int32_t *d_counts, const float *d_g, const float *d_var, float *d_mean) {
+                                   return denoise_guided_launch(&g_dn_ws[device], &g_dn_ws_bytes[device], d_sums, d_counts, spp, width,
+                                                                height, d_g, d_var, dp, d_mean, nullptr, nullptr);
+                               });
+}
+
+int rt_variance_from_moments_device(const float *d_sums, const float *d_moments, const int32_t *d_counts, int32_t spp,
+                                    int32_t width, int32_t height, const float *d_gbuffer, float *d_out, void *stream) {
+    if (int rc = rt_variance_check("rt_variance_from_moments_device", d_sums, d_moments, d_counts, spp, width, height, d_gbuffer, d_out))
+        return rc;
+    return variance_launch(d_sums, d_moments, d_counts, spp, (long long)width * height, d_gbuffer, d_out, (hipStream_t)stream);
+}
+
+}  // extern "C"

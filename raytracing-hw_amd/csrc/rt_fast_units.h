@@ -44,7 +44,7 @@ RT_HD Range unit_range(int next, int target, int c, int k) {
 // Unit k of that pass starts from the record's `open` (else from +0.f).
 RT_HD bool unit_continues(int next, int c, int k) { return k == 0 && next % c != 0; }
 
-// The record's arithmetic part (the device keeps it as rt_mega.h FastRec words).
+// The record's arithmetic part (its words: rt_records.h).
 struct Rec {
     int next;
     float total[3], open[3];
@@ -77,7 +77,8 @@ RT_HD void reported(const Rec &r, int c, float *out) {
     for (int ch = 0; ch < 3; ++ch) out[ch] = r.next % c == 0 ? r.total[ch] : r.total[ch] + r.open[ch];
 }
 
-// Checkpoint check: the record's `open` words are zero where no chunk is open.
+// Checkpoint check: the record's `open` words are zero where no chunk is open (rt_records.h
+// open_words_fit finds them in a whole record).
 RT_HD bool open_words_fit(uint32_t next, int c, const uint32_t *open_words) {
     return next % (uint32_t)c != 0u || (open_words[0] | open_words[1] | open_words[2]) == 0u;
 }

@@ -16,7 +16,7 @@
 // RNG, pixel sum, sample counter and depth budget live in registers; the vertex records go
 // to memory (LaneRec, indexed by lane slot).  Same per-pixel arithmetic, so bit-identical output.
 #pragma once
-#include "rt_fast_units.h"
+#include "rt_records.h"
 #include "rt_wavefront.h"
 #if !defined(__HIPCC__)
 #include <algorithm>   // (host emulation of wave_order)
@@ -120,13 +120,10 @@ __device__ __forceinline__ void lane_sum_set(ML &L, V3 v) { L.sum = v; }
 // The lane's RNG state (minstd word, normal cache) lives in LDS between its uses (sample
 // start, shading), 2 KB per block, instead of three VGPRs held through the traversal.  The
 // minstd word is below 2^31 (modulus 2^31 - 1), so the cache flag (0 or 1) rides in its top
-// bit (rt_device_selfcheck 1 checks the round trip): the kilobyte saved, with the computed
-// linear texel decode's, pays for a twelfth LDS stack frame.
-__device__ __forceinline__ uint32_t rng_word_pack(uint32_t x, uint32_t saved_avail) { return x | saved_avail << 31; }
-__device__ __forceinline__ void rng_word_unpack(uint32_t w, uint32_t &x, uint32_t &saved_avail) {
-    x = w & 0x7fffffffu;
-    saved_avail = w >> 31;
-}
+// bit (rt_records.h rng_word_pack, a parity record's engine word): the kilobyte saved, with the
+// computed linear texel decode's, pays for a twelfth LDS stack frame.
+using rtrec::rng_word_pack;
+using rtrec::rng_word_unpack;
 #if defined(__HIPCC__)
 __shared__ uint32_t mega_lds_rng[2 * 256];
 template <class ML>
@@ -201,15 +198,18 @@ struct Parked {
     Rng x;
     V3 sum;
 };
+// Record k of a buffer of 32-byte records (rt_records.h), as two 16-byte loads or stores.
+__device__ __forceinline__ rtrec::Words record_load(const uint4 *buf, long long k) {
+    const uint4 a = buf[2 * k], b = buf[2 * k + 1];
+    return rtrec::Words{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
+}
+__device__ __forceinline__ void record_store(uint4 *buf, long long k, const rtrec::Words &r) {
+    buf[2 * k] = make_uint4(r.w[0], r.w[1], r.w[2], r.w[3]);
+    buf[2 * k + 1] = make_uint4(r.w[4], r.w[5], r.w[6], r.w[7]);
+}
 __device__ __forceinline__ Parked parked(const uint4 *park, long long k) {
-    const uint4 a = park[2 * k], b = park[2 * k + 1];
-    Parked q;
-    q.pix = a.x;
-    q.s = a.y;
-    rng_word_unpack(a.z, q.x.x, q.x.saved_avail);
-    q.x.saved = __uint_as_float(a.w);
-    q.sum = V3{__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z)};
-    return q;
+    const rtrec::Parity q = rtrec::parity_unpack(record_load(park, k).w);
+    return Parked{q.pix, q.next, Rng{q.state, q.cached_avail, q.cached}, V3{q.sum[0], q.sum[1], q.sum[2]}};
 }
 
 // The RNG state shard pixel p's sample 0 starts from: minstd_rand seeded with the pixel
@@ -271,20 +271,20 @@ __device__ __forceinline__ void mega_assign_fast(ML &L, const DevScene &sc, cons
 // (one atomic per wave: every lane that parks in the same pass of the wave), and resumed by
 // the runahead kernel from exactly that state: its remaining samples run in order from it and
 // add to that sum, so the bits do not change.
-// The park list: 2 x uint4 per lane slot of the parking launch (pixel, next sample, packed RNG
-// word, normal cache | sum, 0); a slot nobody parked in holds pixel 0xffffffff (the host fills
-// it so before the launch).  Indexed by slot, not by an atomic count: no ballot or atomic in
+// The park list: one parity record (rt_records.h) per lane slot of the parking launch; a slot
+// nobody parked in holds pixel 0xffffffff (the host fills it so before the launch).  Indexed by slot, not by an atomic count: no ballot or atomic in
 // the shading code (that cost the plain kernel 28 more spilled VGPRs).
 constexpr uint32_t kNoPark = 0xffffffffu;
 __device__ __forceinline__ void park_pixel(uint4 *park, long long slot, int pix, int s, const Rng &r, V3 sum) {
-    park[2 * slot] = make_uint4((uint32_t)pix, (uint32_t)s, rng_word_pack(r.x, r.saved_avail), __float_as_uint(r.saved));
-    park[2 * slot + 1] = make_uint4(__float_as_uint(sum.x), __float_as_uint(sum.y), __float_as_uint(sum.z), 0u);
+    rtrec::Words rec;
+    rtrec::parity_pack(rtrec::Parity{(uint32_t)pix, (uint32_t)s, r.x, r.saved_avail, r.saved, {sum.x, sum.y, sum.z}}, rec.w);
+    record_store(park, slot, rec);
 }
 
 // ---------------------------------------------------------------- chain buffer (accumulator)
 // rt_accum_* (include/rt_hw.h): a shard's per-pixel chain state kept between renders, one
-// Parked record per shard pixel, indexed by the pixel: (pixel, next sample, start state of that
-// sample, sum of the samples before it).  A pass to absolute sample `spp` is the usual
+// parity record (rt_records.h) per shard pixel, indexed by the pixel: (pixel, next sample, start
+// state of that sample, sum of the samples before it).  A pass to absolute sample `spp` is the usual
 // schedule, except that a pixel starts from its record instead of its seed (mega_assign_chain,
 // spec_convert_chain) and that the lane adding the pixel's sample spp - 1 stores the record
 // back, with the state that sample ended in (the three pixel-done sites: mega_shade,
@@ -344,48 +344,28 @@ __device__ __forceinline__ void mega_assign_chain(ML &L, const DevScene &sc, con
     mega_sample<COUNT>(L, sc, g, root, cnt);
 }
 // ---------------------------------------------------------------- fast accumulator
-// rt_accum_create_fast (include/rt_hw.h, rt_fast_units.h): the chain buffer's 32-byte record of
-// a fast accumulator holds (pixel, next sample, total x, y | total z, open x, y, z): no RNG
-// state, sample s of a pixel draws from its own Philox stream.  Word 1 is the next sample as in
-// a parity record, so the selection, mark and counts kernels read both kinds.  The render
-// kernel only reads records; rt_fast_fold_chain_kernel (rt_device.hip) writes them.
-struct FastRec {
-    uint32_t pix;
-    rtfu::Rec r;
-};
+// rt_accum_create_fast (include/rt_hw.h, rt_fast_units.h): the chain buffer of a fast
+// accumulator holds fast records (rt_records.h): no RNG state, sample s of a pixel draws from its
+// own Philox stream.  The render kernel only reads records; rt_fast_fold_chain_kernel
+// (rt_device.hip) writes them.
+using FastRec = rtrec::Fast;
 __device__ __forceinline__ FastRec fast_rec(const uint4 *chain, long long p) {
-    const uint4 a = chain[2 * p], b = chain[2 * p + 1];
-    FastRec q;
-    q.pix = a.x;
-    q.r.next = (int)a.y;
-    q.r.total[0] = __uint_as_float(a.z);
-    q.r.total[1] = __uint_as_float(a.w);
-    q.r.total[2] = __uint_as_float(b.x);
-    q.r.open[0] = __uint_as_float(b.y);
-    q.r.open[1] = __uint_as_float(b.z);
-    q.r.open[2] = __uint_as_float(b.w);
-    return q;
+    return rtrec::fast_unpack(record_load(chain, p).w);
 }
-// A moments accumulator's second record per pixel, in a buffer of its own (rt_moments.h): 32 bytes,
-// (total2 x, y, z, open2 x | open2 y, z, 0, 0); its `next` is the fast record's.
+// A moments accumulator's second record per pixel, in a buffer of its own (rt_moments.h,
+// rt_records.h); its `next` is the fast record's.
 __device__ __forceinline__ void moment_rec(const uint4 *mom, long long p, rtfu::Rec &r) {
-    const uint4 a = mom[2 * p], b = mom[2 * p + 1];
-    r.total[0] = __uint_as_float(a.x);
-    r.total[1] = __uint_as_float(a.y);
-    r.total[2] = __uint_as_float(a.z);
-    r.open[0] = __uint_as_float(a.w);
-    r.open[1] = __uint_as_float(b.x);
-    r.open[2] = __uint_as_float(b.y);
+    rtrec::moment_unpack(record_load(mom, p).w, r);
 }
 __device__ __forceinline__ void moment_rec_store(uint4 *mom, long long p, const rtfu::Rec &r) {
-    mom[2 * p] = make_uint4(__float_as_uint(r.total[0]), __float_as_uint(r.total[1]), __float_as_uint(r.total[2]),
-                            __float_as_uint(r.open[0]));
-    mom[2 * p + 1] = make_uint4(__float_as_uint(r.open[1]), __float_as_uint(r.open[2]), 0u, 0u);
+    rtrec::Words rec;
+    rtrec::moment_pack(r, rec.w);
+    record_store(mom, p, rec);
 }
 __device__ __forceinline__ void fast_rec_store(uint4 *chain, long long p, const rtfu::Rec &r) {
-    chain[2 * p] = make_uint4((uint32_t)p, (uint32_t)r.next, __float_as_uint(r.total[0]), __float_as_uint(r.total[1]));
-    chain[2 * p + 1] = make_uint4(__float_as_uint(r.total[2]), __float_as_uint(r.open[0]), __float_as_uint(r.open[1]),
-                                  __float_as_uint(r.open[2]));
+    rtrec::Words rec;
+    rtrec::fast_pack(FastRec{(uint32_t)p, r}, rec.w);
+    record_store(chain, p, rec);
 }
 // A pass of a fast accumulator: queue item q = k * n_list + i is unit k of the list's item i
 // (unit-major, like mega_assign_fast: neighbouring lanes take neighbouring pixels), the pixel

@@ -9,8 +9,8 @@
 // second rtfu::Rec, folded by rtfu::fold and reported by rtfu::reported: there is no second fold.
 // Non-finite samples give non-finite moments; nothing is clamped here.
 //
-// From (n, S, Q) two estimates are defined, shared by the device kernels (rt_device.hip
-// rt_variance_kernel, rt_select_kernel's variance form), the host entry
+// From (n, S, Q) two estimates are defined, shared by the device kernels (rt_denoise_device.h
+// rt_variance_kernel, rt_accum_device.h rt_select_kernel's variance form), the host entry
 // (rt_variance_from_moments) and the CPU test (tests/native/moments_host.cpp).  All arithmetic is
 // f32 in the order written; every translation unit that includes this file is built with
 // -ffp-contract=off, and the device build with correctly rounded divide and sqrt, so host and
@@ -25,7 +25,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "rt_fast_units.h"
+#include "rt_records.h"
 #include "rt_select.h"
 
 namespace rtmo {
@@ -91,10 +91,7 @@ RT_HD float variance_of_pixel(int n, const float *S, const float *Q, const float
     return variance_of_mean(n, S, Q, grecord + 4, (int32_t)rtm::f2u(grecord[7]) >= 0);
 }
 
-// Checkpoint check of a moment record (total2 xyz, open2 xyz, 0, 0): the open and pad words are
-// zero where no chunk is open.
-RT_HD bool record_words_fit(uint32_t next, int c, const uint32_t *words) {
-    return next % (uint32_t)c != 0u || (words[3] | words[4] | words[5] | words[6] | words[7]) == 0u;
-}
+// Checkpoint check of a moment record: its open and pad words are zero where no chunk is open.
+using rtrec::record_words_fit;   // (the words and their names: rt_records.h)
 
 }  // namespace rtmo

@@ -691,26 +691,6 @@ struct PathRec {
     __device__ __forceinline__ float get_alpha(int k) const { return alpha[k]; }
 };
 
-// The same records kept structure-of-arrays in HBM for the wavefront pipeline:
-// plane (q * D + k) holds component q of vertex k for every path slot.
-struct SoARec {
-    float *base;
-    long long n;   // slots
-    long long i;   // this slot
-    int D;         // vertex capacity
-    __device__ __forceinline__ float &at(int q, int k) const { return base[((long long)(q * D + k)) * n + i]; }
-    __device__ __forceinline__ void set_e(int k, V3 v) const { at(0, k) = v.x; at(1, k) = v.y; at(2, k) = v.z; }
-    __device__ __forceinline__ void set_brdf(int k, V3 mm, float c, float cs, float a) const {
-        at(3, k) = mm.x; at(4, k) = mm.y; at(5, k) = mm.z;
-        at(6, k) = c; at(7, k) = cs; at(8, k) = a;
-    }
-    __device__ __forceinline__ V3 get_e(int k) const { return V3{at(0, k), at(1, k), at(2, k)}; }
-    __device__ __forceinline__ V3 get_m(int k) const { return V3{at(3, k), at(4, k), at(5, k)}; }
-    __device__ __forceinline__ float get_coeff(int k) const { return at(6, k); }
-    __device__ __forceinline__ float get_cos(int k) const { return at(7, k); }
-    __device__ __forceinline__ float get_alpha(int k) const { return at(8, k); }
-};
-
 // SceneDistribution::sample (random.cpp:194-208): mixture of cosine, VNDF and light
 // sampling chosen by one uniform(-1, 1) draw.
 // The mixture draw (random.cpp:196-203): 0 cosine, 1 VNDF, 2 light.

@@ -2,7 +2,7 @@
 //
 // rt_accum_select (include/rt_hw.h) chooses, per shard pixel, whether the next subset pass
 // renders it up to the absolute sample `target`.  The rule takes plain values, so the device
-// kernel (rt_device.hip rt_select_kernel) and the CPU test (tests/native/select_host.cpp) share
+// kernel (rt_accum_device.h rt_select_kernel) and the CPU test (tests/native/select_host.cpp) share
 // this one text.  All arithmetic is f32 in the order written; every translation unit that
 // includes it is built with -ffp-contract=off, and the device build with correctly rounded
 // divide and sqrt, so host and device agree bit for bit.

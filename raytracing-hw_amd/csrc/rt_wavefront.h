@@ -741,7 +741,7 @@ __device__ __forceinline__ void quad_min_step(float &c, float &cu, float &cv, in
 // round_min: unserved leaf lanes that start another round of the same step (> 64: one
 // round per step).  A wave mostly at leaves (a scene of a few dozen triangles, whose tree
 // is a few levels deep) otherwise serves kCoopLeaves of its leaf lanes per step and idles
-// the rest (rt_device.hip kCoopRoundMin*).
+// the rest (rt_mega_device.h, rt_launch_plan.h kCoopRoundMin*).
 struct NoHook {
     __device__ __forceinline__ void operator()() const {}
 };

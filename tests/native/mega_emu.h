@@ -1,4 +1,4 @@
-// mega_emu.h — TEST ONLY: the one host emulation of rt_mega_kernel's wave loop (rt_device.hip),
+// mega_emu.h — TEST ONLY: the one host emulation of rt_mega_kernel's wave loop (rt_mega_device.h),
 // over the kernel's own per-lane source (raytracing-hw_amd/csrc/rt_mega.h) compiled for the
 // host.  kernel_host.cpp (the one-shot renders) and accum_host.cpp (the accumulator's passes)
 // are entry points over it; the schedule rules it shares with the kernel and the launch plan
@@ -142,7 +142,7 @@ int render_mega(const rt_scene_view *v, int spp, int rank, int world, int row_bl
     st.mid = mid.data();
     const rtd::NodeRec root = rtd::load_node(rtd::mega_nodes(sc), 0);
     const rtd::GlobalNodes nodes{sc.node};
-    // lane state as in rt_device.hip: TravState for the runahead kernel, TravStateU otherwise
+    // lane state as in rt_mega_device.h: TravState for the runahead kernel, TravStateU otherwise
     using Lane = std::conditional_t<SPEC, rtd::MegaLane, rtd::MegaLaneU>;
     std::vector<Lane> lanes((size_t)waves * 64);
     std::vector<std::vector<uint2>> stacks((size_t)waves * 64, std::vector<uint2>(rtd::kStack));

@@ -377,8 +377,8 @@ def test_runahead_with_spare_lanes(rt, kh, per_wave):
     ("cornell_blob", 40, 40, 8, 8, 8, 56, 100), ("practice6_1", 40, 30, 6, 5, 2, 40, 50)])
 def test_handoff_matches_per_pixel(rt, kh, name, w, h, s, waves, spec_waves, below, pct, spread):
     """Hand-off (rt_device.hip RT_HANDOFF): the plain lane-resident kernel parks the pixels of
-    its sparse tail waves at a sample boundary (rt_mega.h park_pixel: pixel, next sample, RNG
-    state, sum so far, by lane slot), and the runahead kernel resumes them (static allotment of
+    its sparse tail waves at a sample boundary (rt_mega.h park_pixel: a parity record of
+    rt_records.h, by lane slot), and the runahead kernel resumes them (static allotment of
     `pct` percent, the rest claimed in the tail), in park-list slot order or (`spread`,
     RT_HANDOFF_SPREAD) through the map that deals the pixels with the most work left one per
     wave.  Same bits as the per-pixel schedule, and pixels were parked."""
