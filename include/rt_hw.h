@@ -182,6 +182,35 @@ int rt_scene_from_view(const rt_scene_view *view, rt_scene **out);
 int rt_scene_get_view(const rt_scene *scene, rt_scene_view *view);
 void rt_scene_free(rt_scene *scene);
 
+/* --- movable camera (additive in ABI 6) ---------------------------------------------------- */
+/* The camera is not part of the scene's device image: the kernels take it by value with every
+ * launch.  rt_scene_set_camera replaces the scene's camera on the host and in the launch
+ * arguments of every device the scene is uploaded to; it uploads nothing and launches nothing, and
+ * works on a scene that is on no device.  rt_scene_get_view reports the new values, cam_fov as
+ * 2 * atanf(tan_half_fov) (nothing on the render path reads cam_fov: the kernels take the tangents).
+ * A NULL argument, a non-finite word or a tangent that is not > 0: RT_ERR_ARG.  The call falls
+ * under "one render per (scene, device) in flight": not while a render or a pass of the scene is.
+ * After rt_scene_set_camera(C) every entry (rt_render*, rt_render_frame, rt_gbuffer*,
+ * rt_intersect_rays, both kernels, fast mode, the counters) behaves bit for bit as on a scene built
+ * by rt_scene_from_view from the same arrays with camera C.
+ *
+ * Accumulators: the scene counts its camera changes (the camera epoch), and an accumulator
+ * remembers the epoch it was created, loaded or reset at.  On an accumulator whose epoch is not
+ * the scene's (a stale one) the read-outs still work and give the old view's result:
+ * rt_accum_sums, rt_accum_device_sums, rt_accum_counts*, rt_accum_moments,
+ * rt_accum_device_moments, rt_accum_state, rt_accum_samples, rt_accum_sample_range (and
+ * rt_accum_fast_chunk, rt_accum_has_moments).  Every other entry (one that renders, selects, marks,
+ * reads the cached G-buffer or writes a file: a checkpoint's header holds the camera, and would
+ * pair the old sums with the new one) fails with RT_ERR_ARG, a message that names rt_accum_reset,
+ * and nothing launched.  rt_accum_reset returns the accumulator to the state rt_accum_create* left
+ * it in (records, sums, moment buffers, samples done = 0), drops the marks, the pending selection
+ * and the cached G-buffer and adopts the scene's epoch; kind, chunk size, partition, flags and
+ * buffers are kept.  After it the accumulator is, bit for bit, a new one on the scene as it now
+ * stands.  It works on an accumulator that is not stale too; it waits for the reset kernel. */
+typedef struct { float pos[3]; float axes[9]; float tan_half_fov[2]; } rt_camera;  /* axes: right, up, forward, as rt_scene_view */
+int rt_scene_get_camera(const rt_scene *scene, rt_camera *out);
+int rt_scene_set_camera(rt_scene *scene, const rt_camera *cam);
+
 /* --- render ----------------------------------------------------------------------- */
 /* Copies the scene to `device` (once per device; later calls reuse it).  One render per
  * (scene, device) may be in flight at a time; different devices render independently. */
@@ -261,6 +290,9 @@ int rt_accum_state(rt_accum *accum, uint32_t *out);
 int rt_accum_save(rt_accum *accum, const char *path);
 int rt_accum_load(rt_scene *scene, int32_t device, const char *path, rt_accum **out);
 void rt_accum_free(rt_accum *accum);
+/* Back to the state after rt_accum_create*, on the scene's camera as it now stands ("movable
+ * camera" above); on `stream`, and it waits. */
+int rt_accum_reset(rt_accum *accum, void *stream);
 
 /* --- per-pixel sample counts: subset passes and adaptive refinement (additive in ABI 6) --- */
 /* Every pixel's record carries its own next sample, so a pass may render a subset of the shard:
@@ -657,6 +689,112 @@ int rt_variance_from_moments_device(const float *d_sums, const float *d_moments,
 int rt_accum_variance(rt_accum *accum, float *out);
 int rt_accum_frame_u8_guided_measured(rt_accum *accum, const rt_denoise_guided_params *params, uint8_t *out_rgb);
 int rt_accum_select_variance(rt_accum *accum, const rt_select *select, void *stream, int64_t *n_selected);
+
+/* --- reprojected temporal history (additive in ABI 6) ---------------------------------------
+ * The temporal half of SVGF (Schied et al. 2017) in front of the filters above: a frame's
+ * demodulated radiance is blended with the previous frame's result at the pixel where the same
+ * surface point was seen, found through the world position P of the first-hit record and the
+ * previous camera.  A pure function of its inputs.  csrc/rt_temporal.h is its text, shared by the
+ * device kernel and the host function; the arithmetic rules are rt_denoise's (f32 +, -, *, /,
+ * comparisons and selects in the order written, nothing contracted, correctly rounded division).
+ * A still camera gains nothing this way: parity frames of one view are identical, and progressive
+ * passes (rt_accum_*) are the tool for a still view.  The history is for motion.
+ *
+ * Parameters.  A NULL params is all defaults.  alpha, alpha_moments: <= 0 takes 0.2, > 1 is
+ * RT_ERR_ARG.  sigma_plane: <= 0 takes 0.02.  normal_min: <= 0 takes 0.9.  max_history: <= 0 takes
+ * 65536, more than 2^20 is RT_ERR_ARG.  A NaN or infinite float parameter is RT_ERR_ARG.  The
+ * thresholds are picked, not measured: 0.2, 0.02 and 0.9, a hard plane test, and the bilinear
+ * footprint without SVGF's 3 x 3 fallback.
+ *
+ * A history is three planes of W * H 16-byte quads, plane-major (RT_HISTORY_WORDS words per
+ * pixel): plane 0 (L.xyz, N), plane 1 (M1.xyz, 0), plane 2 (M2.xyz, 0).  L is the temporally
+ * integrated demodulated radiance, N the history length in frames (a float), M1 and M2 the
+ * integrated per-channel first and second moments of L.  sums, counts / spp, width, height and
+ * gbuffer are rt_denoise's inputs for the new frame; cam_prev, gbuffer_prev and history_prev are
+ * the previous frame's camera, records and history_out.  With history_prev NULL (a first frame)
+ * cam_prev and gbuffer_prev may be NULL; with it given they may not.  out_mean (W * H * 3) and
+ * out_variance (W * H) may each be NULL.  history_out must not be history_prev.
+ *
+ * The rule, per pixel p = (i, j) with record (Np, tp, albedo, E, Pp, mesh):
+ * 0. Prepare: rt_denoise's m, a', L and kind.
+ * 1. Kind pass: the history record is zero words, out_mean = m, out_variance = 0; done.
+ * 2. Look-up ("no history" when history_prev is NULL).  R, U, F: the three axes of cam_prev.
+ *      v = Pp - pos per component;  z = (v.x * F.x + v.y * F.y) + v.z * F.z;  no history unless z > 0
+ *      cx = ((v.x * R.x + v.y * R.y) + v.z * R.z) / z;  cy likewise with U
+ *      fx = ((cx / tan_x + 1.f) * 0.5f) * (float)W - 0.5f      (the inverse of the camera ray)
+ *      fy = ((1.f - cy / tan_y) * 0.5f) * (float)H - 0.5f
+ *    no history unless fx > -1 && fx < (float)W && fy > -1 && fy < (float)H (a NaN fails; the test
+ *    comes before any conversion to int).  x0 = (int)fx, less 1 when (float)x0 > fx;
+ *    wx = fx - (float)x0; the same for y.  Four taps, dy = 0, 1 outer, dx = 0, 1 inner, at
+ *    q = (x0 + dx, y0 + dy) with b = (dx ? wx : 1.f - wx) * (dy ? wy : 1.f - wy).  A tap is used iff
+ *    q is inside the frame; b > 0; history_prev[q].N > 0; the mesh id of gbuffer_prev[q] is >= 0 and
+ *    equals p's; (Np.x * Nq.x + Np.y * Nq.y) + Np.z * Nq.z >= normal_min; and |pd| <= sigma_plane * tp
+ *    with pd the numerator of rt_denoise's plane term for Pq - Pp.  From +0:
+ *      sb += b;  sL += b * Lq;  sN += b * Nq;  sM1 += b * M1q;  sM2 += b * M2q
+ *    There is history iff sb > 0 and all ten quotients by sb (Lh, Nh, M1h, M2h) are finite.
+ * 3. Integrate, with rN = 1.f / N', a = alpha > rN ? alpha : rN, am likewise from alpha_moments:
+ *      valid, history:     N' = min(Nh + 1.f, (float)max_history);  L' = Lh + a * (L - Lh);
+ *                          M1' = M1h + am * (L - M1h);  M2' = M2h + am * (L * L - M2h); a non-finite
+ *                          result in any of the nine sends the pixel to the next line
+ *      valid, no history:  N' = 1;  L' = M1' = L;  M2' = L * L
+ *      fill, history:      N' = Nh, and L', M1', M2' are the history's
+ *      fill, no history:   the record is zero words (N' = 0)
+ * 4. The history record is written as laid out above.  out_mean = L' * a' + E per channel
+ *    (rt_denoise's resolve: an unfilled fill pixel gives E).  out_variance, for N' >= 2: per channel
+ *    vc = M2' - M1' * M1', taken as 0 unless > 0; V = ((v0 + v1) + v2) * a, taken as 0 when not
+ *    finite; 0 otherwise.  That is the variance of the integrated mean were the frames independent,
+ *    summed over the channels: the form rt_denoise_guided's `variance` input takes.  out_mean goes
+ *    to the denoisers as sums at spp = 1.
+ * Known limits: a freshly disoccluded pixel reports V = 0 (one frame measures no variance), and
+ * the weighting is by frames, not by sample counts.
+ *
+ * rt_temporal runs on the host; rt_temporal_device on the current HIP device, asynchronously on
+ * `stream`, every pointer but cam_prev and params a device pointer (16-byte aligned histories and
+ * records), with the host function's bits and no scratch.  Refusals as rt_denoise's, with
+ * history_out in out_mean's place.
+ *
+ * rt_history is the object callers use: two histories and two G-buffers on one device for a scene's
+ * W x H (the scene must be uploaded there).  rt_history_push renders the scene's G-buffer at its
+ * current camera into the current slot, runs the step against the previous slot and the previous
+ * camera, swaps the slots and remembers the camera; the first push, and the first after
+ * rt_history_reset, has no history.  Asynchronous on `stream`; it uses none of the scene's
+ * workspace, and a refused call leaves nothing half made.  rt_history_gbuffer_device: the records
+ * of the last push's view (NULL before one), for rt_denoise*_device without rendering them twice.
+ * rt_history_lengths: N per pixel (W * H floats) to host memory; waits; zeros before a push.  Free
+ * a history before its scene.
+ * rt_history_push_frame_u8 is the push for a caller that holds host arrays and no HIP (the CLI), as
+ * rt_denoise_frame_u8 is for the filter: sums and counts (or NULL and spp) are copied to the
+ * history's device and pushed; the integrated mean, at spp = 1 and with the push's records, passes
+ * through rt_denoise_device (dparams given), rt_denoise_guided_device with the step's out_variance
+ * as its variance (gparams given; DESIGN.md 5.18 has the measurement behind that choice) or neither
+ * (both NULL; both given is RT_ERR_ARG), and is finished to W * H * 3 bytes; it waits. */
+#define RT_HISTORY_WORDS 12
+typedef struct {
+    float alpha;           /* <= 0: 0.2.  least weight of the new frame's colour                */
+    float alpha_moments;   /* <= 0: 0.2.  the same for the moments                              */
+    float sigma_plane;     /* <= 0: 0.02. plane test, fraction of the centre's hit distance     */
+    float normal_min;      /* <= 0: 0.9.  least dot product of the two shading normals          */
+    int32_t max_history;   /* <= 0: 65536. cap of the history length                            */
+} rt_temporal_params;
+int rt_temporal(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
+                const float *gbuffer, const rt_camera *cam_prev, const float *gbuffer_prev,
+                const float *history_prev, const rt_temporal_params *params,
+                float *history_out, float *out_mean, float *out_variance);
+int rt_temporal_device(const float *d_sums, const int32_t *d_counts, int32_t spp, int32_t width, int32_t height,
+                       const float *d_gbuffer, const rt_camera *cam_prev, const float *d_gbuffer_prev,
+                       const float *d_history_prev, const rt_temporal_params *params,
+                       float *d_history_out, float *d_out_mean, float *d_out_variance, void *stream);
+typedef struct rt_history rt_history;
+int rt_history_create(rt_scene *scene, int32_t device, rt_history **out);
+int rt_history_push(rt_history *h, const float *d_sums, const int32_t *d_counts, int32_t spp,
+                    const rt_temporal_params *params, float *d_out_mean, float *d_out_variance, void *stream);
+int rt_history_push_frame_u8(rt_history *h, const float *sums, const int32_t *counts, int32_t spp,
+                             const rt_temporal_params *tparams, const rt_denoise_params *dparams,
+                             const rt_denoise_guided_params *gparams, uint8_t *out_rgb);
+const float *rt_history_gbuffer_device(rt_history *h);
+int rt_history_lengths(rt_history *h, float *out);
+int rt_history_reset(rt_history *h);
+void rt_history_free(rt_history *h);
 
 /* --- misc --------------------------------------------------------------------------- */
 const char *rt_last_error(void);

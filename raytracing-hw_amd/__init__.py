@@ -92,6 +92,39 @@ def denoise_guided_params(iterations=-1, sigma_var=0.0, sigma_plane=0.0, normal_
     return RtDenoiseGuidedParams(int(iterations), float(sigma_var), float(sigma_plane), int(normal_power_log2), float(firefly))
 
 
+class RtCamera(ctypes.Structure):
+    """include/rt_hw.h rt_camera: position, the axes right, up, forward, the half-angle tangents."""
+    _fields_ = [("pos", ctypes.c_float * 3), ("axes", ctypes.c_float * 9), ("tan_half_fov", ctypes.c_float * 2)]
+
+
+def make_camera(pos, axes, tan_half_fov):
+    c = RtCamera()
+    c.pos[:] = [float(x) for x in np.asarray(pos, np.float32).reshape(3)]
+    c.axes[:] = [float(x) for x in np.asarray(axes, np.float32).reshape(9)]
+    c.tan_half_fov[:] = [float(x) for x in np.asarray(tan_half_fov, np.float32).reshape(2)]
+    return c
+
+
+def _camera_arg(cam):
+    """A camera dict (Scene.camera()), an RtCamera or None as the rt_camera the library reads."""
+    if cam is None or isinstance(cam, RtCamera):
+        return cam
+    return make_camera(cam["pos"], cam["axes"], cam["tan_half_fov"])
+
+
+HISTORY_WORDS = 12       # RT_HISTORY_WORDS: 32-bit words of a pixel's temporal history (three planes of quads)
+
+
+class RtTemporalParams(ctypes.Structure):
+    """include/rt_hw.h rt_temporal_params; every field <= 0 takes its default."""
+    _fields_ = [("alpha", ctypes.c_float), ("alpha_moments", ctypes.c_float), ("sigma_plane", ctypes.c_float),
+                ("normal_min", ctypes.c_float), ("max_history", ctypes.c_int32)]
+
+
+def temporal_params(alpha=0.0, alpha_moments=0.0, sigma_plane=0.0, normal_min=0.0, max_history=0):
+    return RtTemporalParams(float(alpha), float(alpha_moments), float(sigma_plane), float(normal_min), int(max_history))
+
+
 class RtStats(ctypes.Structure):
     _fields_ = [("pixels", ctypes.c_uint64), ("samples", ctypes.c_uint64), ("rays", ctypes.c_uint64),
                 ("aabb_tests", ctypes.c_uint64), ("tri_tests", ctypes.c_uint64), ("light_queries", ctypes.c_uint64),
@@ -112,6 +145,8 @@ ABI = {
     "rt_scene_from_view": (ctypes.c_int, [ctypes.POINTER(RtSceneView), ctypes.POINTER(ctypes.c_void_p)]),
     "rt_scene_get_view": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtSceneView)]),
     "rt_scene_free": (None, [ctypes.c_void_p]),
+    "rt_scene_get_camera": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtCamera)]),
+    "rt_scene_set_camera": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtCamera)]),
     "rt_scene_upload": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "rt_shard_rows": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_i]),
     "rt_render": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtParams), _c_f, ctypes.POINTER(RtStats)]),
@@ -143,6 +178,7 @@ ABI = {
     "rt_accum_save": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "rt_accum_load": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]),
     "rt_accum_free": (None, [ctypes.c_void_p]),
+    "rt_accum_reset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     # per-pixel sample counts: subset passes and adaptive refinement
     "rt_accum_mark": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "rt_accum_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtSelect), ctypes.c_void_p,
@@ -190,6 +226,22 @@ ABI = {
     "rt_accum_frame_u8_guided_measured": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtDenoiseGuidedParams), _c_b]),
     "rt_accum_select_variance": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RtSelect), ctypes.c_void_p,
                                                 ctypes.POINTER(ctypes.c_int64)]),
+    # reprojected temporal history
+    "rt_temporal": (ctypes.c_int, [_c_f, _c_i, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_f, ctypes.POINTER(RtCamera), _c_f,
+                                   _c_f, ctypes.POINTER(RtTemporalParams), _c_f, _c_f, _c_f]),
+    "rt_temporal_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                          ctypes.c_void_p, ctypes.POINTER(RtCamera), ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.POINTER(RtTemporalParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p]),
+    "rt_history_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
+    "rt_history_push": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                       ctypes.POINTER(RtTemporalParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rt_history_push_frame_u8": (ctypes.c_int, [ctypes.c_void_p, _c_f, _c_i, ctypes.c_int32, ctypes.POINTER(RtTemporalParams),
+                                                ctypes.POINTER(RtDenoiseParams), ctypes.POINTER(RtDenoiseGuidedParams), _c_b]),
+    "rt_history_gbuffer_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "rt_history_lengths": (ctypes.c_int, [ctypes.c_void_p, _c_f]),
+    "rt_history_reset": (ctypes.c_int, [ctypes.c_void_p]),
+    "rt_history_free": (None, [ctypes.c_void_p]),
 }
 
 _lib_handle = None
@@ -338,6 +390,30 @@ class Scene:
     @property
     def handle(self):
         return self._h
+
+    def camera(self):
+        """rt_scene_get_camera: {"pos": (3,), "axes": (3, 3) rows right, up, forward, "tan_half_fov": (2,)}."""
+        c = RtCamera()
+        _check(lib().rt_scene_get_camera(self._h, ctypes.byref(c)))
+        return {"pos": np.array(c.pos[:], np.float32), "axes": np.array(c.axes[:], np.float32).reshape(3, 3),
+                "tan_half_fov": np.array(c.tan_half_fov[:], np.float32)}
+
+    def set_camera(self, pos=None, axes=None, tan_half_fov=None):
+        """rt_scene_set_camera: look from somewhere else without uploading anything (an omitted part
+        is kept).  Not while a render or a pass of the scene is in flight; an accumulator of the
+        scene then needs reset() before it renders on."""
+        cur = self.camera()
+        c = make_camera(cur["pos"] if pos is None else pos, cur["axes"] if axes is None else axes,
+                        cur["tan_half_fov"] if tan_half_fov is None else tan_half_fov)
+        _check(lib().rt_scene_set_camera(self._h, ctypes.byref(c)))
+
+    def history(self, device=0):
+        """rt_history_create: a reprojected temporal history of this scene's frame on `device`
+        (uploaded here if need be)."""
+        self.upload(device)
+        h = ctypes.c_void_p()
+        _check(lib().rt_history_create(self._h, device, ctypes.byref(h)))
+        return History(self, h.value)
 
     def upload(self, device=0):
         _check(lib().rt_scene_upload(self._h, device))
@@ -598,6 +674,12 @@ class Accumulator:
     def save(self, path):
         _check(lib().rt_accum_save(self._h, os.fsencode(path)))
 
+    def reset(self, stream_ptr=None):
+        """rt_accum_reset: back to the state after creation, on the scene's camera as it now stands
+        (what an accumulator needs after Scene.set_camera before it renders on)."""
+        _check(lib().rt_accum_reset(self._h, ctypes.c_void_p(stream_ptr or 0)))
+        self._n_selected = 0
+
     # --- per-pixel sample counts (include/rt_hw.h rt_accum_select and friends)
     def mark(self, stream_ptr=None):
         """rt_accum_mark: remember the sums and counts as they stand (the selection rule's
@@ -664,6 +746,81 @@ class Accumulator:
         h = getattr(self, "_h", None)
         if h is not None and h.value and _lib_handle is not None:
             _lib_handle.rt_accum_free(h)
+        self._h = None
+
+    def __del__(self):
+        self.free()
+
+
+class History:
+    """A reprojected temporal history (include/rt_hw.h rt_history): push() renders the scene's
+    G-buffer at its current camera and blends the frame's sums with the previous push's result."""
+
+    def __init__(self, scene, handle):
+        self._scene = scene   # (kept alive: the history is freed before its scene)
+        self._h = ctypes.c_void_p(handle)
+
+    def push(self, d_sums_ptr, d_counts_ptr, spp, d_out_ptr, d_var_ptr=0, stream_ptr=None, **params):
+        """rt_history_push: device pointers (d_counts_ptr 0 / None: one spp; d_out_ptr, d_var_ptr 0 /
+        None: not wanted), asynchronous on the stream.  params: temporal_params' arguments."""
+        tp = temporal_params(**params)
+        _check(lib().rt_history_push(self._h, ctypes.c_void_p(d_sums_ptr), ctypes.c_void_p(d_counts_ptr or 0), int(spp),
+                                     ctypes.byref(tp), ctypes.c_void_p(d_out_ptr or 0), ctypes.c_void_p(d_var_ptr or 0),
+                                     ctypes.c_void_p(stream_ptr or 0)))
+
+    def push_accumulator(self, acc, d_out_ptr, d_var_ptr=0, stream_ptr=None, d_counts_ptr=0, **params):
+        """push() of a whole-frame accumulator's device sums and counts.  While every pixel holds one
+        sample count that count is the spp; after subset passes d_counts_ptr must name a device
+        buffer of H * W int32, which receives the count map (rt_accum_counts_device) on the stream."""
+        lo, hi = acc.sample_range
+        if acc.world != 1:
+            raise ValueError("push_accumulator needs a whole-frame accumulator (world = 1)")
+        if lo != hi and not d_counts_ptr:
+            raise ValueError("the pixels hold different sample counts: pass d_counts_ptr, a device buffer for the count map")
+        if lo != hi:
+            _check(lib().rt_accum_counts_device(acc._h, ctypes.c_void_p(d_counts_ptr), ctypes.c_void_p(stream_ptr or 0)))
+        self.push(acc.device_sums_ptr, d_counts_ptr if lo != hi else 0, hi, d_out_ptr, d_var_ptr, stream_ptr, **params)
+
+    def push_frame_u8(self, sums, counts_or_spp, denoise=None, guided=False, **params):
+        """rt_history_push_frame_u8: host sums in, the pushed frame's (H, W, 3) bytes out (waits).
+        denoise: True or a dict of the filter's parameters runs rt_denoise_device on the integrated
+        mean, with guided=True the guided mode with the step's variance.  params: temporal_params'."""
+        sums = np.ascontiguousarray(sums, np.float32)
+        h, w = self._scene.height, self._scene.width
+        if sums.size != h * w * 3:
+            raise ValueError("sums must be the scene's (H, W, 3) frame")
+        counts, spp = None, 0
+        if np.ndim(counts_or_spp) == 0:
+            spp = int(counts_or_spp)
+        else:
+            counts = np.ascontiguousarray(counts_or_spp, np.int32)
+        tp = temporal_params(**params)
+        kw = denoise if isinstance(denoise, dict) else {}
+        dp = denoise_params(**kw) if denoise and not guided else None
+        gp = denoise_guided_params(**kw) if denoise and guided else None
+        rgb = np.zeros((h, w, 3), np.uint8)
+        _check(lib().rt_history_push_frame_u8(self._h, sums.ctypes.data_as(_c_f), counts.ctypes.data_as(_c_i) if counts is not None else None,
+                                              spp, ctypes.byref(tp), ctypes.byref(dp) if dp is not None else None,
+                                              ctypes.byref(gp) if gp is not None else None, rgb.ctypes.data_as(_c_b)))
+        return rgb
+
+    def lengths(self):
+        """(H, W) float32: every pixel's history length in frames (waits)."""
+        out = np.zeros((self._scene.height, self._scene.width), np.float32)
+        _check(lib().rt_history_lengths(self._h, out.ctypes.data_as(_c_f)))
+        return out
+
+    def gbuffer_ptr(self):
+        """The device records of the last push's view (0 before one), for denoise*_device."""
+        return int(lib().rt_history_gbuffer_device(self._h) or 0)
+
+    def reset(self):
+        _check(lib().rt_history_reset(self._h))
+
+    def free(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib_handle is not None:
+            _lib_handle.rt_history_free(h)
         self._h = None
 
     def __del__(self):
@@ -799,6 +956,45 @@ def denoise_device(d_sums_ptr, d_counts_ptr, spp, width, height, d_gbuffer_ptr, 
     _check(lib().rt_denoise_device(ctypes.c_void_p(d_sums_ptr), ctypes.c_void_p(d_counts_ptr or 0), int(spp), width, height,
                                    ctypes.c_void_p(d_gbuffer_ptr), ctypes.byref(dp), ctypes.c_void_p(d_out_ptr),
                                    ctypes.c_void_p(stream_ptr or 0)))
+
+
+def temporal(sums, counts_or_spp, gbuffer, cam_prev=None, gbuffer_prev=None, history_prev=None, **params):
+    """rt_temporal (the host function): one step of the reprojected temporal history.  cam_prev (a
+    Scene.camera() dict or RtCamera), gbuffer_prev and history_prev ((3, H, W, 4) float32) describe
+    the previous frame; all None: a first frame.  Returns (history (3, H, W, 4), mean (H, W, 3),
+    variance (H, W)).  params: temporal_params' arguments."""
+    sums, counts, spp, rec = _denoise_inputs(sums, counts_or_spp, gbuffer)
+    h, w = sums.shape[0], sums.shape[1]
+    cam = _camera_arg(cam_prev)
+    gp = hp = None
+    if gbuffer_prev is not None:
+        gp = gbuffer_pack(gbuffer_prev)
+        if gp.size != h * w * GBUFFER_WORDS:
+            raise ValueError("gbuffer_prev must have one record per pixel")
+    if history_prev is not None:
+        hp = np.ascontiguousarray(history_prev, np.float32)
+        if hp.size != h * w * HISTORY_WORDS:
+            raise ValueError("history_prev must have three planes of one quad per pixel")
+    hist, mean, var = np.zeros((3, h, w, 4), np.float32), np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
+    tp = temporal_params(**params)
+    _check(lib().rt_temporal(sums.ctypes.data_as(_c_f), counts.ctypes.data_as(_c_i) if counts is not None else None, spp, w, h,
+                             rec.ctypes.data_as(_c_f), ctypes.byref(cam) if cam is not None else None,
+                             gp.ctypes.data_as(_c_f) if gp is not None else None, hp.ctypes.data_as(_c_f) if hp is not None else None,
+                             ctypes.byref(tp), hist.ctypes.data_as(_c_f), mean.ctypes.data_as(_c_f), var.ctypes.data_as(_c_f)))
+    return hist, mean, var
+
+
+def temporal_device(d_sums_ptr, d_counts_ptr, spp, width, height, d_gbuffer_ptr, d_history_out_ptr, d_out_ptr=0, d_var_ptr=0,
+                    cam_prev=None, d_gbuffer_prev_ptr=0, d_history_prev_ptr=0, stream_ptr=None, **params):
+    """rt_temporal_device: the same step on the current HIP device (device pointers; 0 / None: not
+    given), asynchronous on the stream."""
+    cam = _camera_arg(cam_prev)
+    tp = temporal_params(**params)
+    V = ctypes.c_void_p
+    _check(lib().rt_temporal_device(V(d_sums_ptr), V(d_counts_ptr or 0), int(spp), width, height, V(d_gbuffer_ptr),
+                                    ctypes.byref(cam) if cam is not None else None, V(d_gbuffer_prev_ptr or 0),
+                                    V(d_history_prev_ptr or 0), ctypes.byref(tp), V(d_history_out_ptr), V(d_out_ptr or 0),
+                                    V(d_var_ptr or 0), V(stream_ptr or 0)))
 
 
 def variance_from_moments(sums, moments, counts_or_spp, gbuffer):

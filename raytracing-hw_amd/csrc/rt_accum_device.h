@@ -10,6 +10,7 @@
 // file in rt_accum_file.h.
 struct rt_accum : rtap::State {
     rt_scene *scene = nullptr;
+    uint32_t epoch = 0;       // the scene's camera epoch its samples were rendered at (create, load, reset)
     rt_params p{};            // rank, world, row_block, device, flags (normalised)
     long long n_pixels = 0;
     int rows = 0;
@@ -214,7 +215,7 @@ int accum_new(rt_scene *s, const rt_params *p, const char *who, rt_accum **out, 
     Shard sh;
     if (int rc = shard_of(s, p, who, sh)) return rc;
     rt_accum *a = new rt_accum();
-    a->scene = s, a->kind = kind;
+    a->scene = s, a->kind = kind, a->epoch = s->cam_epoch;
     a->p = *p;
     a->p.spp = 0, a->p.world = sh.world, a->p.row_block = sh.row_block;
     a->rows = sh.rows, a->n_pixels = sh.n_pixels, a->geom = sh.g;
@@ -246,6 +247,24 @@ int accum_alloc(rt_accum *a) {
 int accum_wait(rt_accum *a) {
     HIP_TRY(hipStreamSynchronize(a->stream));
     return RT_OK;
+}
+
+// The scene's camera has moved since the accumulator's samples were rendered (rt_scene_set_camera):
+// only the read-outs of the old view still work; everything else asks for rt_accum_reset.
+int accum_stale(const rt_accum *a, const std::string &who) {
+    if (a->epoch == a->scene->cam_epoch) return RT_OK;
+    return rt_fail(RT_ERR_ARG, who + ": the scene's camera has changed since this accumulator's samples were rendered; "
+                                     "call rt_accum_reset (its sums, counts and moments still read out the old view)");
+}
+
+// Fresh records and zero sums on `stream` (create and reset; the current device is the accumulator's).
+void accum_init_launch(rt_accum *a, hipStream_t stream) {
+    const dim3 blocks((unsigned)((a->n_pixels + 255) / 256));
+    if (a->fast_c)
+        hipLaunchKernelGGL(rt_fast_chain_init_kernel, blocks, dim3(256), 0, stream, a->n_pixels, a->chain, a->sums);
+    else
+        hipLaunchKernelGGL(rt_chain_init_kernel, blocks, dim3(256), 0, stream, a->scene->dev[a->p.device]->ds, a->geom, a->chain,
+                           a->sums);
 }
 
 // A device buffer of an accumulator made on first use (the current device is the accumulator's).
@@ -299,12 +318,7 @@ int accum_create(rt_scene *s, const rt_params *p, rt_accum **out, const std::str
     int rc = accum_alloc(a);
     if (rc == RT_OK && a->n_pixels > 0) {
         DeviceGuard guard(a->p.device);
-        const dim3 blocks((unsigned)((a->n_pixels + 255) / 256));
-        if (a->fast_c)
-            hipLaunchKernelGGL(rt_fast_chain_init_kernel, blocks, dim3(256), 0, nullptr, a->n_pixels, a->chain, a->sums);
-        else
-            hipLaunchKernelGGL(rt_chain_init_kernel, blocks, dim3(256), 0, nullptr, s->dev[a->p.device]->ds, a->geom, a->chain,
-                               a->sums);
+        accum_init_launch(a, nullptr);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
         if (e != hipSuccess) rc = rt_fail(RT_ERR_DEVICE, who + ": " + hipGetErrorString(e));
@@ -377,6 +391,7 @@ const float *rt_accum_device_moments(rt_accum *a) { return a && a->has_moments()
 
 int rt_accum_add(rt_accum *a, int32_t n_samples, void *stream, rt_stats *st) {
     if (!a) return rt_fail(RT_ERR_ARG, "rt_accum_add: NULL accumulator");
+    if (int rc = accum_stale(a, "rt_accum_add")) return rc;
     const rtap::Pass ps = rtap::plan_add(*a, n_samples, a->n_pixels);
     if (ps.refused) return rt_fail(ps.refused.code, ps.refused.msg);
     if (int rc = accum_pass(a, ps, (hipStream_t)stream, st)) return rc;
@@ -386,6 +401,7 @@ int rt_accum_add(rt_accum *a, int32_t n_samples, void *stream, rt_stats *st) {
 
 int rt_accum_mark(rt_accum *a, void *stream) {
     if (!a) return rt_fail(RT_ERR_ARG, "rt_accum_mark: NULL accumulator");
+    if (int rc = accum_stale(a, "rt_accum_mark")) return rc;
     DeviceGuard guard(a->p.device);
     if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
     // (a pending selection stays: the mark changes no record, so the list is as safe as it was)
@@ -415,6 +431,7 @@ static int accum_select(rt_accum *a, const rt_select *sel, void *stream, int64_t
                                                          std::to_string(rule.x1) + ") x [" + std::to_string(rule.y0) + ", " +
                                                          std::to_string(rule.y1) + ")");
     if (!a) return rt_fail(RT_ERR_ARG, who + ": NULL accumulator");
+    if (int rc = accum_stale(a, who)) return rc;
     if (variance && !a->has_moments())
         return rt_fail(RT_ERR_ARG, who + ": the accumulator keeps no moments (rt_accum_create_fast_moments)");
     a->sel_pending = false;
@@ -471,12 +488,14 @@ int rt_accum_select_variance(rt_accum *a, const rt_select *sel, void *stream, in
 
 int rt_accum_selection(rt_accum *a, int32_t *out_pixels) {
     if (!a || !out_pixels) return rt_fail(RT_ERR_ARG, "rt_accum_selection: NULL argument");
+    if (int rc = accum_stale(a, "rt_accum_selection")) return rc;
     if (!a->sel_pending) return rt_fail(RT_ERR_ARG, "rt_accum_selection: no pending selection (rt_accum_select first)");
     return accum_read_back(a, &rt_accum::sel_list, (size_t)a->sel_n * sizeof(int32_t), out_pixels);
 }
 
 int rt_accum_add_selected(rt_accum *a, void *stream, rt_stats *st) {
     if (!a) return rt_fail(RT_ERR_ARG, "rt_accum_add_selected: NULL accumulator");
+    if (int rc = accum_stale(a, "rt_accum_add_selected")) return rc;
     const rtap::Pass ps = rtap::plan_add_selected(*a);
     if (ps.refused) return rt_fail(ps.refused.code, ps.refused.msg);
     if (!ps.launch) {   // nothing to raise
@@ -524,6 +543,7 @@ const float *rt_accum_device_sums(rt_accum *a) { return a ? a->sums : nullptr; }
 
 int rt_accum_frame_u8(rt_accum *a, uint8_t *out_rgb) {
     if (!a || !out_rgb) return rt_fail(RT_ERR_ARG, "rt_accum_frame_u8: NULL argument");
+    if (int rc = accum_stale(a, "rt_accum_frame_u8")) return rc;
     if (a->samples < 1) return rt_fail(RT_ERR_ARG, "rt_accum_frame_u8: no samples yet");
     if (a->n_pixels == 0) return RT_OK;
     return accum_read_back(a, &rt_accum::rgb, (size_t)a->n_pixels * 3, out_rgb, [&] {
@@ -572,6 +592,7 @@ static rtaf::SceneFacts accum_scene_facts(const rt_scene *s) {
 
 int rt_accum_save(rt_accum *a, const char *path) {
     if (!a || !path) return rt_fail(RT_ERR_ARG, "rt_accum_save: NULL argument");
+    if (int rc = accum_stale(a, "rt_accum_save")) return rc;   // (the header holds the camera: old sums, new camera)
     std::vector<uint32_t> rec, mom;
     if (int rc = accum_records(a, rec)) return rc;
     if (a->has_moments()) {
@@ -632,6 +653,33 @@ int rt_accum_load(rt_scene *s, int32_t device, const char *path, rt_accum **out)
 
 void rt_accum_free(rt_accum *a) { accum_release(a); }
 
+// Back to what accum_create left: fresh records, zero sums and moments, no samples, no mark, no
+// pending selection, no cached G-buffer; the scene's camera epoch adopted.  Kind, chunk size,
+// partition, flags and buffers stay.
+int rt_accum_reset(rt_accum *a, void *stream) {
+    if (!a) return rt_fail(RT_ERR_ARG, "rt_accum_reset: NULL accumulator");
+    if (!a->scene->dev[a->p.device]) return rt_fail(RT_ERR_ARG, "rt_accum_reset: scene not uploaded to device " + std::to_string(a->p.device));
+    DeviceGuard guard(a->p.device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    if (int rc = accum_wait(a)) return rc;   // (the last pass may be on another stream)
+    a->stream = (hipStream_t)stream;
+    if (a->n_pixels > 0) {
+        accum_init_launch(a, a->stream);
+        HIP_TRY(hipGetLastError());
+        if (a->has_moments()) {
+            HIP_TRY(hipMemsetAsync(a->mom, 0, (size_t)a->n_pixels * 32, a->stream));
+            HIP_TRY(hipMemsetAsync(a->moments, 0, (size_t)a->n_pixels * 3 * sizeof(float), a->stream));
+        }
+        if (int rc = accum_wait(a)) return rc;
+    }
+    const int fast_c = a->fast_c;
+    static_cast<rtap::State &>(*a) = rtap::State{};
+    a->fast_c = fast_c;
+    a->gbuf_ready = false;
+    a->epoch = a->scene->cam_epoch;
+    return RT_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -652,6 +700,7 @@ int accum_ensure_gbuffer(rt_accum *a) {
 template <class Check, class Launch>
 int accum_filtered_frame(rt_accum *a, const std::string &who, const char *frame_entry, uint8_t *out_rgb, Check check, Launch launch) {
     if (!a || !out_rgb) return rt_fail(RT_ERR_ARG, who + ": NULL argument");
+    if (int rc = accum_stale(a, who)) return rc;
     if (a->p.world != 1)
         return rt_fail(RT_ERR_ARG, who + ": the filter needs the whole frame (world = 1); gather the shards' "
                                          "sums and G-buffers and use " + frame_entry);
@@ -732,6 +781,7 @@ int rt_accum_frame_u8_guided_measured(rt_accum *a, const rt_denoise_guided_param
 
 int rt_accum_variance(rt_accum *a, float *out) {
     if (!a || !out) return rt_fail(RT_ERR_ARG, "rt_accum_variance: NULL argument");
+    if (int rc = accum_stale(a, "rt_accum_variance")) return rc;   // (it reads the cached G-buffer)
     if (!a->has_moments()) return rt_fail(RT_ERR_ARG, "rt_accum_variance: the accumulator keeps no moments (rt_accum_create_fast_moments)");
     if (a->n_pixels == 0) return RT_OK;
     return accum_read_back(a, &rt_accum::var, (size_t)a->n_pixels * sizeof(float), out, [&] { return accum_variance_launch(a); });

@@ -115,10 +115,13 @@ RT_HD float normal_term(const Geo &c, const Q &nq) {
     for (int i = 0; i < c.normal_power_log2; ++i) nd = nd * nd;
     return nd;
 }
-RT_HD float plane_term(const Geo &c, const Q &pq) {
+// The tap's signed distance from the centre's tangent plane (rt_temporal.h tests it against plane_den).
+RT_HD float plane_dist(const Geo &c, const Q &pq) {
     const float ex = pq.x - c.pp.x, ey = pq.y - c.pp.y, ez = pq.z - c.pp.z;
-    const float pd = (c.np.x * ex + c.np.y * ey) + c.np.z * ez;
-    const float pr = pd / c.plane_den;
+    return (c.np.x * ex + c.np.y * ey) + c.np.z * ez;
+}
+RT_HD float plane_term(const Geo &c, const Q &pq) {
+    const float pr = plane_dist(c, pq) / c.plane_den;
     return 1.f / (1.f + pr * pr);
 }
 // The colour term of tap q at a centre c of kind `kind`: 1 for a centre that is being filled.

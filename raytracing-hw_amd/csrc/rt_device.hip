@@ -67,6 +67,7 @@
 #include "rt_gbuffer.h"
 #include "rt_denoise.h"
 #include "rt_denoise_guided.h"
+#include "rt_temporal.h"
 
 using rtd::Counters;
 using rtd::DevScene;
@@ -1211,6 +1212,17 @@ void rt_device_scene_release(rt_scene *s) {
     s->blob = nullptr;
 }
 
+// rt_scene_set_camera's device half: the camera words of every copy's by-value DevScene (what
+// ensure_device_scene fills from the same fields); the next launch carries them.
+void rt_device_scene_set_camera(rt_scene *s) {
+    for (rt_device_scene *d : s->dev) {
+        if (!d) continue;
+        std::memcpy(d->ds.cam_pos, s->cam_pos, sizeof d->ds.cam_pos);
+        std::memcpy(d->ds.cam_axes, s->cam_axes, sizeof d->ds.cam_axes);
+        std::memcpy(d->ds.tan_fov, s->tan_half_fov, sizeof d->ds.tan_fov);
+    }
+}
+
 // Frame assembly on the root device of rt_render_frame (below).
 __global__ void __launch_bounds__(256) rt_rows_scatter_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
                                                               const int *__restrict__ frame_row_of, long long rows,
@@ -1292,6 +1304,7 @@ int rt_render(rt_scene *s, const rt_params *p, float *out, rt_stats *st) {
 // ------------------------------------------------------------------------ feature buffer, denoiser, accumulator
 #include "rt_denoise_device.h"   // the feature buffer and the denoiser: kernels, launch functions, entries
 #include "rt_accum_device.h"     // rt_accum_*: the accumulator's kernels, helpers and entries
+#include "rt_temporal_device.h"  // rt_temporal_device, rt_history_*: the temporal step's kernel and the history object
 
 // The whole frame as shards 0 .. n-1 of a (world n, row_block) split, shard r on device
 // devices[r] (include/rt_hw.h rt_render_frame).  rt_frame_plan.h defines the layout: which

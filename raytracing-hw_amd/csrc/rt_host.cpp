@@ -23,6 +23,7 @@
 #include "rt_moments.h"
 #include "rt_scene.h"
 #include "rt_select.h"
+#include "rt_temporal.h"
 #include "rt_vec.h"
 
 using rtv::V2;
@@ -826,6 +827,34 @@ void rt_scene_free(rt_scene *s) {
     delete s;
 }
 
+int rt_scene_get_camera(const rt_scene *s, rt_camera *out) {
+    if (!s || !out) return rt_fail(RT_ERR_ARG, "rt_scene_get_camera: NULL argument");
+    std::memcpy(out->pos, s->cam_pos, sizeof out->pos);
+    std::memcpy(out->axes, s->cam_axes, sizeof out->axes);
+    std::memcpy(out->tan_half_fov, s->tan_half_fov, sizeof out->tan_half_fov);
+    return RT_OK;
+}
+
+// The camera on the host and in every device copy's launch arguments (include/rt_hw.h, movable
+// camera): no upload, no launch.  cam_fov follows the tangents; nothing on the render path reads it.
+int rt_scene_set_camera(rt_scene *s, const rt_camera *cam) {
+    if (!s || !cam) return rt_fail(RT_ERR_ARG, "rt_scene_set_camera: NULL argument");
+    float w[14];   // pos, axes, tan_half_fov
+    static_assert(sizeof(rt_camera) == sizeof w, "rt_camera is 14 packed floats");
+    std::memcpy(w, cam, sizeof w);
+    for (int i = 0; i < 14; ++i)
+        if (!rtdn::finite(w[i])) return rt_fail(RT_ERR_ARG, "rt_scene_set_camera: non-finite camera word " + std::to_string(i));
+    if (!(cam->tan_half_fov[0] > 0.f) || !(cam->tan_half_fov[1] > 0.f))
+        return rt_fail(RT_ERR_ARG, "rt_scene_set_camera: tan_half_fov must be > 0");
+    std::memcpy(s->cam_pos, cam->pos, sizeof s->cam_pos);
+    std::memcpy(s->cam_axes, cam->axes, sizeof s->cam_axes);
+    std::memcpy(s->tan_half_fov, cam->tan_half_fov, sizeof s->tan_half_fov);
+    for (int i = 0; i < 2; ++i) s->cam_fov[i] = 2.f * std::atan(s->tan_half_fov[i]);
+    ++s->cam_epoch;
+    rt_device_scene_set_camera(s);
+    return RT_OK;
+}
+
 int64_t rt_shard_rows(int32_t height, int32_t rank, int32_t world, int32_t row_block, int32_t *rows_out) {
     return rt_shard_rows_impl(height, rank, world, row_block, rows_out);
 }
@@ -954,6 +983,40 @@ int rt_denoise_guided(const float *sums, const int32_t *counts, int32_t spp, int
     return RT_OK;
 }
 
+// The temporal step on the host (rt_temporal.h is its text; include/rt_hw.h its rule): per pixel,
+// against the previous frame's records and history.
+int rt_temporal(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height, const float *gbuffer,
+                const rt_camera *cam_prev, const float *gbuffer_prev, const float *history_prev, const rt_temporal_params *params,
+                float *history_out, float *out_mean, float *out_variance) {
+    rttm::Params tp;
+    if (int rc = rt_temporal_check("rt_temporal", sums, counts, spp, width, height, gbuffer, cam_prev, gbuffer_prev, history_prev,
+                                   params, history_out, &tp))
+        return rc;
+    const int64_t n = (int64_t)width * height;
+    // (the caller's arrays need not be 16-byte aligned)
+    std::vector<rtdn::Q> g((size_t)n * 4), gp, hp, ho((size_t)n * rttm::kHistoryQuads);
+    std::memcpy(g.data(), gbuffer, (size_t)n * 64);
+    rttm::Camera cam{};
+    if (history_prev) {
+        gp.resize((size_t)n * 4);
+        hp.resize((size_t)n * rttm::kHistoryQuads);
+        std::memcpy(gp.data(), gbuffer_prev, (size_t)n * 64);
+        std::memcpy(hp.data(), history_prev, (size_t)n * rttm::kHistoryQuads * 16);
+        std::memcpy(&cam, cam_prev, sizeof cam);
+    }
+    const rttm::PlainSrc prev{hp.data(), gp.data(), width, n};
+    for (int64_t p = 0; p < n; ++p) {
+        const rttm::Pixel r = rttm::temporal_pixel(prev, history_prev != nullptr, cam, sums + 3 * p, counts ? counts[p] : spp,
+                                                   &g[4 * p], width, height, tp);
+        for (int k = 0; k < rttm::kHistoryQuads; ++k) ho[(size_t)(k * n + p)] = r.h[k];
+        if (out_mean)
+            for (int c = 0; c < 3; ++c) out_mean[3 * p + c] = r.mean[c];
+        if (out_variance) out_variance[p] = r.variance;
+    }
+    std::memcpy(history_out, ho.data(), (size_t)n * rttm::kHistoryQuads * 16);
+    return RT_OK;
+}
+
 // The measured variance on the host (rt_moments.h is its text): per pixel, from its sum, its
 // moment, its count and its first-hit record.
 int rt_variance_from_moments(const float *sums, const float *moments, const int32_t *counts, int32_t spp, int32_t width,
@@ -1012,6 +1075,22 @@ int rt_denoise_guided_check(const char *who, const float *sums, const int32_t *c
     if (rtdg::resolve_params(p.iterations, p.sigma_var, p.sigma_plane, p.normal_power_log2, p.firefly, *resolved))
         return rt_fail(RT_ERR_ARG, w + ": iterations above " + std::to_string(rtdn::kMaxIterations) + ", normal_power_log2 above " +
                                        std::to_string(rtdn::kMaxNormalPowerLog2) + " or a non-finite sigma or firefly factor");
+    return RT_OK;
+}
+
+int rt_temporal_check(const char *who, const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
+                      const float *gbuffer, const rt_camera *cam_prev, const float *gbuffer_prev, const float *history_prev,
+                      const rt_temporal_params *params, const float *history_out, rttm::Params *resolved) {
+    const std::string w = who;
+    if (int rc = frame_check(w, !sums || !gbuffer || !history_out, counts, spp, width, height)) return rc;
+    if (history_prev && (!cam_prev || !gbuffer_prev))
+        return rt_fail(RT_ERR_ARG, w + ": a previous history needs the previous camera and G-buffer");
+    if (history_prev == history_out) return rt_fail(RT_ERR_ARG, w + ": history_out must not be history_prev");
+    const rt_temporal_params none{0.f, 0.f, 0.f, 0.f, 0};
+    const rt_temporal_params &p = params ? *params : none;
+    if (rttm::resolve_params(p.alpha, p.alpha_moments, p.sigma_plane, p.normal_min, p.max_history, *resolved))
+        return rt_fail(RT_ERR_ARG, w + ": alpha or alpha_moments above 1, max_history above " + std::to_string(rttm::kMaxMaxHistory) +
+                                       " or a non-finite parameter");
     return RT_OK;
 }
 

@@ -53,12 +53,28 @@
 //   RT_AOV_OUT=pfx      the first-hit features of the frame: pfx.normal.ppm (N * 0.5 + 0.5),
 //                       pfx.albedo.ppm (the linear base colour) and pfx.depth.pgm (binary 16-bit PGM,
 //                       big-endian, hit distance / the frame's largest; a miss is 0).
+// A moving camera (rt_scene_set_camera, rt_history_*; unset, every byte written is the one above):
+//   RT_CAMERAS=file     one camera per line, 14 floats: position, right, up, forward, tan_half_fov x
+//                       and y (empty lines and lines that start with # are skipped).  Every line
+//                       renders one one-shot frame at the given samples from that camera, written to
+//                       the output name with the line's index before the extension (out.0000.ppm,
+//                       out.0001.ppm, ...); each raw frame is the reference's frame for that camera.
+//                       Excludes RT_PASS_SPP, RT_ADAPT and RT_CHECKPOINT; a malformed line is an
+//                       error, reported before anything is rendered.
+//   RT_TEMPORAL=alpha   (needs RT_CAMERAS) every frame's sums pass through a reprojected temporal
+//                       history on device 0 before the finish (alpha 0: the default 0.2); RT_DENOISE
+//                       or RT_DENOISE_GUIDED then filter the integrated mean at spp 1 with the
+//                       history's G-buffer.  A still camera gains nothing this way (parity frames of
+//                       one view are identical): RT_PASS_SPP is the tool for a still view.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstdio>
+#include <fstream>
 #include <iostream>
 #include <iomanip>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -334,6 +350,100 @@ static void render_passes(rt_scene *scene, int width, int height, int samples, i
     write_variance();
 }
 
+// RT_CAMERAS: the file's cameras, or false and why.
+static bool read_cameras(const char *path, std::vector<rt_camera> &cams, std::string &why) {
+    std::ifstream f(path);
+    if (!f) {
+        why = std::string("RT_CAMERAS: cannot read ") + path;
+        return false;
+    }
+    std::string line;
+    for (int no = 1; std::getline(f, line); ++no) {
+        const size_t first = line.find_first_not_of(" \t\r");
+        if (first == std::string::npos || line[first] == '#') continue;
+        std::istringstream in(line);
+        float w[14];
+        int got = 0;
+        std::string token;
+        while (in >> token) {
+            char *end = nullptr;
+            const float v = std::strtof(token.c_str(), &end);
+            if (end == token.c_str() || *end != '\0' || !std::isfinite(v) || got == 14) {
+                got = -1;
+                break;
+            }
+            w[got++] = v;
+        }
+        if (got != 14 || !(w[12] > 0.f) || !(w[13] > 0.f)) {
+            why = std::string("RT_CAMERAS: ") + path + " line " + std::to_string(no) +
+                  ": expected 14 finite floats (position, right, up, forward, tan_half_fov x and y > 0)";
+            return false;
+        }
+        rt_camera c;
+        std::copy(w, w + 3, c.pos);
+        std::copy(w + 3, w + 12, c.axes);
+        std::copy(w + 12, w + 14, c.tan_half_fov);
+        cams.push_back(c);
+    }
+    if (cams.empty()) {
+        why = std::string("RT_CAMERAS: no camera in ") + path;
+        return false;
+    }
+    return true;
+}
+
+// out.ppm -> out.0003.ppm (a name without an extension: the index appended).
+static std::string indexed_name(const std::string &path, size_t k) {
+    char idx[16];
+    std::snprintf(idx, sizeof idx, ".%04zu", k);
+    const size_t slash = path.find_last_of('/'), dot = path.find_last_of('.');
+    if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return path + idx;
+    return path.substr(0, dot) + idx + path.substr(dot);
+}
+
+// RT_CAMERAS: one one-shot frame per camera through the existing frame path; with `temporal`
+// (RT_TEMPORAL) every frame's sums pass through a history on device 0 before the finish.
+static void render_cameras(rt_scene *scene, int width, int height, int samples, int n_gpus, int fast_chunk, Denoise &dn,
+                           const std::vector<rt_camera> &cams, const std::string &output, bool temporal, float alpha,
+                           const char *aov_out) {
+    struct Held {   // (freed on every way out, before the scene)
+        rt_history *h = nullptr;
+        ~Held() { rt_history_free(h); }
+    } held;
+    rt_params p{};
+    p.spp = samples;
+    p.row_block = 8;
+    if (fast_chunk) {
+        p.flags = RT_FLAG_FAST;
+        p.fast_chunk = fast_chunk;
+    }
+    rt_temporal_params tp{alpha, 0.f, 0.f, 0.f, 0};
+    std::vector<uint8_t> rgb((size_t)width * height * 3);
+    std::vector<float> sums;
+    for (size_t k = 0; k < cams.size(); ++k) {
+        check(rt_scene_set_camera(scene, &cams[k]));
+        rt_stats st{};
+        if (temporal || dn.on) {
+            sums.resize((size_t)width * height * 3);
+            check(rt_render_frame(scene, &p, n_gpus, nullptr, nullptr, sums.data(), &st));
+        }
+        if (temporal) {
+            if (!held.h) check(rt_history_create(scene, 0, &held.h));   // (the frame has uploaded the scene to device 0)
+            check(rt_history_push_frame_u8(held.h, sums.data(), nullptr, samples, &tp, dn.on && !dn.guided ? &dn.params : nullptr,
+                                           dn.guided ? &dn.guided_params : nullptr, rgb.data()));
+        } else if (dn.on) {
+            dn.gbuffer = frame_gbuffer(scene, width, height);   // (this camera's)
+            check(dn.frame(sums.data(), nullptr, samples, width, height, rgb.data()));
+        } else {
+            check(rt_render_frame(scene, &p, n_gpus, nullptr, rgb.data(), nullptr, &st));
+        }
+        const std::string name = indexed_name(output, k);
+        check(rt_write_ppm(name.c_str(), rgb.data(), width, height));
+        if (aov_out && *aov_out) write_aovs(indexed_name(aov_out, k), frame_gbuffer(scene, width, height), width, height);
+        std::cout << "Frame " << k << " drawn into " << name << " (render " << st.render_ms << " ms)" << std::endl;
+    }
+}
+
 static int int_arg(const char *s) { return std::stoi(std::string(s).substr(0, std::string(s).find(' '))); }
 
 int main(int argc, char *argv[]) {
@@ -403,6 +513,41 @@ int main(int argc, char *argv[]) {
         return 1;
     }
     dn.measured = moments;
+    const char *cams_env = std::getenv("RT_CAMERAS"), *temporal_env = std::getenv("RT_TEMPORAL");
+    const bool cams_on = cams_env && *cams_env, temporal_on = temporal_env && *temporal_env;
+    if (temporal_on && !cams_on) {
+        std::cerr << "rt_solution: RT_TEMPORAL needs RT_CAMERAS (a still view gains nothing from a history: use RT_PASS_SPP)" << std::endl;
+        rt_scene_free(scene);
+        return 1;
+    }
+    if (cams_on && ((pass_env && *pass_env) || (ckpt && *ckpt) || adaptive)) {
+        std::cerr << "rt_solution: RT_CAMERAS excludes RT_PASS_SPP, RT_ADAPT and RT_CHECKPOINT (one one-shot frame per camera)" << std::endl;
+        rt_scene_free(scene);
+        return 1;
+    }
+    if (cams_on) {
+        std::vector<rt_camera> cams;
+        std::string why;
+        const float alpha = temporal_on ? std::strtof(temporal_env, nullptr) : 0.f;
+        if (!read_cameras(cams_env, cams, why) || !(alpha >= 0.f && alpha <= 1.f)) {
+            std::cerr << "rt_solution: " << (why.empty() ? std::string("RT_TEMPORAL must be in 0..1") : why) << std::endl;
+            rt_scene_free(scene);
+            return 1;
+        }
+        try {
+            render_cameras(scene, width, height, samples, n_gpus, fast_chunk, dn, cams, output, temporal_on, alpha, aov_out);
+        } catch (const std::exception &e) {
+            std::cerr << "rt_solution: " << e.what() << std::endl;
+            rt_scene_free(scene);
+            return 1;
+        }
+        double total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        std::cout << "      " << total << " seconds (" << total * 1000 << " ms) elapsed." << std::endl;
+        std::cout << cams.size() << " frames drawn into " << indexed_name(output, 0) << " .. " << indexed_name(output, cams.size() - 1)
+                  << std::endl;
+        rt_scene_free(scene);
+        return 0;
+    }
     if ((pass_env && *pass_env) || (ckpt && *ckpt) || adaptive) {
         const int pass_spp = pass_env && *pass_env ? std::atoi(pass_env) : 0;
         if (pass_env && *pass_env && pass_spp < 1) throw std::runtime_error("RT_PASS_SPP must be >= 1");

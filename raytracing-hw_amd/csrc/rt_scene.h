@@ -18,6 +18,7 @@ struct rt_scene {
     float cam_axes[9] = {0};
     float cam_fov[2] = {0, 0};
     float tan_half_fov[2] = {0, 0};
+    uint32_t cam_epoch = 0;   // rt_scene_set_camera calls so far (an accumulator remembers the one it renders)
 
     std::vector<float> tri, tri_attr, tri_tan, node;
     uint32_t bvh_depth = 0;
@@ -39,6 +40,8 @@ int rt_fail(int code, const std::string &msg);
 
 // implemented in rt_device.hip: frees every device copy and the device image
 void rt_device_scene_release(rt_scene *s);
+// implemented in rt_device.hip: the scene's camera into the launch arguments of every device copy
+void rt_device_scene_set_camera(rt_scene *s);
 
 // argument checks of rt_denoise / rt_denoise_device (rt_host.cpp): RT_OK and the resolved
 // parameters (rt_denoise.h), or the failure as `who` reports it
@@ -57,6 +60,14 @@ int rt_denoise_guided_check(const char *who, const float *sums, const int32_t *c
 // the same for rt_variance_from_moments and its device form (rt_moments.h), which have no parameters
 int rt_variance_check(const char *who, const float *sums, const float *moments, const int32_t *counts, int32_t spp, int32_t width,
                       int32_t height, const float *gbuffer, const float *out);
+
+// the same for rt_temporal and its kin (rt_temporal.h); history_prev given: cam_prev and gbuffer_prev must be
+namespace rttm {
+struct Params;
+}
+int rt_temporal_check(const char *who, const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
+                      const float *gbuffer, const rt_camera *cam_prev, const float *gbuffer_prev, const float *history_prev,
+                      const rt_temporal_params *params, const float *history_out, rttm::Params *resolved);
 
 // row partition helper (rt_host.cpp)
 int64_t rt_shard_rows_impl(int32_t height, int32_t rank, int32_t world, int32_t row_block, int32_t *rows_out);
