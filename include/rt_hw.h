@@ -412,6 +412,17 @@ int32_t rt_accum_fast_chunk(const rt_accum *accum);
  * out_i n x 6 (hit, object id or -1, AABB tests, triangle tests, light AABB tests,
  * light triangle tests). */
 int rt_intersect_rays(rt_scene *scene, int64_t n, const float *org, const float *dir, float *out_f, int64_t *out_i);
+/* The same query and output layout through one of the device's traversals (test entry; ray i is
+ * thread i, so the caller decides which rays share a wave):
+ *   path 0  closest_hit and light_pdf (rt_path.h): rt_intersect_rays is this call;
+ *   path 1  the per-lane steps: trav_step over a private stack with the runahead kernel's cull
+ *           form, then light_step;
+ *   path 2  the cooperative step trav_step_coop with the plain kernel's constants and four stack
+ *           frames in LDS ((u, v) recomputed afterwards, as its shading pass does), then light_step.
+ * The loops of paths 1 and 2 are bounded by the scene's size; a ray still traversing at the
+ * bound is reported with hit = -2.  Any other path is RT_ERR_ARG. */
+int rt_intersect_rays_via(rt_scene *scene, int32_t path, int64_t n, const float *org, const float *dir, float *out_f,
+                          int64_t *out_i);
 
 /* --- frame finish / output (host) ---------------------------------------------------- */
 /* mean -> ACES -> powf(1/2.2) -> roundf(clamp(v*255)) per scene.cpp:54-64, vector.h:222-233, :400-407 */

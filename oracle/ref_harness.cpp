@@ -16,6 +16,7 @@
 //                                              sets Scene::ray_depth, scene.h:24, "-" = no ppm)
 //   time    <gltf> W H spp [rows [stride]]     time Scene::render itself (scene.cpp:17-65)
 //   rays    <gltf> W H n out.rtd               closest-hit known answers (bvh.cpp:239-243) + per-ray test counts
+//   rays_from <gltf> W H rays_in.rtd out.rtd   the same record for the rays of an rtdump file (origin, direction)
 //   dump    <gltf> W H out.rtd                 post-BVH scene arrays (bvh.cpp:166 reorders objects)
 //   samplers <gltf> W H n out.rtd              SceneDistribution::sample/pdf + RNG known answers
 //   pixels  <gltf> W H spp idx.i64 out.rtd [threads]
@@ -281,27 +282,23 @@ static int mode_pixels(int argc, char **argv) {
     return 0;
 }
 
-// Ray-level known answers: camera rays through jittered pixel positions plus one random
-// secondary ray from each camera hit.  Records BVH::intersect's result and the number of
-// AABB / triangle tests it made (reference traversal order), and the light-mixture pdf.
-static int mode_rays(int argc, char **argv) {
-    if (argc < 7) throw std::runtime_error("rays <gltf> W H n out.rtd");
-    int W = atoi(argv[3]), H = atoi(argv[4]), n = atoi(argv[5]);
-    Scene s = parse_scene_gltf(argv[2], W, H, 1);
-    std::mt19937_64 g(20261015);
-    std::uniform_real_distribution<float> U01(0.f, 1.f);
-    std::vector<float> org, dir, t, uv, nrm;
+// Ray-level known answers, shared by `rays` and `rays_from`: one ray exactly as handed to
+// Ray::Ray (origin, un-normalised direction): BVH::intersect's result, the number of AABB /
+// triangle tests it made (reference traversal order), and the light-mixture pdf with its counts.
+struct RayRecorder {
+    const Scene &s;
+    std::unique_ptr<rng::ManyLightsDistribution> ml;
+    std::vector<float> org, dir, t, uv, nrm, lpdf;
     std::vector<int32_t> hit, inside;
     std::vector<int64_t> obj;
-    std::vector<uint64_t> naabb, ntri;
-    std::vector<float> lpdf;
-    std::vector<uint64_t> nlaabb, nltri;
-    bool has_lights = false;
-    for (auto &p : s.objects) has_lights |= p.emissive();
-    std::unique_ptr<rng::ManyLightsDistribution> ml;
-    if (has_lights) ml = std::make_unique<rng::ManyLightsDistribution>(s.objects);
-    // records the ray exactly as handed to Ray::Ray (origin, un-normalised direction)
-    auto record = [&](vector3f o, vector3f dd) {
+    std::vector<uint64_t> naabb, ntri, nlaabb, nltri;
+
+    explicit RayRecorder(const Scene &scene) : s(scene) {
+        bool has_lights = false;
+        for (auto &p : s.objects) has_lights |= p.emissive();
+        if (has_lights) ml = std::make_unique<rng::ManyLightsDistribution>(s.objects);
+    }
+    Intersection record(vector3f o, vector3f dd) {
         Ray r(o, dd);
         reset_counters();
         t_mode = 0;
@@ -324,7 +321,37 @@ static int mode_rays(int argc, char **argv) {
         nlaabb.push_back(c2.laabb);
         nltri.push_back(c2.ltri);
         return it;
-    };
+    }
+    uint64_t write(const char *path) const {
+        RtDump d(path);
+        const uint64_t m = hit.size();
+        d.put("origin", org, {m, 3});
+        d.put("direction", dir, {m, 3});
+        d.put("hit", hit);
+        d.put("object_id", obj);
+        d.put("t", t);
+        d.put("uv", uv, {m, 2});
+        d.put("normal", nrm, {m, 3});
+        d.put("inside", inside);
+        d.put("n_aabb", naabb);
+        d.put("n_tri", ntri);
+        d.put("light_pdf", lpdf);
+        d.put("n_light_aabb", nlaabb);
+        d.put("n_light_tri", nltri);
+        d.close();
+        return m;
+    }
+};
+
+// Camera rays through jittered pixel positions plus one random secondary ray from each
+// camera hit.
+static int mode_rays(int argc, char **argv) {
+    if (argc < 7) throw std::runtime_error("rays <gltf> W H n out.rtd");
+    int W = atoi(argv[3]), H = atoi(argv[4]), n = atoi(argv[5]);
+    Scene s = parse_scene_gltf(argv[2], W, H, 1);
+    std::mt19937_64 g(20261015);
+    std::uniform_real_distribution<float> U01(0.f, 1.f);
+    RayRecorder rec(s);
     for (int k = 0; k < n; ++k) {
         // camera-like ray: same construction as Camera::cast_in_pixel (camera.cpp:49-62)
         vector2f tt{(U01(g) * 2.f - 1.f) * std::tan(s.camera->get_fov().x / 2),
@@ -334,31 +361,33 @@ static int mode_rays(int argc, char **argv) {
         d0 = d0 + tt.y * s.camera->get_axis(1);
         d0 = d0 + 1.f * s.camera->get_axis(2);
         vector3f o0 = s.camera->get_position();
-        Intersection it = record(o0, d0);
+        Intersection it = rec.record(o0, d0);
         if (it.successful) {
             Ray r(o0, d0);
             vector3f pos = r.origin + r.direction * it.distance;
             vector3f d{U01(g) * 2.f - 1.f, U01(g) * 2.f - 1.f, U01(g) * 2.f - 1.f};
-            record(pos + d * 1e-4f, d);
+            rec.record(pos + d * 1e-4f, d);
         }
     }
-    RtDump d(argv[6]);
-    uint64_t m = hit.size();
-    d.put("origin", org, {m, 3});
-    d.put("direction", dir, {m, 3});
-    d.put("hit", hit);
-    d.put("object_id", obj);
-    d.put("t", t);
-    d.put("uv", uv, {m, 2});
-    d.put("normal", nrm, {m, 3});
-    d.put("inside", inside);
-    d.put("n_aabb", naabb);
-    d.put("n_tri", ntri);
-    d.put("light_pdf", lpdf);
-    d.put("n_light_aabb", nlaabb);
-    d.put("n_light_tri", nltri);
-    d.close();
+    const uint64_t m = rec.write(argv[6]);
     std::printf("{\"mode\": \"rays\", \"rays\": %llu}\n", (unsigned long long)m);
+    return 0;
+}
+
+// The same record for a caller's rays: the `origin` and `direction` arrays (n x 3 floats) of
+// an rtdump file, in file order, bit for bit as given (non-finite values included).
+static int mode_rays_from(int argc, char **argv) {
+    if (argc < 7) throw std::runtime_error("rays_from <gltf> W H rays_in.rtd out.rtd");
+    int W = atoi(argv[3]), H = atoi(argv[4]);
+    const std::vector<float> org = rtdump_read_f32(argv[5], "origin", 3);
+    const std::vector<float> dir = rtdump_read_f32(argv[5], "direction", 3);
+    if (org.size() != dir.size()) throw std::runtime_error("rays_from: origin and direction differ in length");
+    Scene s = parse_scene_gltf(argv[2], W, H, 1);
+    RayRecorder rec(s);
+    for (size_t k = 0; k + 2 < org.size(); k += 3)
+        rec.record(vector3f{org[k], org[k + 1], org[k + 2]}, vector3f{dir[k], dir[k + 1], dir[k + 2]});
+    const uint64_t m = rec.write(argv[6]);
+    std::printf("{\"mode\": \"rays_from\", \"rays\": %llu}\n", (unsigned long long)m);
     return 0;
 }
 
@@ -559,11 +588,12 @@ static int mode_finish(int argc, char **argv) {
 
 int main(int argc, char **argv) {
     try {
-        if (argc < 2) throw std::runtime_error("usage: ref_harness sums|time|rays|dump|samplers|finish|pixels ...");
+        if (argc < 2) throw std::runtime_error("usage: ref_harness sums|time|rays|rays_from|dump|samplers|finish|pixels ...");
         std::string m = argv[1];
         if (m == "sums") return mode_sums(argc, argv);
         if (m == "time") return mode_time(argc, argv);
         if (m == "rays") return mode_rays(argc, argv);
+        if (m == "rays_from") return mode_rays_from(argc, argv);
         if (m == "dump") return mode_dump(argc, argv);
         if (m == "samplers") return mode_samplers(argc, argv);
         if (m == "finish") return mode_finish(argc, argv);

@@ -7,6 +7,7 @@
 #pragma once
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -55,3 +56,52 @@ template <> inline char RtDump::code<uint32_t>() { return 'I'; }
 template <> inline char RtDump::code<int64_t>() { return 'q'; }
 template <> inline char RtDump::code<uint64_t>() { return 'Q'; }
 template <> inline char RtDump::code<uint8_t>() { return 'B'; }
+
+// Reads the f32 array `name` of an RTD1 file whose shape is (n, cols).  Every length in the
+// file is checked against the file's size before it is used.
+inline std::vector<float> rtdump_read_f32(const std::string &path, const std::string &name, uint64_t cols) {
+    std::FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) throw std::runtime_error("rtdump: cannot open " + path);
+    std::vector<uint8_t> buf;
+    uint8_t chunk[65536];
+    size_t got;
+    while ((got = std::fread(chunk, 1, sizeof chunk, f)) > 0) buf.insert(buf.end(), chunk, chunk + got);
+    std::fclose(f);
+    size_t p = 4;
+    auto need = [&](uint64_t n) {
+        if (n > buf.size() || p > buf.size() - n) throw std::runtime_error("rtdump: truncated " + path);
+    };
+    if (buf.size() < 4 || std::memcmp(buf.data(), "RTD1", 4) != 0) throw std::runtime_error("rtdump: not an RTD1 file: " + path);
+    for (;;) {
+        need(4);
+        uint32_t len;
+        std::memcpy(&len, &buf[p], 4);
+        p += 4;
+        if (len == 0) break;
+        need((uint64_t)len + 2);
+        const std::string nm((const char *)&buf[p], len);
+        p += len;
+        const uint8_t dt = buf[p], nd = buf[p + 1];
+        p += 2;
+        need(8ull * nd);
+        std::vector<uint64_t> shape(nd);
+        if (nd) std::memcpy(shape.data(), &buf[p], 8ull * nd);
+        p += 8ull * nd;
+        uint64_t count = 1;
+        for (uint64_t d : shape) {
+            if (d != 0 && count > buf.size() / d) throw std::runtime_error("rtdump: truncated " + path);
+            count *= d;
+        }
+        const uint64_t item = (dt == 'd' || dt == 'q' || dt == 'Q') ? 8 : (dt == 'B' ? 1 : 4);
+        if (count > buf.size() / item) throw std::runtime_error("rtdump: truncated " + path);
+        need(count * item);
+        if (nm == name) {
+            if (dt != 'f' || nd != 2 || shape[1] != cols) throw std::runtime_error("rtdump: " + name + " is not an (n, cols) f32 array");
+            std::vector<float> out(count);
+            if (count) std::memcpy(out.data(), &buf[p], count * 4);
+            return out;
+        }
+        p += count * item;
+    }
+    throw std::runtime_error("rtdump: no array " + name + " in " + path);
+}

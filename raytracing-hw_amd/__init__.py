@@ -158,6 +158,8 @@ ABI = {
                                        ctypes.POINTER(RtStats)]),
     "rt_intersect_rays": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, _c_f, _c_f, _c_f,
                                          ctypes.POINTER(ctypes.c_int64)]),
+    "rt_intersect_rays_via": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, _c_f, _c_f, _c_f,
+                                             ctypes.POINTER(ctypes.c_int64)]),
     "rt_tonemap_u8": (ctypes.c_int, [_c_f, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_b]),
     "rt_tonemap_u8_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.c_void_p, ctypes.c_void_p]),
@@ -346,15 +348,18 @@ class Scene:
         del keep
         return cls(h.value, int(arrays["width"]), int(arrays["height"]), int(arrays["samples"]))
 
-    def intersect_rays(self, org, dirs):
-        """Closest hit + light pdf per ray: returns (f32 n x 4 [t,u,v,light_pdf], i64 n x 6)."""
+    def intersect_rays(self, org, dirs, path=0):
+        """Closest hit + light pdf per ray: returns (f32 n x 4 [t,u,v,light_pdf], i64 n x 6).
+        path: the traversal (rt_intersect_rays_via: 0 closest_hit, 1 per-lane steps, 2 coop step;
+        ray i is thread i; hit = -2 where a bounded loop of paths 1 and 2 did not end)."""
         org = np.ascontiguousarray(org, np.float32).reshape(-1, 3)
         dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
         n = org.shape[0]
         out_f = np.zeros((n, 4), np.float32)
         out_i = np.zeros((n, 6), np.int64)
-        _check(lib().rt_intersect_rays(self._h, n, org.ctypes.data_as(_c_f), dirs.ctypes.data_as(_c_f),
-                                       out_f.ctypes.data_as(_c_f), out_i.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        _check(lib().rt_intersect_rays_via(self._h, int(path), n, org.ctypes.data_as(_c_f), dirs.ctypes.data_as(_c_f),
+                                           out_f.ctypes.data_as(_c_f),
+                                           out_i.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         _after_render()
         return out_f, out_i
 

@@ -12,6 +12,8 @@
 //                           chooses, as a compacted ascending list (with rt_select_scan_kernel),
 //                           and rt_mark_kernel / rt_counts_kernel beside it (rt_accum_device.h)
 //   rt_rays_kernel          BVH::intersect + light pdf for explicit rays (test entry)
+//   rt_rays_via_kernel      the same query through trav_step / trav_step_coop and light_step
+//                           (rt_intersect_rays_via paths 1 and 2; bounded loops)
 //   rt_gbuffer_kernel       first-hit feature records from the pixel-centre rays (rt_gbuffer.h)
 //   rt_denoise_{prepare,level,resolve}_kernel  the edge-avoiding a-trous filter of a frame,
 //                           guided by those records (rt_denoise.h)
@@ -1520,37 +1522,6 @@ int rt_render_multi(rt_scene *s, const rt_params *p, int32_t n_devices, float *o
     return rt_render_frame(s, p, n, nullptr, nullptr, out, st);
 }
 
-int rt_intersect_rays(rt_scene *s, int64_t n, const float *org, const float *dir, float *out_f, int64_t *out_i) {
-    if (!s || n < 0 || (n > 0 && (!org || !dir || !out_f || !out_i))) return rt_fail(RT_ERR_ARG, "rt_intersect_rays: bad argument");
-    if (n == 0) return RT_OK;
-    int rc = ensure_device_scene(s, 0);
-    if (rc) return rc;
-    DeviceGuard guard(0);
-    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
-    float *d_o = nullptr, *d_d = nullptr, *d_f = nullptr;
-    long long *d_i = nullptr;
-    const size_t v3 = (size_t)n * 3 * sizeof(float);
-    hipError_t e = hipMalloc(&d_o, v3);
-    if (e == hipSuccess) e = hipMalloc(&d_d, v3);
-    if (e == hipSuccess) e = hipMalloc(&d_f, (size_t)n * 4 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&d_i, (size_t)n * 6 * sizeof(long long));
-    if (e == hipSuccess) e = hipMemcpy(d_o, org, v3, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_d, dir, v3, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(rt_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, s->dev[0]->ds,
-                           (long long)n, d_o, d_d, d_f, d_i);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out_f, d_f, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_i, d_i, (size_t)n * 6 * sizeof(long long), hipMemcpyDeviceToHost);
-    (void)hipFree(d_o);
-    (void)hipFree(d_d);
-    (void)hipFree(d_f);
-    (void)hipFree(d_i);
-    if (e != hipSuccess) return rt_fail(RT_ERR_DEVICE, std::string("rt_intersect_rays: ") + hipGetErrorString(e));
-    return RT_OK;
-}
-
 #if defined(RT_DEBUG_CHECKS)
 // debug builds only: first recorded index violation (code << 56 | value), 0 = none
 int rt_debug_take(unsigned long long *word) {
@@ -1746,6 +1717,55 @@ __device__ __forceinline__ uint32_t pop_check_hash(uint32_t x) {   // (lowbias32
     x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
     return x;
 }
+// The whole queries of rt_device_selfcheck 5 and of rt_intersect_rays_via, each bounded by
+// `bound` steps; false: the lane was still traversing there.  `bits`: the root box result as the
+// producers store it (rt_wavefront.h store_qray, rt_mega.h mega_begin).
+__device__ __forceinline__ uint32_t query_root_bits(const rtd::NodeRec &root, const rtd::Ray &r) {
+    float e;
+    return rtd::box_hit<false>(root.mn, root.mx, r, e) ? 0u : 8u;
+}
+// trav_step_coop with the plain kernel's constants; every lane of the wave calls (valid or not).
+template <int POPS, class Stack>
+__device__ __forceinline__ bool coop_query(const DevScene &sc, const rtd::NodeRec &root, const rtd::Ray &r, uint32_t bits,
+                                           bool valid, int bound, rtd::TravStateU &T, Stack &S, Counters &cnt) {
+    const rtd::GlobalNodes gn{sc.node};
+    bool active = rtd::trav_start<true>(bits, root.a, root.b, T, cnt) && valid;
+    int leaf_defer = 0;
+    for (int it = 0; it < bound && __any(active); ++it)
+        if (rtd::trav_step_coop<true, kCoopLeavesPlain, false, rtd::kLeafDeferPlain, kPlainFarDist2, POPS>(
+                sc, r, T, S, gn, cnt, active, kCoopRoundMinPlain, rtd::NoHook{}, &leaf_defer))
+            active = false;
+    return !active;
+}
+// the per-lane trav_step loop
+template <bool DIST2, class Stack>
+__device__ __forceinline__ bool lane_query(const DevScene &sc, const rtd::NodeRec &root, const rtd::Ray &r, uint32_t bits,
+                                           bool valid, int bound, rtd::TravState &T, Stack &S, Counters &cnt) {
+    const rtd::GlobalNodes gn{sc.node};
+    bool active = rtd::trav_start<true>(bits, root.a, root.b, T, cnt) && valid;
+    for (int it = 0; it < bound && active; ++it)
+        if (rtd::trav_step<true, DIST2>(sc, r, T, S, gn, cnt)) active = false;
+    return !active;
+}
+// ManyLightsDistribution::pdf(r.o, r.d) as the light-split kernel walks it (rt_mega.h
+// mega_shade_split starts the walk, light_step is one node of it); lp: light_pdf's result.
+template <class Stack>
+__device__ __forceinline__ bool light_query(const DevScene &sc, const rtd::Ray &r, bool valid, int bound, Stack &S,
+                                            Counters &cnt, float &lp) {
+    const rtd::Ray lr = rtd::make_ray(r.o, r.d);   // light_pdf's Ray(point, direction)
+    const float4 dq = make_float4(r.d.x, r.d.y, r.d.z, 0.f);
+    rtd::TravState T;
+    T.acc = 0.f;
+    T.sp = 0;
+    S.put(T.sp++, make_uint2(0u, 0u));
+    cnt.lq++;
+    bool active = valid;
+    for (int it = 0; it < bound && active; ++it)
+        if (rtd::light_step<true>(sc, lr, T, S, cnt, &dq)) active = false;
+    lp = T.acc / (float)sc.n_lights;
+    return !active;
+}
+
 template <int K, int POPS>
 __global__ void __launch_bounds__(256) pop_check_kernel(DevScene sc, int n_rays, int bound, unsigned long long *bad) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -1759,26 +1779,18 @@ __global__ void __launch_bounds__(256) pop_check_kernel(DevScene sc, int n_rays,
               root.mn[2] + u[2] * (root.mx[2] - root.mn[2])};
     const float z = 2.f * u[3] - 1.f, ph = 6.28318530718f * u[4], s = sqrtf(fmaxf(0.f, 1.f - z * z));
     const rtd::Ray r = rtd::make_ray(o, rtv::V3{s * cosf(ph), s * sinf(ph), z});
-    const rtd::GlobalNodes gn{sc.node};
     // the coop query
     rtd::TravStateU T;
     Counters cnt{0, 0, 0, 0, 0, 0, 0};
     uint2 spill[rtd::kStack - K];
     rtd::LdsStackT<K> S{spill};
-    bool active = rtd::trav_start<true>(0u, root.a, root.b, T, cnt) && valid;
-    int leaf_defer = 0;
-    for (int it = 0; it < bound && __any(active); ++it)
-        if (rtd::trav_step_coop<true, kCoopLeavesPlain, false, rtd::kLeafDeferPlain, kPlainFarDist2, POPS>(
-                sc, r, T, S, gn, cnt, active, kCoopRoundMinPlain, rtd::NoHook{}, &leaf_defer))
-            active = false;
+    const bool active = !coop_query<POPS>(sc, root, r, 0u, valid, bound, T, S, cnt);
     // the per-lane query
     rtd::TravState T2;
     Counters cnt2{0, 0, 0, 0, 0, 0, 0};
     uint2 frames[rtd::kStack];
     rtd::ArrayStack S2{frames};
-    bool active2 = rtd::trav_start<true>(0u, root.a, root.b, T2, cnt2) && valid;
-    for (int it = 0; it < bound && active2; ++it)
-        if (rtd::trav_step<true, kPlainFarDist2>(sc, r, T2, S2, gn, cnt2)) active2 = false;
+    const bool active2 = !lane_query<kPlainFarDist2>(sc, root, r, 0u, valid, bound, T2, S2, cnt2);
     unsigned long long local = 0;
     if (valid)
         local = (active | active2 | (T.best.prim != T2.best.prim) | (__float_as_uint(T.best.t) != __float_as_uint(T2.best.t)) |
@@ -1786,6 +1798,58 @@ __global__ void __launch_bounds__(256) pop_check_kernel(DevScene sc, int n_rays,
                     ? 1ull : 0ull;
     for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
     if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
+}
+
+// rt_intersect_rays_via paths 1 and 2: the caller's ray k through the production traversals
+// (thread k; threads past n take ray 0 and write nothing, since every lane of a wave must call
+// the coop step).  Path 1: trav_step with the runahead kernel's cull form over an ArrayStack.
+// Path 2: the coop query above, as rt_device_selfcheck 5 instantiates it with four LDS frames
+// and the plain kernel's pop cap, then hit_uv.  Both then walk the light BVH with light_step
+// over the same stack.  hit = -2: a loop reached its bound.
+template <int PATH>
+__global__ void __launch_bounds__(256) rt_rays_via_kernel(DevScene sc, long long n, int bound, int light_bound,
+                                                           const float *org, const float *dir, float *out_f,
+                                                           long long *out_i) {
+    static_assert(PATH == 1 || PATH == 2, "path 0 is rt_rays_kernel");
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool valid = k < n;
+    const long long kr = valid ? k : 0;
+    const rtd::Ray r = rtd::make_ray(rtv::V3{org[3 * kr], org[3 * kr + 1], org[3 * kr + 2]},
+                                     rtv::V3{dir[3 * kr], dir[3 * kr + 1], dir[3 * kr + 2]});
+    const rtd::NodeRec root = rtd::load_node(sc.node, 0);
+    const uint32_t bits = query_root_bits(root, r);
+    Counters c1{0, 0, 0, 0, 0, 0, 0}, c2{0, 0, 0, 0, 0, 0, 0};
+    rtd::Hit h;
+    bool done, light_done = true;
+    float lp = 0.f;
+    if constexpr (PATH == 1) {
+        uint2 frames[rtd::kStack];
+        rtd::ArrayStack S{frames};
+        rtd::TravState T;
+        done = lane_query<RT_SPEC_FAR_DIST2 != 0>(sc, root, r, bits, valid, bound, T, S, c1);
+        h = T.best;
+        if (sc.n_lights) light_done = light_query(sc, r, valid, light_bound, S, c2, lp);
+    } else {
+        uint2 spill[rtd::kStack - 4];
+        rtd::LdsStackT<4> S{spill};
+        rtd::TravStateU T;
+        done = coop_query<RT_PLAIN_MAX_POPS>(sc, root, r, bits, valid, bound, T, S, c1);
+        h = T.best;
+        if (rtd::kUvRecompute && valid && h.prim >= 0) rtd::hit_uv(sc, r, h);
+        if (sc.n_lights) light_done = light_query(sc, r, valid, light_bound, S, c2, lp);
+    }
+    if (!valid) return;
+    const bool ok = h.prim >= 0;
+    out_f[4 * k + 0] = ok ? h.t : 0.f;
+    out_f[4 * k + 1] = ok ? h.u : 0.f;
+    out_f[4 * k + 2] = ok ? h.v : 0.f;
+    out_f[4 * k + 3] = lp;
+    out_i[6 * k + 0] = (done && light_done) ? (long long)ok : -2ll;
+    out_i[6 * k + 1] = ok ? h.prim : -1;
+    out_i[6 * k + 2] = c1.aabb;
+    out_i[6 * k + 3] = c1.tri;
+    out_i[6 * k + 4] = c2.laabb;
+    out_i[6 * k + 5] = c2.ltri;
 }
 
 namespace {
@@ -1904,6 +1968,55 @@ int pop_selfcheck(uint64_t *mismatches) {
 }  // namespace
 
 extern "C" {
+
+int rt_intersect_rays_via(rt_scene *s, int32_t path, int64_t n, const float *org, const float *dir, float *out_f,
+                          int64_t *out_i) {
+    if (!s || n < 0 || (n > 0 && (!org || !dir || !out_f || !out_i))) return rt_fail(RT_ERR_ARG, "rt_intersect_rays: bad argument");
+    if (path < 0 || path > 2) return rt_fail(RT_ERR_ARG, "rt_intersect_rays_via: unknown path " + std::to_string(path));
+    if (n == 0) return RT_OK;
+    int rc = ensure_device_scene(s, 0);
+    if (rc) return rc;
+    DeviceGuard guard(0);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    const DevScene &sc = s->dev[0]->ds;
+    // (a walk visits every node and triangle at most once; the factor covers deferred steps)
+    const long long bound = 4ll * ((long long)sc.n_nodes + sc.n_tris) + 64, light_bound = 8ll * sc.n_lights + 64;
+    if (path != 0 && (sc.n_nodes < 1 || sc.n_tris < 1)) return rt_fail(RT_ERR_ARG, "rt_intersect_rays_via: empty scene");
+    if (bound > 0x7fffffffll || light_bound > 0x7fffffffll) return rt_fail(RT_ERR_LIMIT, "rt_intersect_rays_via: scene too large");
+    float *d_o = nullptr, *d_d = nullptr, *d_f = nullptr;
+    long long *d_i = nullptr;
+    const size_t v3 = (size_t)n * 3 * sizeof(float);
+    hipError_t e = hipMalloc(&d_o, v3);
+    if (e == hipSuccess) e = hipMalloc(&d_d, v3);
+    if (e == hipSuccess) e = hipMalloc(&d_f, (size_t)n * 4 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&d_i, (size_t)n * 6 * sizeof(long long));
+    if (e == hipSuccess) e = hipMemcpy(d_o, org, v3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_d, dir, v3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+        if (path == 0)
+            hipLaunchKernelGGL(rt_rays_kernel, grid, block, 0, nullptr, sc, (long long)n, d_o, d_d, d_f, d_i);
+        else if (path == 1)
+            hipLaunchKernelGGL(rt_rays_via_kernel<1>, grid, block, 0, nullptr, sc, (long long)n, (int)bound, (int)light_bound,
+                               d_o, d_d, d_f, d_i);
+        else
+            hipLaunchKernelGGL(rt_rays_via_kernel<2>, grid, block, 0, nullptr, sc, (long long)n, (int)bound, (int)light_bound,
+                               d_o, d_d, d_f, d_i);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out_f, d_f, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_i, d_i, (size_t)n * 6 * sizeof(long long), hipMemcpyDeviceToHost);
+    (void)hipFree(d_o);
+    (void)hipFree(d_d);
+    (void)hipFree(d_f);
+    (void)hipFree(d_i);
+    if (e != hipSuccess) return rt_fail(RT_ERR_DEVICE, std::string("rt_intersect_rays: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+int rt_intersect_rays(rt_scene *s, int64_t n, const float *org, const float *dir, float *out_f, int64_t *out_i) {
+    return rt_intersect_rays_via(s, 0, n, org, dir, out_f, out_i);
+}
 
 int rt_device_selfcheck(int32_t which, uint64_t *mismatches) {
     if (!mismatches) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck: null output");

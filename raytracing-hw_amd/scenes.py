@@ -26,6 +26,10 @@ the reference's accessor budgets:
                          textures of odd sizes (1x1 to 13x6) in all four material slots, the
                          emissive one included, UVs over about [-3, 4], four constant-UV quads
                          and a camera zfar that cuts the room's far end (edge-case parity tests).
+* ``geoedge``         — not from the reference's examples either: a closed room holding exact
+                         duplicates, coplanar overlap, a dyadic lattice, zero-area triangles and
+                         lights, slivers, meshes at 3e9, 1e15, 2^63 and 1e-20 and the BVH builder's
+                         ties (138 tris; tests/test_geoedge.py).
 
 The textures are read by the reference through tinygltf/stb_image with ``req_comp=4``
 (thirdparty/tinygltf/tiny_gltf.h:2609), i.e. RGBA8 with alpha 255 for P6 input.
@@ -771,7 +775,124 @@ def make_texedge(directory: str) -> str:
     return b.write(directory, "texedge")
 
 
+# geoedge: degenerate geometry and scale extremes (tests/test_geoedge.py).  No
+# node carries a transform: every coordinate below is the float the parsers see.
+GEOEDGE_ROOM = ((-4.0, -2.0, -6.0), (4.0, 2.0, 2.0))
+GEOEDGE_CAMERA_Z = 1.5
+GEOEDGE_LATTICE = {"origin": (-1.0, -0.5, -3.0), "eu": (2.0, 0.0, 0.0), "ev": (0.0, 1.0, 0.0), "nu": 4, "nv": 4}
+GEOEDGE_FAR_X = 3.0e9          # the mesh beyond the reference's 1e9 hit limit
+GEOEDGE_HUGE_EDGE = 1.0e15     # box_dist2 of its box against kFarMax2 and float overflow
+GEOEDGE_HUGE2_EDGE = 2.0 ** 63  # det of a perpendicular ray is 2^126: rcp_ieee's division branch
+GEOEDGE_TINY = 1.0e-20
+# (material name, base colour, emission strength or None)
+GEOEDGE_MATERIALS = [("Wall", (0.8, 0.8, 0.8), None), ("Red", (0.8, 0.2, 0.2), None), ("Green", (0.2, 0.8, 0.2), None),
+                     ("Blue", (0.2, 0.2, 0.8), None), ("Yellow", (0.8, 0.8, 0.2), None), ("Light", (0.0, 0.0, 0.0), 5.0),
+                     ("DegenLight", (0.0, 0.0, 0.0), 5.0)]
+
+
+def _quad_tris(origin, eu, ev, nu=1, nv=1):
+    pos, _, _, _, idx = quad_mesh(origin, eu, ev, nu, nv, (0, 0), (0, 0))
+    return pos[idx.reshape(-1, 3)]
+
+
+def geoedge_parts():
+    """The geoedge meshes in file order: (name, material index, triangles (n, 3, 3) float32).
+    The ray generator of the tests reads the same list."""
+    (x0, y0, z0), (x1, y1, z1) = GEOEDGE_ROOM
+    T = lambda *tris: np.array(tris, F32).reshape(-1, 3, 3)   # noqa: E731
+    parts = [
+        # the closed room: axis-aligned quads (boxes of zero extent) and one ordinary light
+        ("Floor", 0, _quad_tris([x0, y0, z1], [x1 - x0, 0, 0], [0, 0, z0 - z1], 2, 2)),
+        ("Ceiling", 0, _quad_tris([x0, y1, z0], [x1 - x0, 0, 0], [0, 0, z1 - z0], 2, 2)),
+        ("Back", 0, _quad_tris([x0, y0, z0], [x1 - x0, 0, 0], [0, y1 - y0, 0], 2, 2)),
+        ("Left", 1, _quad_tris([x0, y0, z1], [0, 0, z0 - z1], [0, y1 - y0, 0], 2, 2)),
+        ("Right", 2, _quad_tris([x1, y0, z0], [0, 0, z1 - z0], [0, y1 - y0, 0], 2, 2)),
+        ("Front", 0, _quad_tris([x1, y0, z1], [x0 - x1, 0, 0], [0, y1 - y0, 0], 2, 2)),
+        ("Light", 5, _quad_tris([-1.0, 1.96875, -3.0], [2.0, 0, 0], [0, 0, 2.0])),
+        # exact duplicates: one mesh twice at one place, two materials (every hit ties in t, u, v)
+        ("DupA", 1, _quad_tris([-3.5, -1.0, -4.0], [2.0, 0, 0], [0, 2.0, 0], 2, 2)),
+        ("DupB", 2, _quad_tris([-3.5, -1.0, -4.0], [2.0, 0, 0], [0, 2.0, 0], 2, 2)),
+        # coplanar overlap, offset by a power of two: equal t, other (u, v)
+        ("CoplanarA", 3, _quad_tris([1.0, -1.0, -4.5], [2.0, 0, 0], [0, 2.0, 0])),
+        ("CoplanarB", 4, _quad_tris([1.5, -1.0, -4.5], [2.0, 0, 0], [0, 2.0, 0])),
+        # the lattice: every coordinate a multiple of 1/4
+        ("Lattice", 4, _quad_tris(GEOEDGE_LATTICE["origin"], GEOEDGE_LATTICE["eu"], GEOEDGE_LATTICE["ev"],
+                                  GEOEDGE_LATTICE["nu"], GEOEDGE_LATTICE["nv"])),
+        # zero area: collinear, two coincident, three coincident; diffuse and emissive
+        ("DegenDiffuse", 3, T([[2.5, -1.5, -2.0], [2.75, -1.5, -2.0], [3.0, -1.5, -2.0]],
+                              [[2.5, -1.0, -2.0], [2.5, -1.0, -2.0], [3.0, -1.25, -2.25]],
+                              [[2.75, -0.5, -2.0]] * 3)),
+        ("DegenLight", 6, T([[-3.0, 1.5, -2.0], [-2.75, 1.5, -2.0], [-2.5, 1.5, -2.0]],
+                            [[-3.0, 1.25, -2.0], [-3.0, 1.25, -2.0], [-2.5, 1.0, -2.25]],
+                            [[-2.75, 0.75, -2.0]] * 3)),
+        # slivers: a needle (edge ratio 1e6) and a fan nearly edge-on to the camera
+        ("Needle", 1, T([[-0.5, -1.75, -2.0], [0.5, -1.75, -2.0], [-0.5, -1.75 + 1e-6, -2.0]])),
+        ("Fan", 2, np.concatenate([_geoedge_fan(k) for k in range(8)])),
+        # scale extremes
+        ("Far", 3, _quad_tris([GEOEDGE_FAR_X, -4096.0, -4096.0], [0, 0, 8192.0], [0, 8192.0, 0])),
+        ("Huge", 1, T([[100.0, -100.0, -60.0], [100.0 + GEOEDGE_HUGE_EDGE, -100.0, -60.0],
+                       [100.0, -100.0 + GEOEDGE_HUGE_EDGE, -60.0]])),
+        ("Huge2", 2, T([[128.0, -128.0, -70.0], [GEOEDGE_HUGE2_EDGE, -128.0, -70.0], [128.0, GEOEDGE_HUGE2_EDGE, -70.0]])),
+        ("Tiny", 4, T([[0, 0, 0], [GEOEDGE_TINY, 0, 0], [0, GEOEDGE_TINY, 0]],
+                      [[GEOEDGE_TINY, GEOEDGE_TINY, 0], [0, GEOEDGE_TINY, 0], [GEOEDGE_TINY, 0, 0]])),
+        # builder ties: congruent triangles in a row (centres equal on two axes), six triangles
+        # with one box (centres all one point), one triangle alone
+        ("Row", 3, np.stack([np.array([[0.25 * k - 1.0, 1.0, -5.0], [0.25 * k - 0.875, 1.0, -5.0],
+                                       [0.25 * k - 1.0, 1.25, -5.0]], F32) for k in range(8)])),
+        ("SameCentre", 4, _geoedge_same_centre((2.0, 0.5, -2.0), 0.5)),
+        ("Single", 1, T([[-2.0, -1.5, -1.0], [-1.5, -1.5, -1.0], [-2.0, -1.0, -1.5]])),
+    ]
+    return [(n, m, np.ascontiguousarray(t, F32)) for n, m, t in parts]
+
+
+def _geoedge_fan(k: int):
+    """One triangle through the camera's line of sight: two vertices on the sight line
+    towards (x_k, -1.2, -4), the third 1/64 off it."""
+    cam = np.array([0.0, 0.0, GEOEDGE_CAMERA_Z])
+    d = np.array([-1.75 + 0.5 * k, -1.2, -4.0]) - cam
+    d /= np.linalg.norm(d)
+    return np.array([[cam + 3.0 * d, cam + 5.0 * d, cam + 4.0 * d + np.array([0.0, 1.0 / 64, 0.0])]], F32)
+
+
+def _geoedge_same_centre(lo, size):
+    lo = np.asarray(lo, np.float64)
+    corners = [((0, 0, 0), (1, 1, 0), (0, 1, 1)), ((1, 0, 0), (0, 1, 0), (1, 1, 1)), ((0, 0, 1), (1, 0, 0), (0, 1, 0)),
+               ((1, 1, 1), (0, 0, 1), (1, 0, 0)), ((0, 1, 0), (1, 0, 1), (0, 0, 0)), ((1, 0, 1), (0, 1, 1), (1, 1, 0))]
+    return np.array([[lo + size * np.array(c, np.float64) for c in tri] for tri in corners], F32)
+
+
+def make_geoedge(directory: str) -> str:
+    """A closed room (8 x 4 x 8) with one ordinary emissive quad, holding the geometry clean
+    meshes never have: exact duplicates, coplanar overlap, a dyadic lattice, zero-area
+    triangles (diffuse and emissive), slivers, meshes at 3e9, 1e15, 2^63 and 1e-20, and the
+    builder's ties (equal centres, zero-extent boxes, a one-triangle mesh)."""
+    b = GltfBuilder()
+    b.extensions_used.add(_EMISSIVE)
+    b.cameras = [{"name": "Camera", "type": "perspective", "perspective": {
+        "aspectRatio": 24 / 16, "yfov": 0.9, "zfar": 100, "znear": 0.1}}]
+    b.nodes = [{"camera": 0, "name": "Camera", "translation": [0, 0, GEOEDGE_CAMERA_Z]}]
+    for name, base, strength in GEOEDGE_MATERIALS:
+        m = {"doubleSided": True, "name": name,
+             "pbrMetallicRoughness": {"baseColorFactor": list(base) + [1], "metallicFactor": 0, "roughnessFactor": 1}}
+        if strength is not None:
+            m["emissiveFactor"] = [1, 1, 1]
+            m["extensions"] = {_EMISSIVE: {"emissiveStrength": strength}}
+        b.materials.append(m)
+    for name, mat, tris in geoedge_parts():
+        pos = tris.reshape(-1, 3)
+        n = np.cross(tris[:, 1].astype(np.float64) - tris[:, 0], tris[:, 2].astype(np.float64) - tris[:, 0])
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            ln = np.linalg.norm(n, axis=1, keepdims=True)
+            n = np.where((ln > 0) & np.isfinite(ln), n / ln, [0.0, 0.0, 1.0])   # (zero area: any unit normal)
+        nrm = np.repeat(n, 3, axis=0)
+        uv = np.zeros((len(pos), 2), F32)
+        prim = b.primitive(pos, nrm, np.arange(len(pos)), mat, uv=uv)
+        b.nodes.append({"mesh": b.mesh(name, [prim]), "name": name})
+    return b.write(directory, "geoedge")
+
+
 SCENES = {
+    "geoedge": lambda d: make_geoedge(d),
     "cornell": lambda d: make_cornell(d),
     "cornell_blob": lambda d: make_cornell_blob(d),
     "practice6_1": lambda d: make_practice6_1(d),

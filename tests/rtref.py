@@ -220,6 +220,22 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
+def same(a, b):
+    """The geoedge comparison rule, element by element (a bool array): integers are equal;
+    floats are equal bit for bit, so -0.0 and +0.0 differ, with one exception: two NaNs are
+    equal whatever their sign and payload (x86's default NaN is negative, the GPU's positive).
+    No tolerance."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape:
+        raise ValueError(f"shapes differ: {a.shape} {b.shape}")
+    fa, fb = a.dtype.kind == "f", b.dtype.kind == "f"
+    if fa != fb:
+        raise TypeError(f"comparing {a.dtype} with {b.dtype}")
+    if not fa:
+        return a.astype(np.int64) == b.astype(np.int64)
+    return (bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))
+
+
 def row_hash(sums):
     h = np.full(sums.shape[0], 1469598103934665603, np.uint64)
     b = np.ascontiguousarray(sums).view(np.uint8).reshape(sums.shape[0], -1)

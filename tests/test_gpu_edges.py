@@ -18,7 +18,9 @@ import rtref
 pytestmark = pytest.mark.gpu
 
 # (scene, W, H, spp, ray depth or None for the scene's own 6)
-GOLDEN_CASES = [("texedge", 40, 24, 6, None)] + rtref.DEPTH_CASES
+# (geoedge: degenerate geometry and scale extremes; its golden frame holds no
+# NaN, tests/test_geoedge.py, so bit equality is the whole comparison rule there too)
+GOLDEN_CASES = [("texedge", 40, 24, 6, None)] + rtref.DEPTH_CASES + [("geoedge", 24, 16, 4, None)]
 # texture sizes (W, H) dealt over sponza_mini's 69 texture slots
 ODD_SIZES = [(1, 1), (1, 7), (5, 1), (5, 3), (3, 5), (13, 6), (2, 2), (7, 9), (6, 13), (4, 4), (9, 4), (4, 10)]
 
@@ -103,7 +105,8 @@ def test_goldens_every_schedule(gpu, name, w, h, s, depth):
     assert st["pixels"] == w * h
 
 
-@pytest.mark.parametrize("name,w,h,s,depth", [("texedge", 40, 24, 6, None), ("cornell", 33, 17, 8, 15)])
+@pytest.mark.parametrize("name,w,h,s,depth", [("texedge", 40, 24, 6, None), ("cornell", 33, 17, 8, 15),
+                                              ("geoedge", 24, 16, 4, None)])
 def test_fast_mode_vs_oracle(gpu, oracle, name, w, h, s, depth):
     """Fast mode (per-sample Philox streams) on the odd textures, the emissive slot and the
     clip, and at depth 15, against the oracle's restatement of it."""

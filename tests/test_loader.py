@@ -14,7 +14,7 @@ import pytest
 
 import rtref
 
-EXACT = ["cornell", "sponza_mini", "cornell_blob", "practice6_1", "texedge"]
+EXACT = ["cornell", "sponza_mini", "cornell_blob", "practice6_1", "texedge", "geoedge"]
 ROTATED = ["cornell_blob", "practice6_1"]
 KEYS = ["tri", "tri_attr", "tri_tan", "node", "light", "light_node", "mesh_f", "mesh_tex", "mesh_normal_transform"]
 

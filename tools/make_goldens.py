@@ -32,6 +32,12 @@ Outputs (tests/golden/):
                                              # (EDGE_SUMS; their metadata goes to edges_meta.json,
                                              # no other file under tests/golden/ is touched)
     <name>_sums_<W>x<H>x<S>_d<D>.rtd        the same sums with Scene::ray_depth = D
+    python tools/make_goldens.py --geoedge   # only the geoedge fixture (degenerate geometry and
+                                             # caller-made rays): scene files, geoedge_dump.rtd,
+                                             # geoedge_rays_in.rtd (tests/geoedge_util.py),
+                                             # geoedge_rays.rtd (ref_harness rays_from on them),
+                                             # geoedge_sums_24x16x4.rtd and its .ppm; its metadata
+                                             # goes to golden_meta.json "geoedge"
 """
 import hashlib
 import importlib.util
@@ -285,7 +291,48 @@ def edge_goldens():
     print(json.dumps(meta, indent=1))
 
 
+GEOEDGE_SUMS = (24, 16, 4)
+
+
+def geoedge_goldens():
+    """The geoedge fixture: the scene, the reference's dump of it, the generated rays and the
+    reference's answers to them, and one small frame.  Touches no other fixture's files."""
+    import geoedge_util
+    name = "geoedge"
+    rt = rtref.package()
+    sdir = os.path.join(GOLD, "scenes", name)
+    if os.path.isdir(sdir):
+        shutil.rmtree(sdir)
+    gltf = scenes.SCENES[name](sdir)
+    raw = os.path.join("/tmp", f"{name}_dump_full.rtd")
+    meta = {"dump": harness("dump", gltf, 64, 64, raw)}
+    compact_dump(raw, os.path.join(GOLD, f"{name}_dump.rtd"))
+    arrays = rtref.ref_arrays(rt, name, 64, 64, 1)
+    org, dirs, cls = geoedge_util.geoedge_rays(arrays)
+    rays_in = os.path.join(GOLD, f"{name}_rays_in.rtd")
+    rtdump.save(rays_in, {"origin": org, "direction": dirs, "cls": cls})
+    meta["rays"] = harness("rays_from", gltf, 64, 64, rays_in, os.path.join(GOLD, f"{name}_rays.rtd"))
+    meta["ray_classes"] = {c: int((cls == k).sum()) for k, c in enumerate(geoedge_util.CLASSES)}
+    w, h, s = GEOEDGE_SUMS
+    meta[f"sums_{w}x{h}x{s}"] = harness("sums", gltf, w, h, s, os.path.join(GOLD, f"{name}_sums_{w}x{h}x{s}.rtd"), 8,
+                                        os.path.join(GOLD, f"{name}_{w}x{h}x{s}.ppm"))
+    for v in meta.values():
+        if isinstance(v, dict):
+            v.pop("seconds", None)   # (the only field that differs between two runs)
+    path = os.path.join(GOLD, "golden_meta.json")
+    allmeta = json.load(open(path))
+    allmeta[name] = meta
+    with open(path, "w") as f:
+        json.dump(allmeta, f, indent=1, sort_keys=True)
+    print(json.dumps(meta, indent=1))
+
+
 def main():
+    if "--geoedge" in sys.argv:
+        if not os.path.exists(HARNESS):
+            sys.exit("build the reference harness first: make -C oracle ref")
+        geoedge_goldens()
+        return
     if "--edges" in sys.argv:
         if not os.path.exists(HARNESS):
             sys.exit("build the reference harness first: make -C oracle ref")
