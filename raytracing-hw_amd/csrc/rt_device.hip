@@ -11,9 +11,8 @@
 //   rt_select_kernel        an accumulator's subset pass: the pixels the rule of rt_select.h
 //                           chooses, as a compacted ascending list (with rt_select_scan_kernel),
 //                           and rt_mark_kernel / rt_counts_kernel beside it (rt_accum_device.h)
-//   rt_rays_kernel          BVH::intersect + light pdf for explicit rays (test entry)
-//   rt_rays_via_kernel      the same query through trav_step / trav_step_coop and light_step
-//                           (rt_intersect_rays_via paths 1 and 2; bounded loops)
+//   rt_rays[_via]_kernel    BVH::intersect + light pdf for explicit rays, and the six *_check_kernel of
+//                           rt_device_selfcheck: the test entries (rt_check_device.h)
 //   rt_gbuffer_kernel       first-hit feature records from the pixel-centre rays (rt_gbuffer.h)
 //   rt_denoise_{prepare,level,resolve}_kernel  the edge-avoiding a-trous filter of a frame,
 //                           guided by those records (rt_denoise.h)
@@ -33,7 +32,8 @@
 // (rt_render_frame) takes its devices, row partition and buffer layout from rt_frame_plan.h
 // (host only as well).  The accumulator (rt_accum_*, rt_accum_device.h) takes its kinds, parameter
 // checks, host state and passes from rt_accum_plan.h, its checkpoint file from rt_accum_file.h
-// (both host only) and the layout of its per-pixel records from rt_records.h.
+// (both host only) and the layout of its per-pixel records from rt_records.h.  The test entries
+// (rt_device_selfcheck, rt_intersect_rays[_via], the debug build's rt_debug_*) are rt_check_device.h.
 //
 // Concurrency: one render per (scene, device) may be in flight at a time (the pixel queue,
 // counters, vertex records and order buffers of a device copy are shared by its launches);
@@ -522,29 +522,6 @@ __global__ void __launch_bounds__(256) wf_shade_kernel(DevScene sc_in, ShardGeom
         }
     }
     rtd::counters_flush<COUNT>(cnt, counters);
-}
-
-// Ray-level entry: BVH::intersect + ManyLightsDistribution::pdf for explicit rays.
-__global__ void __launch_bounds__(256) rt_rays_kernel(DevScene sc, long long n, const float *org, const float *dir,
-                                                       float *out_f, long long *out_i) {
-    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    rtd::Ray r = rtd::make_ray(rtv::V3{org[3 * k], org[3 * k + 1], org[3 * k + 2]},
-                               rtv::V3{dir[3 * k], dir[3 * k + 1], dir[3 * k + 2]});
-    Counters c1{0, 0, 0, 0, 0, 0, 0}, c2{0, 0, 0, 0, 0, 0, 0};
-    rtd::Hit h;
-    const bool ok = rtd::closest_hit<true>(sc, r, h, c1);
-    const float lp = sc.n_lights ? rtd::light_pdf<true>(sc, r.o, r.d, c2) : 0.f;
-    out_f[4 * k + 0] = ok ? h.t : 0.f;
-    out_f[4 * k + 1] = ok ? h.u : 0.f;
-    out_f[4 * k + 2] = ok ? h.v : 0.f;
-    out_f[4 * k + 3] = lp;
-    out_i[6 * k + 0] = ok;
-    out_i[6 * k + 1] = ok ? h.prim : -1;
-    out_i[6 * k + 2] = c1.aabb;
-    out_i[6 * k + 3] = c1.tri;
-    out_i[6 * k + 4] = c2.laabb;
-    out_i[6 * k + 5] = c2.ltri;
 }
 
 // ------------------------------------------------------------------------ host side
@@ -1271,28 +1248,31 @@ static int quant_thresholds_upload() {
     return RT_OK;
 }
 
+// The launch behind both tonemap entries: per-pixel counts where d_counts is given, else `normalizer`.
+static int finish_launch(const float *d_sum, const int32_t *d_counts, float normalizer, int32_t width, int32_t height,
+                         uint8_t *d_rgb, void *stream) {
+    if (int rc = quant_thresholds_upload()) return rc;
+    const long long n = (long long)width * height * 3;
+    const dim3 blocks((unsigned)std::min<long long>((n + 255) / 256, 4096));
+    if (d_counts)
+        hipLaunchKernelGGL(rt_finish_counts_kernel, blocks, dim3(256), 0, (hipStream_t)stream, d_sum, d_counts, n, d_rgb);
+    else
+        hipLaunchKernelGGL(rt_finish_kernel, blocks, dim3(256), 0, (hipStream_t)stream, d_sum, n, normalizer, d_rgb);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
 int rt_tonemap_u8_counts_device(const float *d_sum, const int32_t *d_counts, int32_t width, int32_t height, uint8_t *d_rgb,
                                 void *stream) {
     if (!d_sum || !d_counts || !d_rgb || width <= 0 || height <= 0)
         return rt_fail(RT_ERR_ARG, "rt_tonemap_u8_counts_device: bad argument");
-    if (int rc = quant_thresholds_upload()) return rc;
-    const long long n = (long long)width * height * 3;
-    const unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(rt_finish_counts_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_sum, d_counts, n, d_rgb);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    return finish_launch(d_sum, d_counts, 0.f, width, height, d_rgb, stream);
 }
 
 int rt_tonemap_u8_device(const float *d_sum, int32_t width, int32_t height, int32_t spp, uint8_t *d_rgb, void *stream) {
     if (!d_sum || !d_rgb || width <= 0 || height <= 0 || spp <= 0)
         return rt_fail(RT_ERR_ARG, "rt_tonemap_u8_device: bad argument");
-    if (int rc = quant_thresholds_upload()) return rc;
-    const long long n = (long long)width * height * 3;
-    const unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(rt_finish_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_sum, n,
-                       1.f / (float)spp, d_rgb);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    return finish_launch(d_sum, nullptr, 1.f / (float)spp, width, height, d_rgb, stream);
 }
 
 int rt_render(rt_scene *s, const rt_params *p, float *out, rt_stats *st) {
@@ -1522,554 +1502,6 @@ int rt_render_multi(rt_scene *s, const rt_params *p, int32_t n_devices, float *o
     return rt_render_frame(s, p, n, nullptr, nullptr, out, st);
 }
 
-#if defined(RT_DEBUG_CHECKS)
-// debug builds only: first recorded index violation (code << 56 | value), 0 = none
-int rt_debug_take(unsigned long long *word) {
-    unsigned long long z = 0;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(word, HIP_SYMBOL(rt_debug_word), sizeof z));
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(rt_debug_word), &z, sizeof z));
-    return RT_OK;
-}
-// debug builds only: poison every lane's traversal phase and stack depth at the lane-resident
-// kernel's start (rt_mega_kernel), for the packing test
-int rt_debug_set_poison(int on) {
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(rt_debug_poison), &on, sizeof on));
-    return RT_OK;
-}
-#endif
-
-// rt_device_selfcheck 0: rcp_ieee against the IEEE division 1.f / x over every float x
-// with a normal reciprocal path (|x| in [2^-126, 2^125)), on the device.
-__global__ void __launch_bounds__(256) rcp_check_kernel(unsigned long long *bad) {
-    unsigned long long local = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (1ull << 32);
-         i += (uint64_t)gridDim.x * blockDim.x) {
-        const float x = __uint_as_float((uint32_t)i);
-        const float ax = fabsf(x);
-        if (!(ax >= 0x1p-126f && ax < 0x1p125f)) continue;
-        const float a = rtd::rcp_ieee(x), b = 1.f / x;
-        local += __float_as_uint(a) != __float_as_uint(b);
-    }
-    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
-    if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
-}
-
-// rt_device_selfcheck 1: the computed linear texel decode (rt_path.h unorm8) against the IEEE
-// division (float)b / 255.f for every byte b, and the packed LDS RNG word (rt_mega.h
-// rng_word_pack) round trip over the state range and both normal-cache flags.
-__global__ void __launch_bounds__(256) decode_check_kernel(unsigned long long *bad) {
-    unsigned long long local = 0;
-    if (blockIdx.x == 0) {
-        const uint32_t b = threadIdx.x;
-        local += __float_as_uint(rtd::unorm8(b)) != __float_as_uint((float)b / 255.f);
-    }
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2147483647ull;
-         i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t x = (uint32_t)i;
-#pragma unroll
-        for (uint32_t f = 0; f < 2; ++f) {
-            uint32_t ux, uf;
-            rtd::rng_word_unpack(rtd::rng_word_pack(x, f), ux, uf);
-            local += (ux != x) | (uf != f);
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
-    if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
-}
-
-// rt_device_selfcheck 4: every material record of an uploaded scene (rt_material.h), read the
-// way the shading pass reads it, against the scene's own tables on the device: the 12 mesh_f
-// floats and 4 mesh_tex indices bit for bit, each slot's descriptor against its texture's
-// tex_info row, (0, 1, 1) for an absent slot, zero padding; a present slot's texture must end
-// inside the texel array (n_texels).  Counts the dwords that differ.
-#if RT_SHADE_GATHER
-__global__ void __launch_bounds__(256) mat_check_kernel(rtd::DevScene sc, unsigned long long n_texels, unsigned long long *bad) {
-    unsigned long long local = 0;
-    for (int m = blockIdx.x * blockDim.x + threadIdx.x; m < sc.n_meshes; m += gridDim.x * blockDim.x) {
-        uint32_t r[32];
-        for (int q = 0; q < 8; ++q) {
-            const uint4 x = sc.mat[8 * m + q];
-            r[4 * q] = x.x; r[4 * q + 1] = x.y; r[4 * q + 2] = x.z; r[4 * q + 3] = x.w;
-        }
-        for (int k = 0; k < 12; ++k) local += r[k] != __float_as_uint(sc.mesh_f[12 * m + k]);
-        for (int k = 0; k < 4; ++k) {
-            const int t = sc.mesh_tex[4 * m + k];
-            local += r[rtmat::kRecTex + k] != (uint32_t)t;
-            uint4 ti = make_uint4(0u, 1u, 1u, 4u);
-            if (t >= 0) {
-                ti = sc.tex_info[t];
-                local += (unsigned long long)ti.x + (unsigned long long)((ti.y + 3) / 4) * ((ti.z + 3) / 4) * 16 > n_texels;
-            }
-            const uint32_t *d = r + rtmat::kRecDesc + 3 * k;
-            local += (d[0] != ti.x) + (d[1] != ti.y) + (d[2] != ti.z);
-        }
-        for (int k = 28; k < 32; ++k) local += r[k] != 0u;
-    }
-    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
-    if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
-}
-#endif
-
-// rt_device_selfcheck 3: the root-free cull (rt_wavefront.h far_gt, kFarMax2) against the
-// device's own sqrtf(x) > acc: 2^24 of the host test's generated pairs (far_case_acc /
-// far_case_x: every exponent of acc, x around acc * acc and around the exact boundary), the
-// special values (zeros, denormals, perfect squares, inf, NaN) and the floats within 64 ulps
-// of kFarMax2 against sqrtf(x) > 1e9f.
-__global__ void __launch_bounds__(256) far_check_kernel(unsigned long long *bad) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;   // (2^24 threads)
-    unsigned long long local = 0;
-    {
-        const uint32_t j = i / (uint32_t)rtd::kFarCaseXs, v = i % (uint32_t)rtd::kFarCaseXs;
-        const float acc = rtd::far_case_acc(j % (uint32_t)rtd::kFarCaseExps, j / (uint32_t)rtd::kFarCaseExps);
-        const float x = rtd::far_case_x(acc, (int)v);
-        local += rtd::far_gt(x, acc) != (sqrtf(x) > acc);
-    }
-    if (i < 54u) {
-        const float accs[6] = {0.f, -0.f, 1e-45f, 0x1p-126f, 1.f, 1e9f};
-        const float xs[9] = {0.f, 1e-45f, 0x1p-126f, 1.f, 4.f, 9.f, 1e18f, __builtin_inff(), __builtin_nanf("")};
-        const float acc = accs[i / 9u], x = xs[i % 9u];
-        local += rtd::far_gt(x, acc) != (sqrtf(x) > acc);
-    }
-    if (i < 132u) {
-        const float x = i < 129u ? rtd::far_case_step(rtd::kFarMax2, (int)i - 64)
-                                 : (i == 129u ? 0.f : (i == 130u ? __builtin_inff() : __builtin_nanf("")));
-        local += (x > rtd::kFarMax2) != (sqrtf(x) > 1e9f);
-    }
-    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
-    if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
-}
-
-}  // extern "C"
-
-// rt_device_selfcheck 2: the cooperative leaf step (rt_wavefront.h trav_step_coop: four
-// helper lanes per leaf lane, DPP quad min with the triangle index as tie-break, NaN t as no
-// hit, several leaf rounds) against the per-lane sequential loop of trav_step (the reference's
-// in-order strict < of bvh.cpp:226-232 over primitive.cpp:17-57).  Leaves of 1-7 triangles
-// over groups rich in exact duplicates (equal t, u, v), coplanar triangles (equal t), NaN and
-// infinite vertices; every lane of a 256-thread block is a leaf lane, so each step serves 8 of
-// a wave's 64 and the rest wait.  Both round policies (one round per step; rounds until every
-// leaf lane is served).  One mismatching field of a case counts once.
-template <int kLeaves>
-__global__ void __launch_bounds__(256) coop_check_kernel(const float4 *tri, int n_tris, const float4 *nodes,
-                                                          const float4 *rays, const uint2 *leaves, int n_cases,
-                                                          int round_min, unsigned long long *bad) {
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    const bool valid = i < n_cases;
-    DevScene sc{};
-    sc.tri = tri;
-    sc.n_tris = n_tris;
-    sc.node = nodes;
-    sc.n_nodes = 2;
-    const float4 ro = rays[2 * (valid ? i : 0)], rdv = rays[2 * (valid ? i : 0) + 1];
-    const rtd::Ray r = rtd::make_ray(rtv::V3{ro.x, ro.y, ro.z}, rtv::V3{rdv.x, rdv.y, rdv.z});
-    const uint2 lf = leaves[valid ? i : 0];
-    rtd::TravState T;
-    T.best.t = 1e9f;
-    T.best.u = T.best.v = 0.f;
-    T.best.prim = -1;
-    T.acc = 1e9f;
-    T.sp = 0;
-    T.a = T.b = 0;
-    T.k = lf.x;
-    T.kend = lf.y;
-    T.phase = rtd::TP_LEAF;
-    Counters cnt{0, 0, 0, 0, 0, 0, 0};
-    uint2 spill[rtd::kStack - 4];
-    rtd::LdsStackT<4> S{spill};
-    const rtd::GlobalNodes gn{nodes};
-    bool active = valid;
-    for (int it = 0; it < 64 && __any(active); ++it)   // (bounded: 7 triangles, 64 lanes, 8 per round)
-        if (rtd::trav_step_coop<false, kLeaves, false>(sc, r, T, S, gn, cnt, active, round_min)) active = false;
-    // the step keeps (t, triangle) only: (u, v) as the shading pass recomputes them
-    if (rtd::kUvRecompute && valid && T.best.prim >= 0) rtd::hit_uv(sc, r, T.best);
-    // sequential reference: trav_step's per-lane loop, one triangle at a time
-    float acc = 1e9f;
-    rtd::Hit best{1e9f, 0.f, 0.f, -1};
-    for (uint32_t k = lf.x; valid && k < lf.y; ++k) {
-        const float4 q0 = tri[3 * k], q1 = tri[3 * k + 1], q2 = tri[3 * k + 2];
-        rtd::TriHit h;
-        if (rtd::tri_hit_bl(rtv::V3{q0.x, q0.y, q0.z}, rtv::V3{q0.w, q1.x, q1.y}, rtv::V3{q1.z, q1.w, q2.x}, r, h)) {
-            acc = h.t < acc ? h.t : acc;
-            if (h.t < best.t) best = rtd::Hit{h.t, h.u, h.v, (int)k};
-        }
-    }
-    unsigned long long local = 0;
-    if (valid)
-        local = (active | (T.best.prim != best.prim) | (__float_as_uint(T.best.t) != __float_as_uint(best.t)) |
-                 (__float_as_uint(T.best.u) != __float_as_uint(best.u)) |
-                 (__float_as_uint(T.best.v) != __float_as_uint(best.v)) | (__float_as_uint(T.acc) != __float_as_uint(acc)))
-                    ? 1ull : 0ull;
-    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
-    if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
-}
-
-// rt_device_selfcheck 5: whole closest-hit queries on an uploaded scene through trav_step_coop (K
-// stack frames in LDS, at most POPS frames popped per step), against the per-lane trav_step loop
-// over an ArrayStack in scratch, in the same kernel: t, triangle, the local best and the AABB
-// and triangle counts, bit for bit.  The waves hold the real mix of node, leaf and pop lanes
-// (the plain kernel's coop records, leaf rounds and leaf deferral); with K = 4 most waves hold
-// lanes whose frames are in scratch.  Ray i starts inside the root box with a direction uniform
-// on the sphere, both from a hash of i; every 64th lane is inactive from the start and the last
-// wave has a single active lane.  Both loops are bounded by `bound` steps: a lane still
-// traversing there counts as a mismatch (a liveness bug fails the check, it does not hang).
-__device__ __forceinline__ uint32_t pop_check_hash(uint32_t x) {   // (lowbias32)
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-// The whole queries of rt_device_selfcheck 5 and of rt_intersect_rays_via, each bounded by
-// `bound` steps; false: the lane was still traversing there.  `bits`: the root box result as the
-// producers store it (rt_wavefront.h store_qray, rt_mega.h mega_begin).
-__device__ __forceinline__ uint32_t query_root_bits(const rtd::NodeRec &root, const rtd::Ray &r) {
-    float e;
-    return rtd::box_hit<false>(root.mn, root.mx, r, e) ? 0u : 8u;
-}
-// trav_step_coop with the plain kernel's constants; every lane of the wave calls (valid or not).
-template <int POPS, class Stack>
-__device__ __forceinline__ bool coop_query(const DevScene &sc, const rtd::NodeRec &root, const rtd::Ray &r, uint32_t bits,
-                                           bool valid, int bound, rtd::TravStateU &T, Stack &S, Counters &cnt) {
-    const rtd::GlobalNodes gn{sc.node};
-    bool active = rtd::trav_start<true>(bits, root.a, root.b, T, cnt) && valid;
-    int leaf_defer = 0;
-    for (int it = 0; it < bound && __any(active); ++it)
-        if (rtd::trav_step_coop<true, kCoopLeavesPlain, false, rtd::kLeafDeferPlain, kPlainFarDist2, POPS>(
-                sc, r, T, S, gn, cnt, active, kCoopRoundMinPlain, rtd::NoHook{}, &leaf_defer))
-            active = false;
-    return !active;
-}
-// the per-lane trav_step loop
-template <bool DIST2, class Stack>
-__device__ __forceinline__ bool lane_query(const DevScene &sc, const rtd::NodeRec &root, const rtd::Ray &r, uint32_t bits,
-                                           bool valid, int bound, rtd::TravState &T, Stack &S, Counters &cnt) {
-    const rtd::GlobalNodes gn{sc.node};
-    bool active = rtd::trav_start<true>(bits, root.a, root.b, T, cnt) && valid;
-    for (int it = 0; it < bound && active; ++it)
-        if (rtd::trav_step<true, DIST2>(sc, r, T, S, gn, cnt)) active = false;
-    return !active;
-}
-// ManyLightsDistribution::pdf(r.o, r.d) as the light-split kernel walks it (rt_mega.h
-// mega_shade_split starts the walk, light_step is one node of it); lp: light_pdf's result.
-template <class Stack>
-__device__ __forceinline__ bool light_query(const DevScene &sc, const rtd::Ray &r, bool valid, int bound, Stack &S,
-                                            Counters &cnt, float &lp) {
-    const rtd::Ray lr = rtd::make_ray(r.o, r.d);   // light_pdf's Ray(point, direction)
-    const float4 dq = make_float4(r.d.x, r.d.y, r.d.z, 0.f);
-    rtd::TravState T;
-    T.acc = 0.f;
-    T.sp = 0;
-    S.put(T.sp++, make_uint2(0u, 0u));
-    cnt.lq++;
-    bool active = valid;
-    for (int it = 0; it < bound && active; ++it)
-        if (rtd::light_step<true>(sc, lr, T, S, cnt, &dq)) active = false;
-    lp = T.acc / (float)sc.n_lights;
-    return !active;
-}
-
-template <int K, int POPS>
-__global__ void __launch_bounds__(256) pop_check_kernel(DevScene sc, int n_rays, int bound, unsigned long long *bad) {
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    const int lane = (int)(threadIdx.x & 63);
-    const bool last_wave = i >= n_rays - 64;
-    const bool valid = i < n_rays && (last_wave ? lane == 0 : lane != 63);
-    const rtd::NodeRec root = rtd::load_node(sc.node, 0);
-    float u[6];
-    for (int c = 0; c < 6; ++c) u[c] = (float)(pop_check_hash(6u * (uint32_t)i + (uint32_t)c) >> 8) * 0x1p-24f;
-    rtv::V3 o{root.mn[0] + u[0] * (root.mx[0] - root.mn[0]), root.mn[1] + u[1] * (root.mx[1] - root.mn[1]),
-              root.mn[2] + u[2] * (root.mx[2] - root.mn[2])};
-    const float z = 2.f * u[3] - 1.f, ph = 6.28318530718f * u[4], s = sqrtf(fmaxf(0.f, 1.f - z * z));
-    const rtd::Ray r = rtd::make_ray(o, rtv::V3{s * cosf(ph), s * sinf(ph), z});
-    // the coop query
-    rtd::TravStateU T;
-    Counters cnt{0, 0, 0, 0, 0, 0, 0};
-    uint2 spill[rtd::kStack - K];
-    rtd::LdsStackT<K> S{spill};
-    const bool active = !coop_query<POPS>(sc, root, r, 0u, valid, bound, T, S, cnt);
-    // the per-lane query
-    rtd::TravState T2;
-    Counters cnt2{0, 0, 0, 0, 0, 0, 0};
-    uint2 frames[rtd::kStack];
-    rtd::ArrayStack S2{frames};
-    const bool active2 = !lane_query<kPlainFarDist2>(sc, root, r, 0u, valid, bound, T2, S2, cnt2);
-    unsigned long long local = 0;
-    if (valid)
-        local = (active | active2 | (T.best.prim != T2.best.prim) | (__float_as_uint(T.best.t) != __float_as_uint(T2.best.t)) |
-                 (__float_as_uint(T.acc) != __float_as_uint(T2.acc)) | (cnt.aabb != cnt2.aabb) | (cnt.tri != cnt2.tri))
-                    ? 1ull : 0ull;
-    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
-    if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
-}
-
-// rt_intersect_rays_via paths 1 and 2: the caller's ray k through the production traversals
-// (thread k; threads past n take ray 0 and write nothing, since every lane of a wave must call
-// the coop step).  Path 1: trav_step with the runahead kernel's cull form over an ArrayStack.
-// Path 2: the coop query above, as rt_device_selfcheck 5 instantiates it with four LDS frames
-// and the plain kernel's pop cap, then hit_uv.  Both then walk the light BVH with light_step
-// over the same stack.  hit = -2: a loop reached its bound.
-template <int PATH>
-__global__ void __launch_bounds__(256) rt_rays_via_kernel(DevScene sc, long long n, int bound, int light_bound,
-                                                           const float *org, const float *dir, float *out_f,
-                                                           long long *out_i) {
-    static_assert(PATH == 1 || PATH == 2, "path 0 is rt_rays_kernel");
-    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool valid = k < n;
-    const long long kr = valid ? k : 0;
-    const rtd::Ray r = rtd::make_ray(rtv::V3{org[3 * kr], org[3 * kr + 1], org[3 * kr + 2]},
-                                     rtv::V3{dir[3 * kr], dir[3 * kr + 1], dir[3 * kr + 2]});
-    const rtd::NodeRec root = rtd::load_node(sc.node, 0);
-    const uint32_t bits = query_root_bits(root, r);
-    Counters c1{0, 0, 0, 0, 0, 0, 0}, c2{0, 0, 0, 0, 0, 0, 0};
-    rtd::Hit h;
-    bool done, light_done = true;
-    float lp = 0.f;
-    if constexpr (PATH == 1) {
-        uint2 frames[rtd::kStack];
-        rtd::ArrayStack S{frames};
-        rtd::TravState T;
-        done = lane_query<RT_SPEC_FAR_DIST2 != 0>(sc, root, r, bits, valid, bound, T, S, c1);
-        h = T.best;
-        if (sc.n_lights) light_done = light_query(sc, r, valid, light_bound, S, c2, lp);
-    } else {
-        uint2 spill[rtd::kStack - 4];
-        rtd::LdsStackT<4> S{spill};
-        rtd::TravStateU T;
-        done = coop_query<RT_PLAIN_MAX_POPS>(sc, root, r, bits, valid, bound, T, S, c1);
-        h = T.best;
-        if (rtd::kUvRecompute && valid && h.prim >= 0) rtd::hit_uv(sc, r, h);
-        if (sc.n_lights) light_done = light_query(sc, r, valid, light_bound, S, c2, lp);
-    }
-    if (!valid) return;
-    const bool ok = h.prim >= 0;
-    out_f[4 * k + 0] = ok ? h.t : 0.f;
-    out_f[4 * k + 1] = ok ? h.u : 0.f;
-    out_f[4 * k + 2] = ok ? h.v : 0.f;
-    out_f[4 * k + 3] = lp;
-    out_i[6 * k + 0] = (done && light_done) ? (long long)ok : -2ll;
-    out_i[6 * k + 1] = ok ? h.prim : -1;
-    out_i[6 * k + 2] = c1.aabb;
-    out_i[6 * k + 3] = c1.tri;
-    out_i[6 * k + 4] = c2.laabb;
-    out_i[6 * k + 5] = c2.ltri;
-}
-
-namespace {
-// Host-made cases of selfcheck 2 (deterministic): 8-triangle groups of a base triangle, its
-// exact copy, a coplanar one behind an equal-t prefix, its copy, a NaN-vertex one, a random
-// one, the base again and an infinite-vertex one; rays from random origins at the base's
-// centroid (jittered); leaves of 1-7 consecutive triangles.
-void coop_cases(std::vector<float> &tri, std::vector<float> &rays, std::vector<uint32_t> &leaves, int n_cases) {
-    uint64_t x = 0x9e3779b97f4a7c15ull;
-    auto rnd = [&]() {   // [0, 1)
-        x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-        return (float)((x >> 40) & 0xffffff) / 16777216.f;
-    };
-    const int groups = 512;
-    tri.assign((size_t)groups * 8 * 12, 0.f);
-    std::vector<float> cen((size_t)groups * 3);
-    for (int gi = 0; gi < groups; ++gi) {
-        float v0[3], U[3], V[3];
-        for (int c = 0; c < 3; ++c) {
-            v0[c] = rnd() * 4.f - 2.f;
-            U[c] = rnd() * 2.f - 1.f;
-            V[c] = rnd() * 2.f - 1.f;
-            cen[3 * gi + c] = v0[c] + (U[c] + V[c]) / 3.f;
-        }
-        for (int t = 0; t < 8; ++t) {
-            float *o = &tri[((size_t)gi * 8 + t) * 12];
-            float a[3], u[3], w[3];
-            for (int c = 0; c < 3; ++c) {
-                a[c] = v0[c]; u[c] = U[c]; w[c] = V[c];
-                if (t == 2 || t == 3) { a[c] = v0[c] + 0.25f * U[c]; }   // same plane, shifted: equal t, other u
-                if (t == 5) { a[c] = rnd() * 4.f - 2.f; u[c] = rnd() * 2.f - 1.f; w[c] = rnd() * 2.f - 1.f; }
-            }
-            if (t == 4) a[1] = __builtin_nanf("");
-            if (t == 7) u[0] = __builtin_inff();
-            for (int c = 0; c < 3; ++c) { o[c] = a[c]; o[3 + c] = u[c]; o[6 + c] = w[c]; }
-        }
-    }
-    rays.assign((size_t)n_cases * 8, 0.f);
-    leaves.assign((size_t)n_cases * 2, 0u);
-    for (int i = 0; i < n_cases; ++i) {
-        const int gi = (int)(rnd() * groups) % groups;
-        float o[3], d[3];
-        for (int c = 0; c < 3; ++c) {
-            o[c] = rnd() * 20.f - 10.f;
-            d[c] = cen[3 * gi + c] + (rnd() - 0.5f) * 0.2f - o[c];
-        }
-        for (int c = 0; c < 3; ++c) { rays[8 * (size_t)i + c] = o[c]; rays[8 * (size_t)i + 4 + c] = d[c]; }
-        const uint32_t len = 1u + (uint32_t)(rnd() * 7.f) % 7u, first = (uint32_t)gi * 8u + (uint32_t)(rnd() * 8.f) % 8u;
-        const uint32_t k0 = std::min<uint32_t>(first, (uint32_t)groups * 8u - len);
-        leaves[2 * (size_t)i] = k0;
-        leaves[2 * (size_t)i + 1] = k0 + len;
-    }
-}
-
-// rt_device_selfcheck 4 over every device copy that exists (an error where there is none).
-int mat_selfcheck(uint64_t *mismatches) {
-#if RT_SHADE_GATHER
-    std::lock_guard<std::mutex> lk(g_live_mu);
-    if (g_live.empty()) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck 4: no scene is uploaded");
-    uint64_t total = 0;
-    for (rt_device_scene *ds : g_live) {
-        DeviceGuard guard(ds->device);
-        if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "rt_device_selfcheck 4: hipSetDevice failed");
-        unsigned long long *d = nullptr, h = 0;
-        HIP_TRY(hipMalloc((void **)&d, sizeof *d));
-        hipError_t e = hipMemset(d, 0, sizeof *d);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(mat_check_kernel, dim3(64), dim3(256), 0, nullptr, ds->ds, (unsigned long long)ds->n_texels, d);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
-        (void)hipFree(d);
-        if (e != hipSuccess) return rt_fail(RT_ERR_DEVICE, std::string("rt_device_selfcheck 4: ") + hipGetErrorString(e));
-        total += h;
-    }
-    *mismatches = total;
-    return RT_OK;
-#else
-    return rt_fail(RT_ERR_ARG, "rt_device_selfcheck 4: built without RT_SHADE_GATHER");
-#endif
-}
-// rt_device_selfcheck 5 over every device copy that exists (an error where there is none).
-template <int K, int POPS>
-void pop_check_launch(const DevScene &sc, int n_rays, int bound, unsigned long long *d) {
-    hipLaunchKernelGGL((pop_check_kernel<K, POPS>), dim3((unsigned)(n_rays / 256)), dim3(256), 0, nullptr, sc, n_rays, bound, d);
-}
-int pop_selfcheck(uint64_t *mismatches) {
-    std::lock_guard<std::mutex> lk(g_live_mu);
-    if (g_live.empty()) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck 5: no scene is uploaded");
-    uint64_t total = 0;
-    for (rt_device_scene *ds : g_live) {
-        DeviceGuard guard(ds->device);
-        if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "rt_device_selfcheck 5: hipSetDevice failed");
-        if (ds->ds.n_nodes < 1 || ds->ds.n_tris < 1) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck 5: empty scene");
-        const int n_rays = 16384;
-        const long long bound = 4ll * ((long long)ds->ds.n_nodes + ds->ds.n_tris) + 64;
-        if (bound > 0x7fffffffll) return rt_fail(RT_ERR_LIMIT, "rt_device_selfcheck 5: scene too large");
-        unsigned long long *d = nullptr, h = 0;
-        HIP_TRY(hipMalloc((void **)&d, sizeof *d));
-        hipError_t e = hipMemset(d, 0, sizeof *d);
-        if (e == hipSuccess) {
-            pop_check_launch<rtd::kLdsStack, 1>(ds->ds, n_rays, (int)bound, d);
-            pop_check_launch<rtd::kLdsStack, 2>(ds->ds, n_rays, (int)bound, d);
-            pop_check_launch<4, 1>(ds->ds, n_rays, (int)bound, d);   // (frames in scratch in most waves)
-            pop_check_launch<4, 2>(ds->ds, n_rays, (int)bound, d);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
-        (void)hipFree(d);
-        if (e != hipSuccess) return rt_fail(RT_ERR_DEVICE, std::string("rt_device_selfcheck 5: ") + hipGetErrorString(e));
-        total += h;
-    }
-    *mismatches = total;
-    return RT_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int rt_intersect_rays_via(rt_scene *s, int32_t path, int64_t n, const float *org, const float *dir, float *out_f,
-                          int64_t *out_i) {
-    if (!s || n < 0 || (n > 0 && (!org || !dir || !out_f || !out_i))) return rt_fail(RT_ERR_ARG, "rt_intersect_rays: bad argument");
-    if (path < 0 || path > 2) return rt_fail(RT_ERR_ARG, "rt_intersect_rays_via: unknown path " + std::to_string(path));
-    if (n == 0) return RT_OK;
-    int rc = ensure_device_scene(s, 0);
-    if (rc) return rc;
-    DeviceGuard guard(0);
-    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
-    const DevScene &sc = s->dev[0]->ds;
-    // (a walk visits every node and triangle at most once; the factor covers deferred steps)
-    const long long bound = 4ll * ((long long)sc.n_nodes + sc.n_tris) + 64, light_bound = 8ll * sc.n_lights + 64;
-    if (path != 0 && (sc.n_nodes < 1 || sc.n_tris < 1)) return rt_fail(RT_ERR_ARG, "rt_intersect_rays_via: empty scene");
-    if (bound > 0x7fffffffll || light_bound > 0x7fffffffll) return rt_fail(RT_ERR_LIMIT, "rt_intersect_rays_via: scene too large");
-    float *d_o = nullptr, *d_d = nullptr, *d_f = nullptr;
-    long long *d_i = nullptr;
-    const size_t v3 = (size_t)n * 3 * sizeof(float);
-    hipError_t e = hipMalloc(&d_o, v3);
-    if (e == hipSuccess) e = hipMalloc(&d_d, v3);
-    if (e == hipSuccess) e = hipMalloc(&d_f, (size_t)n * 4 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&d_i, (size_t)n * 6 * sizeof(long long));
-    if (e == hipSuccess) e = hipMemcpy(d_o, org, v3, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_d, dir, v3, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-        if (path == 0)
-            hipLaunchKernelGGL(rt_rays_kernel, grid, block, 0, nullptr, sc, (long long)n, d_o, d_d, d_f, d_i);
-        else if (path == 1)
-            hipLaunchKernelGGL(rt_rays_via_kernel<1>, grid, block, 0, nullptr, sc, (long long)n, (int)bound, (int)light_bound,
-                               d_o, d_d, d_f, d_i);
-        else
-            hipLaunchKernelGGL(rt_rays_via_kernel<2>, grid, block, 0, nullptr, sc, (long long)n, (int)bound, (int)light_bound,
-                               d_o, d_d, d_f, d_i);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out_f, d_f, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_i, d_i, (size_t)n * 6 * sizeof(long long), hipMemcpyDeviceToHost);
-    (void)hipFree(d_o);
-    (void)hipFree(d_d);
-    (void)hipFree(d_f);
-    (void)hipFree(d_i);
-    if (e != hipSuccess) return rt_fail(RT_ERR_DEVICE, std::string("rt_intersect_rays: ") + hipGetErrorString(e));
-    return RT_OK;
-}
-
-int rt_intersect_rays(rt_scene *s, int64_t n, const float *org, const float *dir, float *out_f, int64_t *out_i) {
-    return rt_intersect_rays_via(s, 0, n, org, dir, out_f, out_i);
-}
-
-int rt_device_selfcheck(int32_t which, uint64_t *mismatches) {
-    if (!mismatches) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck: null output");
-    if (which < 0 || which > 5) return rt_fail(RT_ERR_ARG, "rt_device_selfcheck: unknown check " + std::to_string(which));
-    if (which == 4) return mat_selfcheck(mismatches);
-    if (which == 5) return pop_selfcheck(mismatches);
-    unsigned long long *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, sizeof *d));
-    hipError_t e = hipMemset(d, 0, sizeof *d);
-    void *cbuf = nullptr;
-    if (e == hipSuccess) {
-        if (which == 0) {
-            hipLaunchKernelGGL(rcp_check_kernel, dim3(4096), dim3(256), 0, nullptr, d);
-        } else if (which == 1) {
-            hipLaunchKernelGGL(decode_check_kernel, dim3(4096), dim3(256), 0, nullptr, d);
-        } else if (which == 3) {
-            hipLaunchKernelGGL(far_check_kernel, dim3((1u << 24) / 256u), dim3(256), 0, nullptr, d);
-        } else {
-            const int n_cases = 1 << 16;
-            std::vector<float> tri, rays;
-            std::vector<uint32_t> leaves;
-            coop_cases(tri, rays, leaves, n_cases);
-            const size_t bt = tri.size() * 4 + 64, br = rays.size() * 4, bl = leaves.size() * 4, bn = 256;
-            e = hipMalloc(&cbuf, bt + br + bl + bn);
-            uint8_t *b = (uint8_t *)cbuf;
-            if (e == hipSuccess) e = hipMemset(cbuf, 0, bt + br + bl + bn);
-            if (e == hipSuccess) e = hipMemcpy(b, tri.data(), tri.size() * 4, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(b + bt, rays.data(), br, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(b + bt + br, leaves.data(), bl, hipMemcpyHostToDevice);
-            const int n_tris = (int)(tri.size() / 12);
-            const unsigned blocks = (unsigned)(n_cases / 256);
-            if (e == hipSuccess) {
-                for (int rm : {65, 1}) {   // one round per step; every leaf lane served in the step
-                    hipLaunchKernelGGL(coop_check_kernel<8>, dim3(blocks), dim3(256), 0, nullptr, (const float4 *)b,
-                                       n_tris, (const float4 *)(b + bt + br + bl), (const float4 *)(b + bt),
-                                       (const uint2 *)(b + bt + br), n_cases, rm, d);
-                    hipLaunchKernelGGL(coop_check_kernel<16>, dim3(blocks), dim3(256), 0, nullptr, (const float4 *)b,
-                                       n_tris, (const float4 *)(b + bt + br + bl), (const float4 *)(b + bt),
-                                       (const uint2 *)(b + bt + br), n_cases, rm, d);
-                }
-            }
-        }
-        if (e == hipSuccess) e = hipGetLastError();
-    }
-    unsigned long long h = 0;
-    if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof h, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (cbuf) (void)hipFree(cbuf);
-    if (e != hipSuccess) return rt_fail(RT_ERR_DEVICE, std::string("rt_device_selfcheck: ") + hipGetErrorString(e));
-    *mismatches = h;
-    return RT_OK;
-}
-
 int32_t rt_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -2082,3 +1514,5 @@ int rt_device_synchronize(void) {
 }
 
 }  // extern "C"
+
+#include "rt_check_device.h"   // rt_device_selfcheck, rt_intersect_rays[_via], rt_debug_*: kernels, host halves, entries

@@ -57,6 +57,23 @@ def test_rays_match_reference(scenes, gold, rays_in, path, source, order):
     gu.check_rays(rays_in, gold, out_f, out_i, f"path {path}, {source}, {order} order:")
 
 
+@pytest.fixture(scope="module")
+def whole(scenes, rays_in):
+    """The whole ray set through each path of the loader scene, once."""
+    return {path: scenes["loader"].intersect_rays(rays_in["origin"], rays_in["direction"], path=path) for path in (0, 1, 2)}
+
+
+@pytest.mark.parametrize("n", [1, 64, 257])
+@pytest.mark.parametrize("path", [0, 1, 2])
+def test_prefix_equals_whole_set(scenes, rays_in, whole, path, n):
+    """The first n rays alone give the first n rows of the whole set: a lone lane, one exactly
+    full wave, and a block boundary with one ray in the last block (the threads past n of paths 1
+    and 2 take ray 0 and must write nothing)."""
+    f, i = scenes["loader"].intersect_rays(rays_in["origin"][:n], rays_in["direction"][:n], path=path)
+    assert not (i[:, 0] == -2).any(), f"path {path}, n {n}: a ray reached the step bound"
+    assert rtref.same(f, whole[path][0][:n]).all() and np.array_equal(i, whole[path][1][:n])
+
+
 def test_unknown_path_is_refused(gpu, scenes, rays_in):
     with pytest.raises(gpu.RtError, match="unknown path"):
         scenes["loader"].intersect_rays(rays_in["origin"][:4], rays_in["direction"][:4], path=3)
