@@ -825,7 +825,8 @@ int rt_device_synchronize(void);
  * around the 1e9 constant; which 4: the material records of every uploaded scene against the
  * scene's own tables; which 5: whole closest-hit queries of 16,384 hashed rays on every
  * uploaded scene through the cooperative step (one and two frames popped per step; 12 and 4
- * stack frames in LDS) against the per-lane step loop (t, triangle, local
+ * stack frames in LDS; with every best frame and with none after a near subtree without a
+ * hit: eight launches) against the per-lane step loop (t, triangle, local
  * best, AABB and triangle counts; a query that does not end within 4 x (nodes + triangles) +
  * 64 steps is a mismatch); *mismatches = values (cases) that differ (0 = exact). */
 int rt_device_selfcheck(int32_t which, uint64_t *mismatches);

@@ -3,7 +3,7 @@
 // and the debug build's rt_debug_take / rt_debug_set_poison.  Included by rt_device.hip at its end, after
 // rt_temporal_device.h and the whole-frame path, so the build stays one translation unit: it needs DeviceGuard,
 // HIP_TRY, ensure_device_scene and g_live from there and the plain kernel's constants (kCoopLeavesPlain,
-// kCoopRoundMinPlain, kPlainFarDist2, RT_PLAIN_MAX_POPS) from rt_mega_device.h for the steps of rt_wavefront.h.
+// kCoopRoundMinPlain, kPlainFarDist2, kPlainAccElide, RT_PLAIN_MAX_POPS) from rt_mega_device.h for the steps of rt_wavefront.h.
 
 // HIP_TRY for these entries: the failure's text is the entry's prefix `who` and the error string.
 #define HIP_TRY_AS(who, expr) \
@@ -194,8 +194,9 @@ __global__ void __launch_bounds__(256) coop_check_kernel(const float4 *tri, int 
 }
 
 // rt_device_selfcheck 5: whole closest-hit queries on an uploaded scene through trav_step_coop (K
-// stack frames in LDS, at most POPS frames popped per step), against the per-lane trav_step loop
-// over an ArrayStack in scratch, in the same kernel: t, triangle, the local best and the AABB
+// stack frames in LDS, at most POPS frames popped per step, with every best frame or with none after a
+// near subtree without a hit: ELIDE), against the per-lane trav_step loop, which pushes every best
+// frame, over an ArrayStack in scratch, in the same kernel: t, triangle, the local best and the AABB
 // and triangle counts, bit for bit.  The waves hold the real mix of node, leaf and pop lanes
 // (the plain kernel's coop records, leaf rounds and leaf deferral); with K = 4 most waves hold
 // lanes whose frames are in scratch.  Ray i starts inside the root box with a direction uniform
@@ -214,26 +215,27 @@ __device__ __forceinline__ uint32_t query_root_bits(const rtd::NodeRec &root, co
     return rtd::box_hit<false>(root.mn, root.mx, r, e) ? 0u : 8u;
 }
 // trav_step_coop with the plain kernel's constants; every lane of the wave calls (valid or not).
-template <int POPS, class Stack>
+// ELIDE: no best frame after a near subtree without a hit (rt_wavefront.h trav_pop).
+template <int POPS, bool ELIDE, class Stack>
 __device__ __forceinline__ bool coop_query(const DevScene &sc, const rtd::NodeRec &root, const rtd::Ray &r, uint32_t bits,
                                            bool valid, int bound, rtd::TravStateU &T, Stack &S, Counters &cnt) {
     const rtd::GlobalNodes gn{sc.node};
     bool active = rtd::trav_start<true>(bits, root.a, root.b, T, cnt) && valid;
     int leaf_defer = 0;
     for (int it = 0; it < bound && __any(active); ++it)
-        if (rtd::trav_step_coop<true, kCoopLeavesPlain, false, rtd::kLeafDeferPlain, kPlainFarDist2, POPS>(
+        if (rtd::trav_step_coop<true, kCoopLeavesPlain, false, rtd::kLeafDeferPlain, kPlainFarDist2, POPS, ELIDE>(
                 sc, r, T, S, gn, cnt, active, kCoopRoundMinPlain, rtd::NoHook{}, &leaf_defer))
             active = false;
     return !active;
 }
-// the per-lane trav_step loop
-template <bool DIST2, class Stack>
+// the per-lane trav_step loop (ELIDE as above)
+template <bool DIST2, bool ELIDE, class Stack>
 __device__ __forceinline__ bool lane_query(const DevScene &sc, const rtd::NodeRec &root, const rtd::Ray &r, uint32_t bits,
                                            bool valid, int bound, rtd::TravState &T, Stack &S, Counters &cnt) {
     const rtd::GlobalNodes gn{sc.node};
     bool active = rtd::trav_start<true>(bits, root.a, root.b, T, cnt) && valid;
     for (int it = 0; it < bound && active; ++it)
-        if (rtd::trav_step<true, DIST2>(sc, r, T, S, gn, cnt)) active = false;
+        if (rtd::trav_step<true, DIST2, ELIDE>(sc, r, T, S, gn, cnt)) active = false;
     return !active;
 }
 // ManyLightsDistribution::pdf(r.o, r.d) as the light-split kernel walks it (rt_mega.h
@@ -255,7 +257,7 @@ __device__ __forceinline__ bool light_query(const DevScene &sc, const rtd::Ray &
     return !active;
 }
 
-template <int K, int POPS>
+template <int K, int POPS, bool ELIDE>
 __global__ void __launch_bounds__(256) pop_check_kernel(DevScene sc, int n_rays, int bound, unsigned long long *bad) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     const int lane = (int)(threadIdx.x & 63);
@@ -273,13 +275,13 @@ __global__ void __launch_bounds__(256) pop_check_kernel(DevScene sc, int n_rays,
     Counters cnt{0, 0, 0, 0, 0, 0, 0};
     uint2 spill[rtd::kStack - K];
     rtd::LdsStackT<K> S{spill};
-    const bool active = !coop_query<POPS>(sc, root, r, 0u, valid, bound, T, S, cnt);
-    // the per-lane query
+    const bool active = !coop_query<POPS, ELIDE>(sc, root, r, 0u, valid, bound, T, S, cnt);
+    // the per-lane query, with every best frame
     rtd::TravState T2;
     Counters cnt2{0, 0, 0, 0, 0, 0, 0};
     uint2 frames[rtd::kStack];
     rtd::ArrayStack S2{frames};
-    const bool active2 = !lane_query<kPlainFarDist2>(sc, root, r, 0u, valid, bound, T2, S2, cnt2);
+    const bool active2 = !lane_query<kPlainFarDist2, false>(sc, root, r, 0u, valid, bound, T2, S2, cnt2);
     unsigned long long local = 0;
     if (valid)
         local = (active | active2 | (T.best.prim != T2.best.prim) | (__float_as_uint(T.best.t) != __float_as_uint(T2.best.t)) |
@@ -345,14 +347,14 @@ __global__ void __launch_bounds__(256) rt_rays_via_kernel(DevScene sc, long long
         uint2 frames[rtd::kStack];
         rtd::ArrayStack S{frames};
         rtd::TravState T;
-        done = lane_query<RT_SPEC_FAR_DIST2 != 0>(sc, root, r, bits, valid, bound, T, S, c1);
+        done = lane_query<RT_SPEC_FAR_DIST2 != 0, RT_SPEC_ACC_ELIDE != 0>(sc, root, r, bits, valid, bound, T, S, c1);
         h = T.best;
         if (sc.n_lights) light_done = light_query(sc, r, valid, light_bound, S, c2, lp);
     } else {
         uint2 spill[rtd::kStack - 4];
         rtd::LdsStackT<4> S{spill};
         rtd::TravStateU T;
-        done = coop_query<RT_PLAIN_MAX_POPS>(sc, root, r, bits, valid, bound, T, S, c1);
+        done = coop_query<RT_PLAIN_MAX_POPS, kPlainAccElide>(sc, root, r, bits, valid, bound, T, S, c1);
         h = T.best;
         if (rtd::kUvRecompute && valid && h.prim >= 0) rtd::hit_uv(sc, r, h);
         if (sc.n_lights) light_done = light_query(sc, r, valid, light_bound, S, c2, lp);
@@ -510,8 +512,11 @@ int pop_selfcheck(uint64_t *mismatches) {
         const long long bound = 4ll * ((long long)ds.ds.n_nodes + ds.ds.n_tris) + 64;
         if (bound > 0x7fffffffll) return rt_fail(RT_ERR_LIMIT, "rt_device_selfcheck 5: scene too large");
         if (int rc = c.make()) return rc;
-        for (auto kernel : {pop_check_kernel<rtd::kLdsStack, 1>, pop_check_kernel<rtd::kLdsStack, 2>,
-                            pop_check_kernel<4, 1>, pop_check_kernel<4, 2>})   // (4: frames in scratch in most waves)
+        // (4: frames in scratch in most waves; both frame rules, rt_wavefront.h trav_pop ELIDE)
+        for (auto kernel : {pop_check_kernel<rtd::kLdsStack, 1, false>, pop_check_kernel<rtd::kLdsStack, 2, false>,
+                            pop_check_kernel<4, 1, false>, pop_check_kernel<4, 2, false>,
+                            pop_check_kernel<rtd::kLdsStack, 1, true>, pop_check_kernel<rtd::kLdsStack, 2, true>,
+                            pop_check_kernel<4, 1, true>, pop_check_kernel<4, 2, true>})
             hipLaunchKernelGGL(kernel, dim3((unsigned)(n_rays / 256)), dim3(256), 0, nullptr, ds.ds, n_rays, (int)bound, c.d);
         return RT_OK;
     });

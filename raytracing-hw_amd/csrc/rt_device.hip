@@ -458,7 +458,8 @@ __global__ void __launch_bounds__(256) wf_extend_kernel(DevScene sc, const float
                 }
             }
         }
-        if (busy && rtd::trav_step<COUNT>(sc, r, T, S, nodes, cnt)) {
+        // (every best frame, as before RT_ACC_ELIDE: this kernel was not measured with it)
+        if (busy && rtd::trav_step<COUNT, rtd::kFarDist2, false>(sc, r, T, S, nodes, cnt)) {
             rtd::store_hit(hits, q, T.best);
             busy = false;
         }

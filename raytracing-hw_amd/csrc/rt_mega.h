@@ -678,6 +678,14 @@ __device__ __forceinline__ void mega_shade_split(ML &L, const DevScene &sc, cons
 
 // One iteration of a wave's main loop for one lane, given the wave's decision: shade the
 // READY lanes this iteration (shade_now), or step the traversing lanes.
+// The per-lane step here is the light-split kernels' on the device (the others step in
+// rt_mega_device.h's coop loop) and the host emulation's.  The light-split kernels were not
+// measured with RT_ACC_ELIDE (rt_wavefront.h), so it pushes every best frame; 1 is for the host
+// test that runs the emulation in both forms (tests/test_acc_elide.py).
+#ifndef RT_LANE_ACC_ELIDE
+#define RT_LANE_ACC_ELIDE 0
+#endif
+constexpr bool kLaneAccElide = RT_LANE_ACC_ELIDE != 0;
 template <bool COUNT, class Stack, class Nodes, bool FAST = false, bool LSPLIT = false, bool CHAIN = false,
           int G = SHADE_TABLES, bool MOM = false, class ML>
 __device__ __forceinline__ void mega_iterate(ML &L, bool shade_now, const DevScene &sc, const ShardGeom &g,
@@ -700,7 +708,7 @@ __device__ __forceinline__ void mega_iterate(ML &L, bool shade_now, const DevSce
         if (L.state == M_READY)
             mega_shade<COUNT, FAST, CHAIN, G, MOM>(L, sc, g, st, spp, out, cost, root, stk, cnt, tail, park, queue);
     } else if (L.state == M_TRAV) {
-        if (trav_step<COUNT>(sc, L.r, L.T, stk, nodes, cnt)) L.state = M_READY;
+        if (trav_step<COUNT, kFarDist2, kLaneAccElide>(sc, L.r, L.T, stk, nodes, cnt)) L.state = M_READY;
     }
 }
 

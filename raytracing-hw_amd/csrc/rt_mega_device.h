@@ -114,6 +114,21 @@ constexpr bool kPlainFarDist2 = RT_PLAIN_FAR_DIST2 != 0;
 #ifndef RT_SPEC_MAX_POPS
 #define RT_SPEC_MAX_POPS 2
 #endif
+// No best frame when the near subtree found no hit (rt_wavefront.h RT_ACC_ELIDE, trav_pop ELIDE), per
+// kernel and by the rule above.  One call each, three interleaved rounds against the form without it
+// (profiles/accelide_ab.jsonl, accelide_spec_ab.jsonl):
+//   plain kernel, 1-GPU frame      915.9-920.9 ms against 965.4-966.8 (-47.3 ms, spread 5.0);
+//   runahead kernel, 8-way shards  slowest 167.7-168.2 against 174.7-175.0 ms (-6.9 ms, spread 0.5), mean
+//                                  166.5-166.7 against 173.2-173.4, three renders per shard.
+// Both take it.  The counting, fast-mode, light-split and accumulator (CHAIN, plain and runahead)
+// instantiations and the wavefront kernel were not measured and push every best frame.
+#ifndef RT_PLAIN_ACC_ELIDE
+#define RT_PLAIN_ACC_ELIDE RT_ACC_ELIDE
+#endif
+#ifndef RT_SPEC_ACC_ELIDE
+#define RT_SPEC_ACC_ELIDE RT_ACC_ELIDE
+#endif
+constexpr bool kPlainAccElide = RT_PLAIN_ACC_ELIDE != 0;
 // Leaf rounds per coop step (rt_wavefront.h trav_step_coop round_min): a further round
 // while at least this many leaf lanes are unserved.  Plain kernel: 8 (sponza 1080p 1292 ->
 // 1278 ms against one round per step).  The runahead kernel's depends on the scene
@@ -148,7 +163,8 @@ struct MegaCfg {
     static constexpr int leaf_defer = spec ? rtd::kLeafDefer : COUNT ? 0 : rtd::kLeafDeferPlain;
     static constexpr bool far_dist2 = spec ? RT_SPEC_FAR_DIST2 != 0 : kPlainFarDist2;
     static constexpr int max_pops = spec ? RT_SPEC_MAX_POPS : COUNT ? rtd::kMaxPops : RT_PLAIN_MAX_POPS;
-    static constexpr int coop_round_min = kCoopRoundMinPlain;   // (the runahead kernel's comes with the launch: st.round_min)
+    static constexpr bool acc_elide = !CHAIN && (spec ? RT_SPEC_ACC_ELIDE != 0 : plain && kPlainAccElide);
+    static constexpr int coop_round_min = kCoopRoundMinPlain;  // (the runahead kernel's comes with the launch: st.round_min)
     static constexpr bool pack_trav = kPackTrav && !LSPLIT && !spec && !FAST;   // RT_PACK_TRAV through its shading pass
 };
 
@@ -239,7 +255,8 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
     unsigned long long pf[7] = {0, 0, 0, 0, 0, 0, 0};
     if (threadIdx.x < 8) rt_prof_lds[threadIdx.x] = 0;
     if (threadIdx.x < 16) rtd::spec_prof_lds[threadIdx.x] = 0;
-    if (threadIdx.x < 4 * rtd::kPopProfN) rtd::pop_prof_lds[threadIdx.x / rtd::kPopProfN][threadIdx.x % rtd::kPopProfN] = 0;
+    if (threadIdx.x < 4 * rtd::kPopProfLds) rtd::pop_prof_lds[threadIdx.x / rtd::kPopProfLds][threadIdx.x % rtd::kPopProfLds] = 0;
+    if (threadIdx.x < 4) rtd::pop_best_lds[threadIdx.x] = 0;
     if ((threadIdx.x & 63) == 0) rtd::spec_wave_t0_lds[threadIdx.x >> 6] = wall_clock64();
     __syncthreads();
     long long tp = clock64();
@@ -423,7 +440,8 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
             int kt = nt;
             int leaf_defer = 0;   // (the runahead kernel's leaf steps deferred in a row: rt_wavefront.h RT_LEAF_DEFER)
             do {
-                if (rtd::trav_step_coop<COUNT, V::coop_leaves, V::mask_load, V::leaf_defer, V::far_dist2, V::max_pops>(
+                if (rtd::trav_step_coop<COUNT, V::coop_leaves, V::mask_load, V::leaf_defer, V::far_dist2, V::max_pops,
+                                         V::acc_elide>(
                         sc, L.r, L.T, S, nodes, cnt, L.state == rtd::M_TRAV, V::spec ? st.round_min : V::coop_round_min,
                         rtd::NoHook{}, &leaf_defer))
                     L.state = rtd::M_READY;
@@ -493,7 +511,8 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
     __syncthreads();
     if (threadIdx.x < 8) atomicAdd(&g_mega_seg[threadIdx.x], rt_prof_lds[threadIdx.x]);
     if (threadIdx.x < 16) atomicAdd(&rtd::g_spec_prof[threadIdx.x], rtd::spec_prof_lds[threadIdx.x]);
-    if (threadIdx.x < rtd::kPopProfN)
+    if (threadIdx.x < 4) atomicAdd(&rtd::g_pop_prof[rtd::kPopProfLds + threadIdx.x], (unsigned long long)rtd::pop_best_lds[threadIdx.x]);
+    if (threadIdx.x < rtd::kPopProfLds)
         atomicAdd(&rtd::g_pop_prof[threadIdx.x], rtd::pop_prof_lds[0][threadIdx.x] + rtd::pop_prof_lds[1][threadIdx.x] +
                                                      rtd::pop_prof_lds[2][threadIdx.x] + rtd::pop_prof_lds[3][threadIdx.x]);
 #endif

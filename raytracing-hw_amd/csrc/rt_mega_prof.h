@@ -145,6 +145,13 @@ int mega_prof_report(hipStream_t stream, bool count, long long n_pixels, const i
         std::fprintf(stderr, "[mega pop] steps with a pop by popping lanes (1-4, 5-8, ..., 61-64):");
         for (int b = 0; b < 16; ++b) std::fprintf(stderr, " %.4f", pp[4] ? (double)pp[8 + b] / pp[4] : 0.0);
         std::fprintf(stderr, "\n");
+        // best frames (rt_wavefront.h trav_pop ELIDE): a far child that survives pushes one unless its near best
+        // is 1e9 and the kernel elides those; a popped one is a merge, carried over when its lane entered the step popping
+        // (counted in wave 0 of every block: per coop step of those waves)
+        const double ss = pp[7] ? (double)pp[7] : 1.0;
+        std::fprintf(stderr, "[mega pop] best frames, wave 0 of each block: far children entered after a near subtree/step=%.3f "
+                     "with near best 1e9=%.4f | best frames popped/step=%.3f carried over=%.4f\n",
+                     pp[24] / ss, pp[24] ? (double)pp[25] / pp[24] : 0.0, pp[26] / ss, pp[26] ? (double)pp[27] / pp[26] : 0.0);
     }
     // wave finish times relative to the first wave start: percentiles (ms)
     unsigned nw = 0;

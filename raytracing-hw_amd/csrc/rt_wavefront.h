@@ -125,9 +125,12 @@ __device__ __forceinline__ void counters_flush(const Counters &c, unsigned long 
 //       far frame  (a << 10 | b, entry distance)  pushed when both children are hit
 //                                                  (the distance squared: RT_FAR_DIST2 below);
 //       best frame (kFrameAcc,  node's near best)  pushed when the far child is entered
-//                                                  after a near subtree.
-//     No frame is needed when a node has only one child to visit: its local best starts at
-//     1e9, so merging it is the identity.
+//                                                  after a near subtree that found a hit.
+//     A best frame is merged as min(far subtree's best, near best).  Every local best starts
+//     at 1e9 and is only lowered (a strict < against a hit's t, which a NaN or infinite t
+//     never passes, or that min), so it never exceeds 1e9 and merging 1e9 is the identity.
+//     Hence no frame is needed when a node has only one child to visit, nor when the near
+//     subtree found no hit (its best is still 1e9: RT_ACC_ELIDE below, trav_pop ELIDE).
 constexpr uint32_t kFrameMaxA = (1u << 22) - 1;
 constexpr uint32_t kFrameAcc = 0xffffffffu;
 
@@ -498,8 +501,30 @@ constexpr int kMaxPops = RT_MAX_POPS;
 // costs one conversion and one f64 compare in place of the f32 compare.
 // MAXP: the cap for this caller (the lane-resident kernels' coop step passes its kernel's own,
 // rt_device.hip RT_PLAIN_MAX_POPS / RT_SPEC_MAX_POPS).
-template <bool DIST2 = kFarDist2, int MAXP = kMaxPops, class Stack, class TS>
-__device__ __forceinline__ bool trav_pop(TS &T, Stack &stk) {
+// ELIDE: a far child that survives pushes the node's best frame only if the near subtree found
+// a hit (acc != 1e9f).  A frame holding 1e9 merges as the identity (acc <= 1e9 always: the
+// frame description above), yet it cost an LDS write, an LDS read and, under a cap of MAXP
+// frames, one more step of its lane in a pop chain.  Same visits, tests, counters and bits; a
+// lane only reaches its next far child a step sooner.  The test is a per-lane compare around
+// the stack write; nothing wave-uniform is held for it.  RT_ACC_ELIDE=0 is the A/B baseline:
+// every kernel's code is then what it was.  The lane-resident kernels pass their own
+// (rt_mega_device.h MegaCfg::acc_elide).
+#ifndef RT_ACC_ELIDE
+#define RT_ACC_ELIDE 1
+#endif
+constexpr bool kAccElide = RT_ACC_ELIDE != 0;
+// Diagnostics build (RT_MEGA_PROF): trav_pop notes what it did with best frames, for the coop
+// step's pop_prof_step below.  Bit 0: a far child survived (a best frame pushed, or elided),
+// bit 1: the near best was 1e9 there, bits 2-3: best frames popped.
+#if defined(RT_MEGA_PROF) && defined(__HIPCC__)
+#define RT_POP_PROF_ARG , uint32_t *prof_note = nullptr
+#define RT_POP_PROF_NOTE(bits) do { if (prof_note) *prof_note += (bits); } while (0)
+#else
+#define RT_POP_PROF_ARG
+#define RT_POP_PROF_NOTE(bits) ((void)0)
+#endif
+template <bool DIST2 = kFarDist2, int MAXP = kMaxPops, bool ELIDE = kAccElide, class Stack, class TS>
+__device__ __forceinline__ bool trav_pop(TS &T, Stack &stk RT_POP_PROF_ARG) {
     float acc = T.acc;
     int sp = T.sp;
     double thr = DIST2 ? far_thr(acc) : 0.0;
@@ -519,14 +544,19 @@ __device__ __forceinline__ bool trav_pop(TS &T, Stack &stk) {
             const float p = __uint_as_float(f.y);
             acc = acc < p ? acc : p;
             if (DIST2) thr = far_thr(acc);
+            RT_POP_PROF_NOTE(4u);
             continue;
         }
         const float e = __uint_as_float(f.y);
         if (!(DIST2 ? far_gt_thr(e, thr) : e > acc)) {   // far child survives the near subtree's best
-            stk.put(sp++, make_uint2(kFrameAcc, __float_as_uint(acc)));
+            if (!ELIDE || acc != 1e9f) {
+                stk.put(sp++, make_uint2(kFrameAcc, __float_as_uint(acc)));
 #ifdef RT_STACK_PROBE
-            RT_STACK_PROBE(sp);
+                RT_STACK_PROBE(sp);
 #endif
+            }
+            RT_CHECK(acc <= 1e9f, 18, __float_as_uint(acc), (void)0);   // (what the elided merge relies on)
+            RT_POP_PROF_NOTE(acc == 1e9f ? 3u : 1u);
             T.sp = sp;
             T.acc = 1e9f;
             trav_enter(T, f.x >> 10, f.x & 1023u);
@@ -580,7 +610,7 @@ __device__ __forceinline__ void node_step(const float4 q[4], const Ray &r, TS &T
 // Both memory reads of the step issue before either test (node lanes and leaf lanes load
 // through the same registers), so a wave split between node and leaf steps waits for one
 // round trip per iteration, not two.
-template <bool COUNT, bool DIST2 = kFarDist2, class Stack, class Nodes, class TS>
+template <bool COUNT, bool DIST2 = kFarDist2, bool ELIDE = kAccElide, class Stack, class Nodes, class TS>
 __device__ __forceinline__ bool trav_step(const DevScene &sc, const Ray &r, TS &T, Stack &stk,
                                           const Nodes &nodes, Counters &cnt) {
     constexpr int N = RT_LEAF_N;
@@ -624,7 +654,7 @@ __device__ __forceinline__ bool trav_step(const DevScene &sc, const Ray &r, TS &
         T.k = k + N;
         if (T.k >= T.kend) T.phase = TP_POP;
     }
-    if (T.phase == TP_POP) return trav_pop<DIST2>(T, stk);
+    if (T.phase == TP_POP) return trav_pop<DIST2, kMaxPops, ELIDE>(T, stk);
     return false;
 }
 
@@ -787,16 +817,35 @@ constexpr int kLeafDeferPlain = RT_PLAIN_LEAF_DEFER;
 // Diagnostics build (RT_MEGA_PROF): what the pop block costs and for how many lanes it runs,
 // per wave in LDS (lane 0 adds), summed into g_pop_prof at the kernel's end.
 // [0] coop steps [1]-[3] lanes at TP_NODE / TP_LEAF / TP_POP when the step ends [4] steps in
-// which trav_pop runs [5] lanes it runs for [6] its clock64 cycles [7] unused
-// [8]-[23] steps by popping lanes: 1-4, 5-8, ..., 61-64
-constexpr int kPopProfN = 24;
+// which trav_pop runs [5] lanes it runs for [6] its clock64 cycles [7] coop steps of the sampled waves
+// [8]-[23] steps by popping lanes: 1-4, 5-8, ..., 61-64.
+// Best frames, counted in wave 0 of every block only (four u32 in LDS: the plain kernel's block has
+// no room for more and must keep its blocks per CU): [24] far children that survive the cull (each
+// pushes a best frame unless trav_pop elides it) [25] of them, those whose near best is 1e9
+// [26] best frames popped [27] of them, by lanes that entered the step in TP_POP (carried over).
+constexpr int kPopProfLds = 24, kPopProfN = 28;
 #if defined(RT_MEGA_PROF) && defined(__HIPCC__)
 __device__ unsigned long long g_pop_prof[kPopProfN];
-__shared__ unsigned long long pop_prof_lds[4][kPopProfN];
-// One coop step's line of the pop profile (every lane calls; `trav`: still traversing).
-__device__ __forceinline__ void pop_prof_step(bool trav, int phase, int n_pop, long long cyc) {
+__shared__ unsigned long long pop_prof_lds[4][kPopProfLds];
+__shared__ uint32_t pop_best_lds[4];
+// One coop step's line of the pop profile (every lane calls; `trav`: still traversing; `note`:
+// trav_pop's, `carried`: the lane entered the step in TP_POP).
+__device__ __forceinline__ void pop_prof_step(bool trav, int phase, int n_pop, long long cyc, uint32_t note, bool carried) {
     const int nn = __popcll(__ballot(trav && phase == TP_NODE)), nl = __popcll(__ballot(trav && phase == TP_LEAF)),
               np = __popcll(__ballot(trav && phase == TP_POP));
+    if (threadIdx.x < 64) {   // (MAXP <= 2 in the lane-resident kernels: a lane pops 0, 1 or 2 best frames)
+        const uint32_t popped = (note >> 2) & 3u;
+        const int n_far = __popcll(__ballot((note & 1u) != 0)), n_far9 = __popcll(__ballot((note & 2u) != 0));
+        const int n_best = __popcll(__ballot(popped >= 1u)) + __popcll(__ballot(popped >= 2u));
+        const int n_best_c = __popcll(__ballot(popped >= 1u && carried)) + __popcll(__ballot(popped >= 2u && carried));
+        if (threadIdx.x == 0) {
+            pop_prof_lds[0][7] += 1;
+            pop_best_lds[0] += (uint32_t)n_far;
+            pop_best_lds[1] += (uint32_t)n_far9;
+            pop_best_lds[2] += (uint32_t)n_best;
+            pop_best_lds[3] += (uint32_t)n_best_c;
+        }
+    }
     if ((threadIdx.x & 63) == 0) {
         unsigned long long *c = pop_prof_lds[threadIdx.x >> 6];
         c[0] += 1;
@@ -813,24 +862,25 @@ __device__ __forceinline__ void pop_prof_step(bool trav, int phase, int n_pop, l
 }
 #endif
 // The coop step's tail: the node lanes' pair test, then the return up the stack (POPS frames at most).
-template <bool COUNT, bool DIST2, int POPS, class Stack, class TS>
+template <bool COUNT, bool DIST2, int POPS, bool ELIDE, class Stack, class TS>
 __device__ __forceinline__ bool coop_tail(bool at_node, bool active, const float4 q[4], const Ray &r, TS &T, Stack &stk,
-                                          Counters &cnt) {
+                                          Counters &cnt, bool carried = false) {
     if (at_node) node_step<COUNT, DIST2>(q, r, T, stk, cnt);
 #if defined(RT_MEGA_PROF)
     const unsigned long long pm = __ballot(active && T.phase == TP_POP);
     const long long pc0 = clock64();
     bool done = false;
-    if (active && T.phase == TP_POP) done = trav_pop<DIST2, POPS>(T, stk);
-    pop_prof_step(active && !done, T.phase, __popcll(pm), pm ? clock64() - pc0 : 0);
+    uint32_t note = 0;
+    if (active && T.phase == TP_POP) done = trav_pop<DIST2, POPS, ELIDE>(T, stk, &note);
+    pop_prof_step(active && !done, T.phase, __popcll(pm), pm ? clock64() - pc0 : 0, note, carried);
     return done;
 #else
-    if (active && T.phase == TP_POP) return trav_pop<DIST2, POPS>(T, stk);
+    if (active && T.phase == TP_POP) return trav_pop<DIST2, POPS, ELIDE>(T, stk);
     return false;
 #endif
 }
 template <bool COUNT, int kCoopLeaves, bool MASK_LOAD, int DEFER = kLeafDefer, bool DIST2 = kFarDist2,
-          int POPS = kMaxPops, class Stack, class Nodes, class TS, class Hook = NoHook>
+          int POPS = kMaxPops, bool ELIDE = kAccElide, class Stack, class Nodes, class TS, class Hook = NoHook>
 __device__ __forceinline__ bool trav_step_coop(const DevScene &sc, const Ray &r, TS &T, Stack &stk,
                                                const Nodes &nodes, Counters &cnt, bool active, int round_min,
                                                const Hook &hook = Hook{}, int *leaf_defer = nullptr) {
@@ -930,7 +980,8 @@ __device__ __forceinline__ bool trav_step_coop(const DevScene &sc, const Ray &r,
         }
     }
     hook();
-    return coop_tail<COUNT, DIST2, POPS>(at_node, active, q, r, T, stk, cnt);
+    // (the last argument is read by the diagnostics build only: a lane whose pop was carried over)
+    return coop_tail<COUNT, DIST2, POPS, ELIDE>(at_node, active, q, r, T, stk, cnt, active && !at_node && !at_leaf);
 }
 
 #endif
@@ -948,7 +999,7 @@ __device__ __forceinline__ void closest_hit_wf(const DevScene &sc, const float4 
     ArrayStack S{stk};
     const GlobalNodes nodes{sc.node};
     if (trav_start<COUNT>(bits, root.a, root.b, T, cnt))
-        while (!trav_step<COUNT>(sc, r, T, S, nodes, cnt)) {
+        while (!trav_step<COUNT, kFarDist2, false>(sc, r, T, S, nodes, cnt)) {   // (as the wavefront kernel: every best frame)
         }
     best = T.best;
 }
