@@ -147,6 +147,16 @@ template <class ML>
 __device__ __forceinline__ void lane_rng_set(ML &L, const Rng &r) { L.rng = r; }
 #endif
 
+// The lane's RNG as shade_pre reaches it under CONV_RNG (rt_path.h rng_load / rng_store).
+template <class ML>
+struct LaneRngSlot {
+    ML &L;
+};
+template <class ML>
+__device__ __forceinline__ Rng rng_load(const LaneRngSlot<ML> &s) { return lane_rng(s.L); }
+template <class ML>
+__device__ __forceinline__ void rng_store(LaneRngSlot<ML> &s, const Rng &v) { lane_rng_set(s.L, v); }
+
 // The lane's sample counter, depth budget and recorded-vertex count, packed in one register
 // (samples < 2^20, ray_depth <= 15, vertices <= 16: checked by the host) so the loop state
 // that stays live through the shading code is two registers smaller.
@@ -172,8 +182,9 @@ __device__ __forceinline__ void mega_begin(ML &L, const NodeRec &root, Counters 
 }
 
 // Next sample of the lane's pixel: jittered camera ray (scene.cpp:36-39).  Fast mode: the
-// sample's own Philox-seeded stream (rt_path.h fast_sample_seed).
-template <bool COUNT, bool FAST = false, class ML>
+// sample's own Philox-seeded stream (rt_path.h fast_sample_seed).  RAW: L.r gets the camera ray's
+// origin and direction only, and the caller starts it (mega_shade's common ray start).
+template <bool COUNT, bool FAST = false, bool RAW = false, class ML>
 __device__ __forceinline__ void mega_sample(ML &L, const DevScene &sc, const ShardGeom &g, const NodeRec &root,
                                             Counters &cnt) {
     LaneCtr c = lane_ctr(L);
@@ -184,12 +195,12 @@ __device__ __forceinline__ void mega_sample(ML &L, const DevScene &sc, const Sha
         const float ox = rng_offset(rng);
         const float oy = rng_offset(rng);
         c.power = sc.ray_depth - 1;
-        L.r = camera_ray(sc, px, py, ox, oy);
+        L.r = camera_ray<RAW>(sc, px, py, ox, oy);
     }
     lane_rng_set(L, rng);
     c.nv = 0;
     lane_ctr_set(L, c);
-    mega_begin<COUNT>(L, root, cnt);
+    if constexpr (!RAW) mega_begin<COUNT>(L, root, cnt);
 }
 
 // A parked pixel: (pixel, next sample, start state of that sample, sum so far)
@@ -454,11 +465,15 @@ __device__ void spec_job_end(ML &L, const DevScene &sc, const ShardGeom &g, cons
 // (rt_device.hip RT_PLAIN_SHADE_GATHER, RT_SPEC_SHADE_GATHER).
 // `MOM` (FAST only, a moments pass): the sample's squared colour is added to the unit's second
 // partial (L.sum2), written at the unit's end to the squares' part of the partial buffer.
-template <bool COUNT, bool FAST = false, bool CHAIN = false, int G = SHADE_TABLES, bool MOM = false, class Stack, class ML>
+// `CV`: which parts of RT_SHADE_CONVERGE the pass has (rt_path.h CONV_START, CONV_RNG), per
+// kernel too (rt_mega_device.h MegaCfg::converge).
+template <bool COUNT, bool FAST = false, bool CHAIN = false, int G = SHADE_TABLES, bool MOM = false, int CV = 0,
+          class Stack, class ML>
 __device__ __forceinline__ void mega_shade(ML &L, const DevScene &sc, const ShardGeom &g, const WfState &st,
                                            int spp, float *out, unsigned *cost, const NodeRec &root, Stack &stk,
                                            Counters &cnt, bool tail = false, bool park = false,
                                            const unsigned long long *queue = nullptr) {
+    RT_PROF_BEGIN
     LaneRec P{st.rec_ab, st.rec_c, mega_slot_of(L), st.lanes, V3{0.f, 0.f, 0.f}, 0, false};
     Hit h = L.T.best;
     LaneCtr c = lane_ctr(L);
@@ -488,9 +503,17 @@ __device__ __forceinline__ void mega_shade(ML &L, const DevScene &sc, const Shar
             }
 #endif
         }
-        Rng rng = lane_rng(L);
-        const bool cont = shade_hit<COUNT, G>(sc, L.r, h, rng, cnt, P, c.nv, stk, r1p);   // (stack free: T.sp == 0)
-        lane_rng_set(L, rng);
+        bool cont;
+        if constexpr ((CV & CONV_RNG) != 0) {
+            LaneRngSlot<ML> slot{L};
+            RT_PROF_SEG(6);   // (round-1 loads, (u, v) recompute)
+            cont = shade_hit<COUNT, G, CV>(sc, L.r, h, slot, cnt, P, c.nv, stk, r1p);
+        } else {
+            Rng rng = lane_rng(L);
+            RT_PROF_SEG(6);
+            cont = shade_hit<COUNT, G, CV>(sc, L.r, h, rng, cnt, P, c.nv, stk, r1p);   // (stack free: T.sp == 0)
+            lane_rng_set(L, rng);
+        }
         if (cont && c.power > 0) {
             c.power -= 1;
             next = true;
@@ -500,50 +523,62 @@ __device__ __forceinline__ void mega_shade(ML &L, const DevScene &sc, const Shar
     // vertex shaded here folds from its emission in registers.  Fast mode writes it and folds
     // from memory: keeping it live there made that instantiation spill 31 VGPRs instead of 22.)
     if constexpr (FAST) P.flush_e();
+    RT_PROF_MARK();   // (segment 7: fold, sum, restart, ray start)
+    // CONV_START: the bounce and the next sample leave L.r's origin and direction as computed and
+    // meet at the pass's one ray start (the end of this function); every other end returns.
+    constexpr bool kOneStart = (CV & CONV_START) != 0;
     if (next) {
         lane_ctr_set(L, c);
-        mega_begin<COUNT>(L, root, cnt);
-        return;
-    }
-    if (!COUNT && !FAST && tail) {   // runahead job: colour of sample c.s, end state in the RNG slot
-        spec_job_end<CHAIN>(L, sc, g, st, spp, out, root, fold_path(P, c.nv, shaded), c, queue);
-        return;
-    }
-    V3 sm;
-    if constexpr (MOM) {   // (q = x * x, one multiply per channel; both partials in sample order)
-        const V3 x = fold_path(P, c.nv, !FAST && shaded);
-        sm = rtv::add(lane_sum(L), x);
-        L.sum2 = rtv::add(L.sum2, rtv::mulv(x, x));
-    } else {
-        sm = rtv::add(lane_sum(L), fold_path(P, c.nv, !FAST && shaded));
-    }
-    lane_sum_set(L, sm);
-    if (++c.s == (FAST ? L.send : spp)) {
-        const long long o = FAST ? L.dst : L.pix;
-        out[3 * o + 0] = sm.x;
-        out[3 * o + 1] = sm.y;
-        out[3 * o + 2] = sm.z;
-        if constexpr (MOM) {   // (the squares' part of the partial buffer: its address in the queue block)
-            float *out2 = (float *)queue[kMomentPartWord];
-            out2[3 * o + 0] = L.sum2.x;
-            out2[3 * o + 1] = L.sum2.y;
-            out2[3 * o + 2] = L.sum2.z;
+        if constexpr (!kOneStart) {
+            mega_begin<COUNT>(L, root, cnt);
+            return;
         }
-        if (COUNT && cost) cost[L.pix] = (unsigned)(cnt.aabb + cnt.tri + cnt.laabb + cnt.ltri - L.work0);
-        // (accumulator: the record of the pixel's next pass; the lane's RNG is at the state its
-        // last sample ended in)
-        if constexpr (CHAIN && !FAST) chain_store(chain_of(queue), (uint32_t)L.pix, (uint32_t)c.s, lane_rng(L), sm);
-        L.pix = -1;
-        L.state = M_IDLE;
-        return;
     }
-    if (!COUNT && !FAST && park) {   // (idle, still holding its pixel: the kernel's loop parks it)
+    if (!next) {
+        if (!COUNT && !FAST && tail) {   // runahead job: colour of sample c.s, end state in the RNG slot
+            spec_job_end<CHAIN>(L, sc, g, st, spp, out, root, fold_path(P, c.nv, shaded), c, queue);
+            return;
+        }
+        V3 sm;
+        if constexpr (MOM) {   // (q = x * x, one multiply per channel; both partials in sample order)
+            const V3 x = fold_path(P, c.nv, !FAST && shaded);
+            sm = rtv::add(lane_sum(L), x);
+            L.sum2 = rtv::add(L.sum2, rtv::mulv(x, x));
+        } else {
+            sm = rtv::add(lane_sum(L), fold_path(P, c.nv, !FAST && shaded));
+        }
+        lane_sum_set(L, sm);
+        if (++c.s == (FAST ? L.send : spp)) {
+            const long long o = FAST ? L.dst : L.pix;
+            out[3 * o + 0] = sm.x;
+            out[3 * o + 1] = sm.y;
+            out[3 * o + 2] = sm.z;
+            if constexpr (MOM) {   // (the squares' part of the partial buffer: its address in the queue block)
+                float *out2 = (float *)queue[kMomentPartWord];
+                out2[3 * o + 0] = L.sum2.x;
+                out2[3 * o + 1] = L.sum2.y;
+                out2[3 * o + 2] = L.sum2.z;
+            }
+            if (COUNT && cost) cost[L.pix] = (unsigned)(cnt.aabb + cnt.tri + cnt.laabb + cnt.ltri - L.work0);
+            // (accumulator: the record of the pixel's next pass; the lane's RNG is at the state its
+            // last sample ended in)
+            if constexpr (CHAIN && !FAST) chain_store(chain_of(queue), (uint32_t)L.pix, (uint32_t)c.s, lane_rng(L), sm);
+            L.pix = -1;
+            L.state = M_IDLE;
+            return;
+        }
+        if (!COUNT && !FAST && park) {   // (idle, still holding its pixel: the kernel's loop parks it)
+            lane_ctr_set(L, c);
+            L.state = M_IDLE;
+            return;
+        }
         lane_ctr_set(L, c);
-        L.state = M_IDLE;
-        return;
+        mega_sample<COUNT, FAST, kOneStart>(L, sc, g, root, cnt);
     }
-    lane_ctr_set(L, c);
-    mega_sample<COUNT, FAST>(L, sc, g, root, cnt);
+    if constexpr (kOneStart) {
+        L.r = make_ray(L.r.o, L.r.d);
+        mega_begin<COUNT>(L, root, cnt);
+    }
 }
 
 // ---------------------------------------------------------------- light-split kernel
@@ -687,7 +722,7 @@ __device__ __forceinline__ void mega_shade_split(ML &L, const DevScene &sc, cons
 #endif
 constexpr bool kLaneAccElide = RT_LANE_ACC_ELIDE != 0;
 template <bool COUNT, class Stack, class Nodes, bool FAST = false, bool LSPLIT = false, bool CHAIN = false,
-          int G = SHADE_TABLES, bool MOM = false, class ML>
+          int G = SHADE_TABLES, bool MOM = false, int CV = 0, class ML>
 __device__ __forceinline__ void mega_iterate(ML &L, bool shade_now, const DevScene &sc, const ShardGeom &g,
                                              const WfState &st, int spp, float *out, unsigned *cost,
                                              const NodeRec &root, Stack &stk, const Nodes &nodes, Counters &cnt,
@@ -706,7 +741,7 @@ __device__ __forceinline__ void mega_iterate(ML &L, bool shade_now, const DevSce
     }
     if (shade_now) {
         if (L.state == M_READY)
-            mega_shade<COUNT, FAST, CHAIN, G, MOM>(L, sc, g, st, spp, out, cost, root, stk, cnt, tail, park, queue);
+            mega_shade<COUNT, FAST, CHAIN, G, MOM, CV>(L, sc, g, st, spp, out, cost, root, stk, cnt, tail, park, queue);
     } else if (L.state == M_TRAV) {
         if (trav_step<COUNT, kFarDist2, kLaneAccElide>(sc, L.r, L.T, stk, nodes, cnt)) L.state = M_READY;
     }

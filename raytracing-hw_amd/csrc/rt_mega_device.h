@@ -129,6 +129,21 @@ constexpr bool kPlainFarDist2 = RT_PLAIN_FAR_DIST2 != 0;
 #define RT_SPEC_ACC_ELIDE RT_ACC_ELIDE
 #endif
 constexpr bool kPlainAccElide = RT_PLAIN_ACC_ELIDE != 0;
+// One ray start per shading pass and the RNG state read where it is drawn from (rt_path.h
+// RT_SHADE_CONVERGE, a mask: CONV_START, CONV_RNG), per kernel and by the rule above.  One call, three
+// interleaved rounds against the form without them (profiles/shconv_parts_ab.jsonl):
+//   plain kernel, 1-GPU frame      903.4-904.5 ms against 917.8-918.1 (-13.7 ms, spread 1.1);
+//   the committed tree, two more calls (shconv_ab.jsonl, shconv_ab2.jsonl): -11.2 ms (spread 4.3, the
+//   one call under three spreads) and -12.9 ms (spread 4.2).
+// The plain kernel takes both.  The runahead kernel was not measured with them (its 8-way shards ran
+// the parent form in that call: slowest 168.1-169.9 ms in every build), and neither were the counting,
+// fast-mode, light-split and accumulator instantiations: all keep the parent form.
+#ifndef RT_PLAIN_SHADE_CONVERGE
+#define RT_PLAIN_SHADE_CONVERGE RT_SHADE_CONVERGE
+#endif
+#ifndef RT_SPEC_SHADE_CONVERGE
+#define RT_SPEC_SHADE_CONVERGE 0
+#endif
 // Leaf rounds per coop step (rt_wavefront.h trav_step_coop round_min): a further round
 // while at least this many leaf lanes are unserved.  Plain kernel: 8 (sponza 1080p 1292 ->
 // 1278 ms against one round per step).  The runahead kernel's depends on the scene
@@ -164,6 +179,7 @@ struct MegaCfg {
     static constexpr bool far_dist2 = spec ? RT_SPEC_FAR_DIST2 != 0 : kPlainFarDist2;
     static constexpr int max_pops = spec ? RT_SPEC_MAX_POPS : COUNT ? rtd::kMaxPops : RT_PLAIN_MAX_POPS;
     static constexpr bool acc_elide = !CHAIN && (spec ? RT_SPEC_ACC_ELIDE != 0 : plain && kPlainAccElide);
+    static constexpr int converge = CHAIN ? 0 : spec ? RT_SPEC_SHADE_CONVERGE : plain ? RT_PLAIN_SHADE_CONVERGE : 0;   // (a mask)
     static constexpr int coop_round_min = kCoopRoundMinPlain;  // (the runahead kernel's comes with the launch: st.round_min)
     static constexpr bool pack_trav = kPackTrav && !LSPLIT && !spec && !FAST;   // RT_PACK_TRAV through its shading pass
 };
@@ -470,7 +486,7 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
             if (L.state == rtd::M_READY) {
                 L.T.phase = 0;   // dead in a READY lane (its stack is empty: T.sp == 0)
                 L.T.sp = 0;
-                rtd::mega_shade<COUNT, FAST, V::chain, V::shade>(L, sc, g, st, spp, out, cost, root, S, cnt, V::spec && tail, park,
+                rtd::mega_shade<COUNT, FAST, V::chain, V::shade, false, V::converge>(L, sc, g, st, spp, out, cost, root, S, cnt, V::spec && tail, park,
                                                                  queue);
             } else {
                 L.T.phase = (int)(pk & 3u);
@@ -478,7 +494,7 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
                 L.T.sp = (int)(pk >> 5);
             }
         } else {
-            rtd::mega_iterate<COUNT, decltype(S), decltype(nodes), FAST, LSPLIT, V::chain, V::shade, V::mom>(
+            rtd::mega_iterate<COUNT, decltype(S), decltype(nodes), FAST, LSPLIT, V::chain, V::shade, V::mom, V::converge>(
                 L, shade_now, sc, g, st, spp, out, cost, root, S, nodes, cnt, V::spec && tail, false, queue);
             // RT_INV_RECOMPUTE: 1 / direction is recomputed after a shading pass (the same IEEE
             // division as make_ray, so the same bits), so a traversing lane does not hold it
@@ -494,6 +510,7 @@ rt_mega_kernel(DevScene sc_in, ShardGeom g, rtd::WfState st, int spp, float *out
             const long long t1 = clock64();
             pf[shade_now ? 0 : 1] += (unsigned long long)(t1 - tp);
             tp = t1;
+            if (!LSPLIT && shade_now && lane == 0) atomicAdd(&rt_prof_lds[7], (unsigned long long)(t1 - rt_prof_mark_lds[threadIdx.x >> 6]));
         }
 #endif
     }

@@ -126,9 +126,10 @@ int mega_prof_report(hipStream_t stream, bool count, long long n_pixels, const i
     HIP_TRY(hipMemcpyFromSymbolAsync(sg, HIP_SYMBOL(g_mega_seg), sizeof sg, 0, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     std::fprintf(stderr, "[mega prof] shade segments, cycles per shade iteration: mesh+emission=%.0f "
-                 "normal=%.0f mr=%.0f sample=%.0f pdf=%.0f base+brdf=%.0f\n",
+                 "normal=%.0f mr=%.0f sample=%.0f pdf=%.0f base+brdf=%.0f before=%.0f after=%.0f\n",
                  (double)sg[0] / pf[3], (double)sg[1] / pf[3], (double)sg[2] / pf[3],
-                 (double)sg[3] / pf[3], (double)sg[4] / pf[3], (double)sg[5] / pf[3]);
+                 (double)sg[3] / pf[3], (double)sg[4] / pf[3], (double)sg[5] / pf[3], (double)sg[6] / pf[3],
+                 (double)sg[7] / pf[3]);
     // the pop block of the coop step (rt_wavefront.h g_pop_prof): how often it runs, for how many
     // lanes, and its share of the traversal iterations' cycles
     unsigned long long pp[rtd::kPopProfN];

@@ -62,9 +62,19 @@ __shared__ unsigned long long rt_prof_lds[8];
             atomicAdd(&rt_prof_lds[k], (unsigned long long)(t1_ - rt_pt_));                              \
         rt_pt_ = t1_;                                                                                    \
     } while (0)
+// Segment 7 (from the end of shade_hit to the pass's end, where the wave is whole again): the
+// first active lane leaves the time at RT_PROF_MARK, and the kernel's loop adds the rest after the
+// pass (rt_mega_device.h).
+__shared__ long long rt_prof_mark_lds[4];
+#define RT_PROF_MARK()                                                                                   \
+    do {                                                                                                 \
+        if ((int)(threadIdx.x & 63) == __ffsll((unsigned long long)__ballot(1)) - 1)                     \
+            rt_prof_mark_lds[threadIdx.x >> 6] = clock64();                                              \
+    } while (0)
 #else
 #define RT_PROF_BEGIN
 #define RT_PROF_SEG(k) do { } while (0)
+#define RT_PROF_MARK() do { } while (0)
 #endif
 
 namespace rtd {
@@ -706,6 +716,26 @@ __device__ __forceinline__ V3 scene_sample(const DevScene &sc, V3 pos, V3 N, V3 
     return light_sample(sc, pos, rng);
 }
 
+// RT_SHADE_CONVERGE: work the lane-resident kernels' shading pass (rt_mega.h mega_shade) did in
+// several divergent branches, or held across the pass, done once and where it is used.  A mask
+// (template parameter CV of the pass's functions, chosen per kernel in rt_mega_device.h,
+// MegaCfg::converge); 0 is the A/B build, the pass as it was, and what every other caller gets.
+//   CONV_START  one ray start per pass: the bounce (shade_post) and the next sample (camera_ray)
+//               leave with the new ray's origin and its direction as computed, and the pass
+//               normalises, divides and tests the root box once for both, where each branch
+//               held its own copy of make_ray and mega_begin.
+//   CONV_RNG    the lane's RNG state is read where the sampler draws from it and written back
+//               behind the sampler (rng_load / rng_store on rt_mega.h's LaneRngSlot), where it
+//               was read at the pass's start and held through the gather, the pdf and the BRDF.
+// Every lane makes the same draws and float operations on the same operands in the same order.
+#ifndef RT_SHADE_CONVERGE
+#define RT_SHADE_CONVERGE 3
+#endif
+enum { CONV_START = 1, CONV_RNG = 2 };
+// Where shade_pre finds the RNG: the caller's own state, or a slot it names (rt_mega.h).
+__device__ __forceinline__ Rng rng_load(const Rng &r) { return r; }
+__device__ __forceinline__ void rng_store(Rng &r, const Rng &v) { r = v; }
+
 // The RNG draws of one sample (scene.cpp:36-41) whose path calls SceneDistribution::sample
 // k times, without the geometry: the two pixel offsets, then per call the mixture draw and
 // the chosen sampler's draws (cosine: three polar normals through the cache; VNDF: the disc
@@ -953,8 +983,9 @@ __device__ __forceinline__ SlotTexels slot_gather(const DevScene &sc, bool prese
 //            lane has a slot skips that slot's loads.
 // The arithmetic is the tables' form's, operation for operation: only where loads are issued
 // and where their results wait differs.
-template <bool COUNT, int G = SHADE_TABLES, class Rec>
-__device__ __forceinline__ bool shade_pre(const DevScene &sc, const Ray &r, const Hit &hit, Rng &rng, Counters &cnt,
+// CV: the parts of RT_SHADE_CONVERGE this pass has (above); `rng_at`: see rng_load.
+template <bool COUNT, int G = SHADE_TABLES, int CV = 0, class Rec, class RngAt>
+__device__ __forceinline__ bool shade_pre(const DevScene &sc, const Ray &r, const Hit &hit, RngAt &rng_at, Counters &cnt,
                                           Rec &P, int &nv, ShadeMid &m, const ShadeTri *r1 = nullptr) {
     RT_PROF_BEGIN
     if (COUNT) cnt.hits++;
@@ -1071,7 +1102,9 @@ __device__ __forceinline__ bool shade_pre(const DevScene &sc, const Ray &r, cons
     const V3 pos = rtv::add(r.o, rtv::mul(r.d, hit.t));
     const V3 eye = rtv::neg(r.d);
     RT_PROF_SEG(2);
+    Rng rng = rng_load(rng_at);   // (CONV_RNG: the lane's slot, read here and written back here)
     const V3 dir = scene_sample(sc, pos, N, eye, r2, rng);
+    rng_store(rng_at, rng);
     RT_PROF_SEG(3);
     nv++;
     if (rtv::dot(dir, N) <= 0.f) {
@@ -1094,7 +1127,8 @@ __device__ __forceinline__ float scene_pdf_lp(const DevScene &sc, V3 N, V3 eye, 
     return (cosine_pdf(N, dir) + lp + vndf_pdf(N, eye, r2, dir)) / 3;
 }
 
-template <int G = SHADE_TABLES, class Rec>
+// RAW: r_out gets the bounce ray's origin and the direction as sampled; its caller makes the ray.
+template <int G = SHADE_TABLES, bool RAW = false, class Rec>
 __device__ __forceinline__ bool shade_post(const DevScene &sc, const V3 rd, const ShadeMid &m, float pdf, Rec &P, int nv,
                                            Ray &r_out) {
     RT_PROF_BEGIN
@@ -1143,7 +1177,12 @@ __device__ __forceinline__ bool shade_post(const DevScene &sc, const V3 rd, cons
     const V3 dielectric = rtv::add(rtv::mul(diffuse, 1 - dsc), rtv::mul(rtv::mul(V3{1.f, 1.f, 1.f}, spec), dsc));
     P.set_brdf(nv - 1, rtv::add(rtv::mul(dielectric, 1 - metallic), rtv::mul(metal, metallic)), coeff,
                rtv::dot(dir, N), mf[8]);
-    r_out = make_ray(rtv::add(pos, rtv::mul(dir, kStep)), dir);
+    if constexpr (RAW) {
+        r_out.o = rtv::add(pos, rtv::mul(dir, kStep));
+        r_out.d = dir;
+    } else {
+        r_out = make_ray(rtv::add(pos, rtv::mul(dir, kStep)), dir);
+    }
     RT_PROF_SEG(5);
     return true;
 }
@@ -1154,15 +1193,15 @@ __device__ __forceinline__ bool shade_post(const DevScene &sc, const V3 rd, cons
 // ray.  Returns false where the recursion returns at this vertex (sample below the surface,
 // pdf <= 0 or NaN).
 // `stk`: the light walk's stack (see light_pdf).
-template <bool COUNT, int G = SHADE_TABLES, class Rec, class Stack>
-__device__ bool shade_hit(const DevScene &sc, Ray &r, const Hit &hit, Rng &rng, Counters &cnt, Rec &P, int &nv,
+template <bool COUNT, int G = SHADE_TABLES, int CV = 0, class Rec, class Stack, class RngAt>
+__device__ bool shade_hit(const DevScene &sc, Ray &r, const Hit &hit, RngAt &rng, Counters &cnt, Rec &P, int &nv,
                           Stack &stk, const ShadeTri *r1 = nullptr) {
     ShadeMid m;
-    if (!shade_pre<COUNT, G>(sc, r, hit, rng, cnt, P, nv, m, r1)) return false;
+    if (!shade_pre<COUNT, G, CV>(sc, r, hit, rng, cnt, P, nv, m, r1)) return false;
     RT_PROF_BEGIN
     const float pdf = scene_pdf<COUNT>(sc, m.pos, m.N, rtv::neg(r.d), m.r2, m.dir, cnt, stk);
     RT_PROF_SEG(4);
-    return shade_post<G>(sc, r.d, m, pdf, P, nv, r);
+    return shade_post<G, (CV & CONV_START) != 0>(sc, r.d, m, pdf, P, nv, r);
 }
 template <bool COUNT, class Rec>
 __device__ bool shade_hit(const DevScene &sc, Ray &r, const Hit &hit, Rng &rng, Counters &cnt, Rec &P, int &nv) {
@@ -1230,7 +1269,8 @@ __device__ V3 trace_sample(const DevScene &sc, Ray r, Rng &rng, Counters &cnt) {
     return fold_path(P, nv);
 }
 
-// Camera::cast_in_pixel (camera.cpp:49-62)
+// Camera::cast_in_pixel (camera.cpp:49-62); RAW: origin and direction before Ray::Ray
+template <bool RAW = false>
 __device__ __forceinline__ Ray camera_ray(const DevScene &sc, int px, int py, float ox, float oy) {
     V3 t;
     t.x = (2.f * ((float)px + 0.5f + ox) / sc.fwidth - 1) * sc.tan_fov[0];
@@ -1241,7 +1281,15 @@ __device__ __forceinline__ Ray camera_ray(const DevScene &sc, int px, int py, fl
 #pragma unroll
     for (int i = 0; i < 3; ++i)
         d = rtv::add(d, rtv::mul(V3{sc.cam_axes[3 * i], sc.cam_axes[3 * i + 1], sc.cam_axes[3 * i + 2]}, tv[i]));
-    return make_ray(V3{sc.cam_pos[0], sc.cam_pos[1], sc.cam_pos[2]}, d);
+    if constexpr (RAW) {
+        Ray r;
+        r.o = V3{sc.cam_pos[0], sc.cam_pos[1], sc.cam_pos[2]};
+        r.d = d;
+        r.inv = V3{0.f, 0.f, 0.f};
+        return r;
+    } else {
+        return make_ray(V3{sc.cam_pos[0], sc.cam_pos[1], sc.cam_pos[2]}, d);
+    }
 }
 
 // Scene::render body for one pixel (scene.cpp:34-43) with the per-pixel RNG convention.
