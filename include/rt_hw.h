@@ -423,6 +423,21 @@ int rt_intersect_rays(rt_scene *scene, int64_t n, const float *org, const float 
  * bound is reported with hit = -2.  Any other path is RT_ERR_ARG. */
 int rt_intersect_rays_via(rt_scene *scene, int32_t path, int64_t n, const float *org, const float *dir, float *out_f,
                           int64_t *out_i);
+/* Sampler-level query (test entry): SceneDistribution::sample, then ::pdf of the drawn direction, for
+ * explicit shading frames.  Host arrays: frame n x 10 (point, normal, eye direction, roughness2; taken
+ * as given, nothing is normalised), seed n (the engine's seed, 1 .. 2147483646), warm n (0, or 1: one
+ * polar normal is drawn first, so the normal cache is full where the sampler starts).  Frame i is thread
+ * i and starts from Engine(seed[i]) with an empty normal cache.  out_f n x 6 (direction, pdf, the light
+ * distribution's pdf alone, the next polar normal), out_i n x 4 (status, the next engine output, light
+ * AABB tests, light triangle tests).
+ *   path 0  scene_sample, then scene_pdf over a private stack (rt_path.h), as the per-pixel and
+ *           wavefront kernels compose them;
+ *   path 1  scene_sample, the light_step walk (bounded by the light list's size), scene_pdf_lp, as the
+ *           lane-resident kernels compose them.
+ * Status 0: complete; -2: the light walk reached its bound.  A NULL argument, another path, a seed
+ * outside its range or a warm flag above 1: RT_ERR_ARG, before any device work. */
+int rt_sample_frames_via(rt_scene *scene, int32_t path, int64_t n, const float *frame, const uint32_t *seed,
+                         const uint32_t *warm, float *out_f, int64_t *out_i);
 
 /* --- frame finish / output (host) ---------------------------------------------------- */
 /* mean -> ACES -> powf(1/2.2) -> roundf(clamp(v*255)) per scene.cpp:54-64, vector.h:222-233, :400-407 */

@@ -19,6 +19,8 @@
 //   rays_from <gltf> W H rays_in.rtd out.rtd   the same record for the rays of an rtdump file (origin, direction)
 //   dump    <gltf> W H out.rtd                 post-BVH scene arrays (bvh.cpp:166 reorders objects)
 //   samplers <gltf> W H n out.rtd              SceneDistribution::sample/pdf + RNG known answers
+//   samplers_from <gltf> W H in.rtd out.rtd [nolights]
+//                                              the same for the frames, seeds and warm flags of an rtdump file
 //   pixels  <gltf> W H spp idx.i64 out.rtd [threads]
 //                                              per-pixel sums of the listed frame pixels (raw int64
 //                                              indices j*W+i) at full spp, + per-pixel test counts
@@ -553,6 +555,71 @@ static int mode_samplers(int argc, char **argv) {
     return 0;
 }
 
+// The sampler known answers for a caller's shading frames: the `frame` (n x 10 floats: point,
+// normal, eye, roughness2), `seed` and `warm` arrays of an rtdump file, in file order, bit for bit
+// as given.  Per row: a reset normal cache and Engine(seed), `warm` draws of rng::normal::sample (so
+// the cache is full where the sampler starts), SceneDistribution::sample, then ::pdf with the counted
+// tests of its light walk, ManyLightsDistribution::pdf alone, and one more normal and one engine
+// output: these pin the cache's flag, its value and the number of draws.  `nolights`: the
+// distribution over an empty primitive list (the /= 1.5f mixture and the two-term pdf).
+static int mode_samplers_from(int argc, char **argv) {
+    if (argc < 7) throw std::runtime_error("samplers_from <gltf> W H in.rtd out.rtd [nolights]");
+    int W = atoi(argv[3]), H = atoi(argv[4]);
+    const bool nolights = argc > 7 && std::strcmp(argv[7], "nolights") == 0;
+    const std::vector<float> in = rtdump_read_f32(argv[5], "frame", 10);
+    const std::vector<uint32_t> seeds = rtdump_read_u32(argv[5], "seed"), warm = rtdump_read_u32(argv[5], "warm");
+    const size_t n = seeds.size();
+    if (in.size() != 10 * n || warm.size() != n) throw std::runtime_error("samplers_from: frame, seed and warm differ in length");
+    Scene s = parse_scene_gltf(argv[2], W, H, 1);
+    const std::vector<Primitive> none;
+    const std::vector<Primitive> &prims = nolights ? none : s.objects;
+    rng::SceneDistribution sd(prims);
+    bool has_lights = false;
+    for (auto &p : prims) has_lights |= p.emissive();
+    std::unique_ptr<rng::ManyLightsDistribution> ml;
+    if (has_lights) ml = std::make_unique<rng::ManyLightsDistribution>(prims);
+    std::vector<float> outd, outp, outn, outl, outr;
+    std::vector<uint32_t> next;
+    std::vector<uint64_t> nlaabb, nltri;
+    for (size_t k = 0; k < n; ++k) {
+        const float *f = &in[10 * k];
+        const vector3f point{f[0], f[1], f[2]}, nn{f[3], f[4], f[5]}, eye{f[6], f[7], f[8]};
+        if (seeds[k] < 1u || seeds[k] > 2147483646u || warm[k] > 1u) throw std::runtime_error("samplers_from: seed or warm out of range");
+        rng::normDist.reset();
+        Engine e(seeds[k]);
+        for (uint32_t w = 0; w < warm[k]; ++w) (void)rng::normal::sample(e);
+        const vector3f d = sd.sample(point, nn, eye, f[9], e);
+        reset_counters();
+        t_mode = 0;
+        const float pdf = sd.pdf(point, nn, eye, f[9], d);
+        const Counters c = total_counters();
+        const float lp = ml ? ml->pdf(point, d) : 0.f;
+        // and as the `rays` record asks for it: through Ray::Ray, which normalises d once more (an ulp's
+        // difference where normalising a unit vector is not the identity)
+        const Ray r(point, d);
+        outr.push_back(ml ? ml->pdf(r.origin, r.direction) : 0.f);
+        outd.push_back(d.x); outd.push_back(d.y); outd.push_back(d.z);
+        outp.push_back(pdf);
+        outl.push_back(lp);
+        nlaabb.push_back(c.laabb);
+        nltri.push_back(c.ltri);
+        outn.push_back(rng::normal::sample(e));
+        next.push_back((uint32_t)e());
+    }
+    RtDump d(argv[6]);
+    d.put("dir", outd, {(uint64_t)n, 3});
+    d.put("pdf", outp);
+    d.put("light_pdf", outl);
+    d.put("ray_light_pdf", outr);
+    d.put("next_normal", outn);
+    d.put("next", next);
+    d.put("n_light_aabb", nlaabb);
+    d.put("n_light_tri", nltri);
+    d.close();
+    std::printf("{\"mode\": \"samplers_from\", \"n\": %llu, \"lights\": %d}\n", (unsigned long long)n, has_lights ? 1 : 0);
+    return 0;
+}
+
 // finish <out.rtd> <out.ppm> W H spp: the frame finish of Scene::render (scene.cpp:54-64)
 // and Scene::draw_into (Canvas::write_to, canvas.h:76-89) on deterministic synthetic pixel
 // sums spanning zero, tiny, mid-range, saturating, negative and NaN/inf values.
@@ -588,7 +655,7 @@ static int mode_finish(int argc, char **argv) {
 
 int main(int argc, char **argv) {
     try {
-        if (argc < 2) throw std::runtime_error("usage: ref_harness sums|time|rays|rays_from|dump|samplers|finish|pixels ...");
+        if (argc < 2) throw std::runtime_error("usage: ref_harness sums|time|rays|rays_from|dump|samplers|samplers_from|finish|pixels ...");
         std::string m = argv[1];
         if (m == "sums") return mode_sums(argc, argv);
         if (m == "time") return mode_time(argc, argv);
@@ -596,6 +663,7 @@ int main(int argc, char **argv) {
         if (m == "rays_from") return mode_rays_from(argc, argv);
         if (m == "dump") return mode_dump(argc, argv);
         if (m == "samplers") return mode_samplers(argc, argv);
+        if (m == "samplers_from") return mode_samplers_from(argc, argv);
         if (m == "finish") return mode_finish(argc, argv);
         if (m == "pixels") return mode_pixels(argc, argv);
         throw std::runtime_error("unknown mode " + m);

@@ -57,9 +57,9 @@ template <> inline char RtDump::code<int64_t>() { return 'q'; }
 template <> inline char RtDump::code<uint64_t>() { return 'Q'; }
 template <> inline char RtDump::code<uint8_t>() { return 'B'; }
 
-// Reads the f32 array `name` of an RTD1 file whose shape is (n, cols).  Every length in the
-// file is checked against the file's size before it is used.
-inline std::vector<float> rtdump_read_f32(const std::string &path, const std::string &name, uint64_t cols) {
+// Reads the array `name` of an RTD1 file: 4-byte items of dtype `want` ('f' or 'I'), shape (n, cols),
+// or (n) where cols is 0.  Every length in the file is checked against the file's size before it is used.
+inline std::vector<uint32_t> rtdump_read_words(const std::string &path, const std::string &name, char want, uint64_t cols) {
     std::FILE *f = std::fopen(path.c_str(), "rb");
     if (!f) throw std::runtime_error("rtdump: cannot open " + path);
     std::vector<uint8_t> buf;
@@ -96,12 +96,22 @@ inline std::vector<float> rtdump_read_f32(const std::string &path, const std::st
         if (count > buf.size() / item) throw std::runtime_error("rtdump: truncated " + path);
         need(count * item);
         if (nm == name) {
-            if (dt != 'f' || nd != 2 || shape[1] != cols) throw std::runtime_error("rtdump: " + name + " is not an (n, cols) f32 array");
-            std::vector<float> out(count);
+            if (dt != (uint8_t)want || (cols ? (nd != 2 || shape[1] != cols) : nd != 1))
+                throw std::runtime_error("rtdump: " + name + " has another type or shape than asked for");
+            std::vector<uint32_t> out(count);
             if (count) std::memcpy(out.data(), &buf[p], count * 4);
             return out;
         }
         p += count * item;
     }
     throw std::runtime_error("rtdump: no array " + name + " in " + path);
+}
+inline std::vector<float> rtdump_read_f32(const std::string &path, const std::string &name, uint64_t cols) {
+    const std::vector<uint32_t> w = rtdump_read_words(path, name, 'f', cols);
+    std::vector<float> out(w.size());
+    if (!w.empty()) std::memcpy(out.data(), w.data(), w.size() * 4);
+    return out;
+}
+inline std::vector<uint32_t> rtdump_read_u32(const std::string &path, const std::string &name) {
+    return rtdump_read_words(path, name, 'I', 0);
 }

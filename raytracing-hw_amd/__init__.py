@@ -160,6 +160,9 @@ ABI = {
                                          ctypes.POINTER(ctypes.c_int64)]),
     "rt_intersect_rays_via": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, _c_f, _c_f, _c_f,
                                              ctypes.POINTER(ctypes.c_int64)]),
+    "rt_sample_frames_via": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, _c_f,
+                                            ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), _c_f,
+                                            ctypes.POINTER(ctypes.c_int64)]),
     "rt_tonemap_u8": (ctypes.c_int, [_c_f, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_b]),
     "rt_tonemap_u8_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.c_void_p, ctypes.c_void_p]),
@@ -360,6 +363,27 @@ class Scene:
         _check(lib().rt_intersect_rays_via(self._h, int(path), n, org.ctypes.data_as(_c_f), dirs.ctypes.data_as(_c_f),
                                            out_f.ctypes.data_as(_c_f),
                                            out_i.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        _after_render()
+        return out_f, out_i
+
+    def sample_frames(self, frame, seed, warm, path=0):
+        """Sampled direction + pdf per shading frame (rt_sample_frames_via): frame n x 10 (point, normal,
+        eye, roughness2), seed and warm n; returns (f32 n x 6 [dir, pdf, light pdf, next normal],
+        i64 n x 4 [status, next engine output, light AABB tests, light triangle tests]).  path 0:
+        scene_pdf, 1: the light_step walk and scene_pdf_lp; frame i is thread i; status -2 where
+        path 1's walk did not end."""
+        frame = np.ascontiguousarray(frame, np.float32).reshape(-1, 10)
+        seed = np.ascontiguousarray(seed, np.uint32).reshape(-1)
+        warm = np.ascontiguousarray(warm, np.uint32).reshape(-1)
+        n = frame.shape[0]
+        if seed.shape[0] != n or warm.shape[0] != n:
+            raise ValueError("sample_frames: frame, seed and warm differ in length")
+        out_f = np.zeros((n, 6), np.float32)
+        out_i = np.zeros((n, 4), np.int64)
+        c_u = ctypes.POINTER(ctypes.c_uint32)
+        _check(lib().rt_sample_frames_via(self._h, int(path), n, frame.ctypes.data_as(_c_f), seed.ctypes.data_as(c_u),
+                                          warm.ctypes.data_as(c_u), out_f.ctypes.data_as(_c_f),
+                                          out_i.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         _after_render()
         return out_f, out_i
 

@@ -2,6 +2,7 @@
 // kernels and their host halves), the ray queries rt_intersect_rays[_via] (rt_rays_kernel, rt_rays_via_kernel)
 // and the debug build's rt_debug_take / rt_debug_set_poison.  Included by rt_device.hip at its end, after
 // rt_temporal_device.h and the whole-frame path, so the build stays one translation unit: it needs DeviceGuard,
+// (and the shading-frame query rt_sample_frames_via: rt_frames_kernel)
 // HIP_TRY, ensure_device_scene and g_live from there and the plain kernel's constants (kCoopLeavesPlain,
 // kCoopRoundMinPlain, kPlainFarDist2, kPlainAccElide, RT_PLAIN_MAX_POPS) from rt_mega_device.h for the steps of rt_wavefront.h.
 
@@ -364,6 +365,58 @@ __global__ void __launch_bounds__(256) rt_rays_via_kernel(DevScene sc, long long
     query_store(out_f, out_i, k, ok, h, lp, (done && light_done) ? (long long)ok : -2ll, c1, c2);
 }
 
+// rt_sample_frames_via: the caller's shading frame k (point, normal, eye, roughness2) on thread k, from
+// Rng(seed[k]) with an empty normal cache, after warm[k] (0 or 1) polar normals, which fill it:
+// scene_sample, then the pdf of the drawn direction.  Path 0: scene_pdf<true> over a LocalStack, as
+// shade_hit and the wavefront shade kernel compose them (the light pdf alone is a second, uncounted
+// light_pdf).  Path 1: light_query (the light_step walk, status -2 at its bound) and scene_pdf_lp, as
+// both lane-resident families compose them.  Then one more polar normal and one engine output: the
+// cache's flag and value and the number of draws.  The host has checked seed and warm, so the RNG's
+// rejection loops end by themselves; no other loop here depends on the caller's values.
+template <int PATH>
+__global__ void __launch_bounds__(256) rt_frames_kernel(DevScene sc, long long n, int light_bound, const float *frame,
+                                                         const uint32_t *seed, const uint32_t *warm, float *out_f,
+                                                         long long *out_i) {
+    static_assert(PATH == 0 || PATH == 1, "two compositions");
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const float *f = frame + 10 * k;
+    const rtv::V3 pos{f[0], f[1], f[2]}, N{f[3], f[4], f[5]}, eye{f[6], f[7], f[8]};
+    const float r2 = f[9];
+    rtd::Rng rng{seed[k], 0u, 0.f};
+    if (warm[k]) (void)rtd::rng_normal(rng);
+    Counters cnt{0, 0, 0, 0, 0, 0, 0};
+    const rtv::V3 d = rtd::scene_sample(sc, pos, N, eye, r2, rng);
+    float pdf, lp = 0.f;
+    bool done = true;
+    if constexpr (PATH == 0) {
+        rtd::LocalStack S;
+        pdf = rtd::scene_pdf<true>(sc, pos, N, eye, r2, d, cnt, S);
+        Counters c2{0, 0, 0, 0, 0, 0, 0};
+        if (sc.n_lights) lp = rtd::light_pdf<false>(sc, pos, d, c2, S);
+    } else {
+        if (sc.n_lights) {
+            rtd::LocalStack S;
+            rtd::Ray q;   // (light_query makes light_pdf's Ray(point, direction) of these two)
+            q.o = pos;
+            q.d = d;
+            q.inv = d;
+            done = light_query(sc, q, true, light_bound, S, cnt, lp);
+        }
+        pdf = rtd::scene_pdf_lp(sc, N, eye, r2, d, lp);
+    }
+    out_f[6 * k + 0] = d.x;
+    out_f[6 * k + 1] = d.y;
+    out_f[6 * k + 2] = d.z;
+    out_f[6 * k + 3] = pdf;
+    out_f[6 * k + 4] = lp;
+    out_f[6 * k + 5] = rtd::rng_normal(rng);
+    out_i[4 * k + 0] = done ? 0ll : -2ll;
+    out_i[4 * k + 1] = (long long)rtd::rng_next(rng);
+    out_i[4 * k + 2] = cnt.laabb;
+    out_i[4 * k + 3] = cnt.ltri;
+}
+
 namespace {
 // Host-made cases of selfcheck 2 (deterministic): 8-triangle groups of a base triangle, its
 // exact copy, a coplanar one behind an equal-t prefix, its copy, a NaN-vertex one, a random
@@ -561,6 +614,45 @@ int rt_intersect_rays_via(rt_scene *s, int32_t path, int64_t n, const float *org
 
 int rt_intersect_rays(rt_scene *s, int64_t n, const float *org, const float *dir, float *out_f, int64_t *out_i) {
     return rt_intersect_rays_via(s, 0, n, org, dir, out_f, out_i);
+}
+
+int rt_sample_frames_via(rt_scene *s, int32_t path, int64_t n, const float *frame, const uint32_t *seed, const uint32_t *warm,
+                         float *out_f, int64_t *out_i) {
+    const char *who = "rt_sample_frames_via: ";
+    if (!s || n < 0 || (n > 0 && (!frame || !seed || !warm || !out_f || !out_i)))
+        return rt_fail(RT_ERR_ARG, "rt_sample_frames_via: bad argument");
+    if (path < 0 || path > 1) return rt_fail(RT_ERR_ARG, "rt_sample_frames_via: unknown path " + std::to_string(path));
+    // (an engine state of 0 or 2^31 - 1 stays there, and the polar loop would not end on it)
+    for (int64_t k = 0; k < n; ++k) {
+        if (seed[k] < 1u || seed[k] > 2147483646u)
+            return rt_fail(RT_ERR_ARG, "rt_sample_frames_via: seed of frame " + std::to_string(k) + " is outside 1 .. 2147483646");
+        if (warm[k] > 1u) return rt_fail(RT_ERR_ARG, "rt_sample_frames_via: warm of frame " + std::to_string(k) + " is neither 0 nor 1");
+    }
+    if (n == 0) return RT_OK;
+    if (n > (1ll << 30)) return rt_fail(RT_ERR_LIMIT, "rt_sample_frames_via: more than 2^30 frames");
+    if (int rc = ensure_device_scene(s, 0)) return rc;
+    DeviceGuard guard(0);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    const DevScene &sc = s->dev[0]->ds;
+    const long long light_bound = 8ll * sc.n_lights + 64;   // (as rt_intersect_rays_via's)
+    if (light_bound > 0x7fffffffll) return rt_fail(RT_ERR_LIMIT, "rt_sample_frames_via: scene too large");
+    // one buffer: the integer results (8-byte words), the float results, the frames, the seeds, the warm flags
+    const size_t bi = (size_t)n * 4 * sizeof(long long), bf = (size_t)n * 6 * sizeof(float), bfr = (size_t)n * 10 * sizeof(float),
+                 bw = (size_t)n * sizeof(uint32_t);
+    DeviceBuf buf;
+    HIP_TRY_AS(who, buf.alloc(bi + bf + bfr + 2 * bw));
+    long long *d_i = (long long *)buf.p;
+    float *d_f = (float *)(buf.p + bi), *d_fr = (float *)(buf.p + bi + bf);
+    uint32_t *d_s = (uint32_t *)(buf.p + bi + bf + bfr), *d_w = (uint32_t *)(buf.p + bi + bf + bfr + bw);
+    HIP_TRY_AS(who, hipMemcpy(d_fr, frame, bfr, hipMemcpyHostToDevice));
+    HIP_TRY_AS(who, hipMemcpy(d_s, seed, bw, hipMemcpyHostToDevice));
+    HIP_TRY_AS(who, hipMemcpy(d_w, warm, bw, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(path == 0 ? rt_frames_kernel<0> : rt_frames_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       nullptr, sc, (long long)n, (int)light_bound, d_fr, d_s, d_w, d_f, d_i);
+    HIP_TRY_AS(who, hipGetLastError());
+    HIP_TRY_AS(who, hipMemcpy(out_f, d_f, bf, hipMemcpyDeviceToHost));
+    HIP_TRY_AS(who, hipMemcpy(out_i, d_i, bi, hipMemcpyDeviceToHost));
+    return RT_OK;
 }
 
 int rt_device_selfcheck(int32_t which, uint64_t *mismatches) {

@@ -69,6 +69,56 @@ extern "C" int kh_render_wf(const rt_scene_view *v, int spp, int rank, int world
     return 0;
 }
 
+// The record of the shadeedge chain, in the layout of rt_sample_frames_via (include/rt_hw.h):
+// warm[k] polar normals are drawn before the sampler, so its cache is full at entry; out_f row = (dir, pdf,
+// the light pdf alone, the next polar normal), out_i row = (status, the next engine output, the light walk's
+// AABB and triangle tests).  path 0: scene_pdf<true> over a LocalStack; path 1: light_step until the walk is
+// done (status -2 at 8 * n_lights + 64 steps), then scene_pdf_lp.  warm == nullptr: a cold cache everywhere.
+static void samplers_row(const rtd::DevScene &sc, int path, const float *f, uint32_t seed, uint32_t warm, float *of,
+                         int64_t *oi) {
+    const rtv::V3 pos{f[0], f[1], f[2]}, N{f[3], f[4], f[5]}, eye{f[6], f[7], f[8]};
+    rtd::Rng rng{seed, 0u, 0.f};
+    if (warm) (void)rtd::rng_normal(rng);
+    rtd::Counters cnt{0, 0, 0, 0, 0, 0, 0}, c2{0, 0, 0, 0, 0, 0, 0};
+    const rtv::V3 d = rtd::scene_sample(sc, pos, N, eye, f[9], rng);
+    float pdf, lp = 0.f;
+    int64_t status = 0;
+    if (path == 0) {
+        pdf = rtd::scene_pdf<true>(sc, pos, N, eye, f[9], d, cnt);
+        if (sc.n_lights) lp = rtd::light_pdf<true>(sc, pos, d, c2);
+    } else {
+        if (sc.n_lights) {
+            const rtd::Ray lr = rtd::make_ray(pos, d);   // light_pdf's Ray(point, direction)
+            const float4 dq = make_float4(d.x, d.y, d.z, 0.f);
+            rtd::LocalStack S;
+            rtd::TravState T;
+            T.acc = 0.f;
+            T.sp = 0;
+            S.put(T.sp++, make_uint2(0u, 0u));
+            bool active = true;
+            for (long long it = 0; it < 8ll * sc.n_lights + 64 && active; ++it)
+                if (rtd::light_step<true>(sc, lr, T, S, cnt, &dq)) active = false;
+            lp = T.acc / (float)sc.n_lights;
+            if (active) status = -2;
+        }
+        pdf = rtd::scene_pdf_lp(sc, N, eye, f[9], d, lp);
+    }
+    of[0] = d.x;
+    of[1] = d.y;
+    of[2] = d.z;
+    of[3] = pdf;
+    of[4] = lp;
+    of[5] = rtd::rng_normal(rng);
+    oi[0] = status;
+    oi[1] = rtd::rng_next(rng);
+    oi[2] = cnt.laabb;
+    oi[3] = cnt.ltri;
+}
+extern "C" void kh_sample_frames(const rt_scene_view *v, int path, int64_t n, const float *frame, const uint32_t *seed,
+                                 const uint32_t *warm, float *out_f, int64_t *out_i) {
+    rtd::DevScene sc = make(v);
+    for (int64_t k = 0; k < n; ++k) samplers_row(sc, path, frame + 10 * k, seed[k], warm ? warm[k] : 0u, out_f + 6 * k, out_i + 4 * k);
+}
 // SceneDistribution sample + pdf from explicit shading frames (the sampler goldens):
 // frame = (point, normal, eye, roughness2); each draw starts from Rng(seed) with an empty
 // normal cache; next_out = the engine's next output after the draw (pins draws consumed).
@@ -86,6 +136,46 @@ extern "C" void kh_samplers(const rt_scene_view *v, int64_t n, const float *fram
         dir_out[3 * k + 1] = d.y;
         dir_out[3 * k + 2] = d.z;
         next_out[k] = rtd::rng_next(rng);
+    }
+}
+
+// What the draws of one scene_sample were, for the aimed seeds of the shadeedge `branch` class: the mixture's
+// s as mixture_pick computes it, the sampler it picks, and that sampler's own draws (light: the pick's uniform,
+// u and v before the fold; VNDF: the disc pairs rejected).  The draws are restated here from the same RNG
+// functions; tf row = (s, pick uniform, u, v), ti row = (sampler, disc pairs rejected, engine output after
+// the restated draws and one more polar normal).  The caller checks that output against kh_sample_frames'
+// own: they differ only where cosine_sample retried.
+extern "C" void kh_sampler_trace(int n_lights, int64_t n, const uint32_t *seed, const uint32_t *warm, float *tf, int64_t *ti) {
+    for (int64_t k = 0; k < n; ++k) {
+        rtd::Rng rng{seed[k], 0u, 0.f};
+        if (warm && warm[k]) (void)rtd::rng_normal(rng);
+        rtd::Rng probe = rng;
+        const int b = rtd::mixture_pick(probe, n_lights);
+        float s = (rtd::rng_uniform_m11(rng) + 1.f) * 3 * 0.5f;
+        if (!n_lights) s /= 1.5f;
+        float *f = tf + 4 * k;
+        f[0] = s;
+        f[1] = f[2] = f[3] = 0.f;
+        int64_t rejected = 0;
+        if (b == 0) {
+            (void)rtd::sphere(rng);
+        } else if (b == 1) {
+            float ux, uy;
+            do {
+                ux = rtd::rng_uniform_m11(rng);
+                uy = rtd::rng_uniform_m11(rng);
+                ++rejected;
+            } while (ux * ux + uy * uy > 1.f);
+            --rejected;
+        } else {
+            f[1] = rtd::rng_uniform_m11(rng);
+            f[2] = (rtd::rng_uniform_m11(rng) + 1.f) / 2;
+            f[3] = (rtd::rng_uniform_m11(rng) + 1.f) / 2;
+        }
+        ti[3 * k] = b;
+        ti[3 * k + 1] = rejected;
+        (void)rtd::rng_normal(rng);
+        ti[3 * k + 2] = rtd::rng_next(rng);
     }
 }
 

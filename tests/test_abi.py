@@ -26,7 +26,7 @@ def declared_functions():
 def test_header_declares_the_boundary():
     names = declared_functions()
     for must in ["rt_scene_load_gltf", "rt_scene_from_view", "rt_render", "rt_render_device", "rt_intersect_rays",
-                 "rt_intersect_rays_via",
+                 "rt_intersect_rays_via", "rt_sample_frames_via",
                  "rt_tonemap_u8", "rt_write_ppm", "rt_shard_rows", "rt_last_error", "rt_abi_version",
                  "rt_render_multi", "rt_render_frame"]:
         assert must in names

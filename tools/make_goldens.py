@@ -38,6 +38,11 @@ Outputs (tests/golden/):
                                              # geoedge_rays.rtd (ref_harness rays_from on them),
                                              # geoedge_sums_24x16x4.rtd and its .ppm; its metadata
                                              # goes to golden_meta.json "geoedge"
+    python tools/make_goldens.py --shadeedge # only the shadeedge fixtures (singular shading frames):
+                                             # shadeedge_<scene>_in.rtd (tests/shadeedge_util.py) and
+                                             # shadeedge_<scene>.rtd (ref_harness samplers_from on them)
+                                             # for cornell, geoedge, practice6_1 and cornell without
+                                             # lights; class counts go to golden_meta.json "shadeedge"
 """
 import hashlib
 import importlib.util
@@ -327,7 +332,34 @@ def geoedge_goldens():
     print(json.dumps(meta, indent=1))
 
 
+def shadeedge_goldens():
+    """The shadeedge fixtures: per scene the generated shading frames (tests/shadeedge_util.py) and the
+    reference's answers to them (ref_harness samplers_from).  Touches no other fixture's files."""
+    import shadeedge_util as su
+    rt = rtref.package()
+    meta = {}
+    for scene in su.SCENES:
+        name, nolights = su.scene_file(scene)
+        fin = su.shadeedge_frames(su.scene_arrays(rt, scene))
+        path_in = os.path.join(GOLD, f"shadeedge_{scene}_in.rtd")
+        rtdump.save(path_in, fin)
+        info = harness("samplers_from", os.path.join(GOLD, "scenes", name, name + ".gltf"), 64, 64, path_in,
+                       os.path.join(GOLD, f"shadeedge_{scene}.rtd"), *(["nolights"] if nolights else []))
+        meta[scene] = {"samplers_from": info, "classes": {c: int((fin["cls"] == k).sum()) for k, c in enumerate(su.CLASSES)}}
+    path = os.path.join(GOLD, "golden_meta.json")
+    allmeta = json.load(open(path))
+    allmeta["shadeedge"] = meta
+    with open(path, "w") as f:
+        json.dump(allmeta, f, indent=1, sort_keys=True)
+    print(json.dumps(meta, indent=1))
+
+
 def main():
+    if "--shadeedge" in sys.argv:
+        if not os.path.exists(HARNESS):
+            sys.exit("build the reference harness first: make -C oracle ref")
+        shadeedge_goldens()
+        return
     if "--geoedge" in sys.argv:
         if not os.path.exists(HARNESS):
             sys.exit("build the reference harness first: make -C oracle ref")
