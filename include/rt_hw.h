@@ -211,6 +211,62 @@ typedef struct { float pos[3]; float axes[9]; float tan_half_fov[2]; } rt_camera
 int rt_scene_get_camera(const rt_scene *scene, rt_camera *out);
 int rt_scene_set_camera(rt_scene *scene, const rt_camera *cam);
 
+/* --- movable geometry: triangle updates and a device-side BVH refit (additive in ABI 6) ------- */
+/* New triangle records go into the scene in place and every node box is recomputed bottom-up; the
+ * tree's topology and the primitive order are kept.  csrc/rt_refit.h is the rule's text, shared by
+ * the host function, the device kernels and the CPU tests:
+ *   select    smin(a, b) = b < a ? b : a, smax(a, b) = a < b ? b : a per component (std::min / std::max)
+ *   start     every fold starts from the empty box (+FLT_MAX, -FLT_MAX)
+ *   triangle  grow over v0, v0 + U, v0 + V in that order, each sum one f32 add per component
+ *   leaf      grow over the boxes of its triangles first .. first + count - 1, in order
+ *   internal  grow(left child's box), then grow(right child's box)
+ * These are the boxes the reference's build gives the same ranges (Primitive::aabb primitive.cpp:63-75,
+ * buildNode bvh.cpp:131-133): the bits of a bound are those of the first element in primitive order that
+ * attains it (+0 and -0 keep their order), and a NaN component is never taken (an all-NaN triangle
+ * gives the empty box, which changes nothing in its parent).
+ *
+ * rt_scene_update_tris replaces triangles [first, first + count) (post-build order, the ids
+ * rt_intersect_rays reports).  tri: count x 12; tri_attr: count x 16 or NULL (kept); tri_tan: count x 12
+ * or NULL (kept); records are taken as given (nothing normalised, non-finite words allowed).  The mesh
+ * id word of tri_attr is ignored: a triangle never changes mesh.  Topology, primitive order, bvh_depth,
+ * the light list and the light BVH are unchanged.  It updates the host arrays and refits the host
+ * `node`, patches the cached device image (a later upload to another device is current), and on every
+ * device the scene is uploaded to copies the range, scatters it into the arrays, runs the device
+ * refit and waits: a device copy's boxes come from the device kernels, not from the host's.  It works
+ * on a scene that is on no device.
+ * rt_scene_update_tris_device: the same with the new records already on `device` (device pointers,
+ * 16-byte aligned, not inside the scene's own arrays), the scatter and the refit enqueued on `stream`;
+ * it then reads the changed range and the node array back into the host arrays and the cached image, and
+ * waits.  The scene must be uploaded to `device` and to no other device.
+ * Refusals, all before any launch or copy (nothing is left half made): NULL tri, a range beyond
+ * n_tris, a triangle of the range that belongs to an emissive mesh (mesh_f emission not all zero;
+ * moving lights are not supported: the light records and the light BVH are not remapped), and for the
+ * device entry a scene that is not on `device`, or also on another, or a misaligned pointer:
+ * RT_ERR_ARG.  count == 0 is RT_OK and nothing happens.
+ * Both fall under "one render per (scene, device) in flight", and so do rt_gbuffer*, rt_history_push and
+ * the ray queries against an update: no update may run while any entry reads the scene's device copy.
+ *
+ * Contract: after an update every entry (rt_render*, rt_render_frame, both kernels, fast mode,
+ * runahead, the counters, rt_gbuffer*, rt_intersect_rays*, rt_sample_frames_via, rt_device_selfcheck
+ * 4 and 5) behaves bit for bit as on rt_scene_from_view(the same arrays, node = rt_refit_view(...)).
+ * Accumulators: an update bumps the scene's epoch exactly as rt_scene_set_camera does, so the stale
+ * rule and rt_accum_reset above apply unchanged.  A checkpoint's header holds no geometry: loading one
+ * onto moved geometry is undetected, as it is for any other scene with equal counts.
+ * rt_history: nothing changes in it; for a moved object its mesh, normal and plane tests accept or
+ * reject as they stand, and there are no motion vectors (a known limit).
+ * A refit keeps the topology: after large moves the tree is still correct, but its quality (overlap
+ * of sibling boxes) is whatever the moves left; there is no rebuild. */
+int rt_scene_update_tris(rt_scene *scene, uint32_t first, uint32_t count,
+                         const float *tri, const float *tri_attr, const float *tri_tan);
+int rt_scene_update_tris_device(rt_scene *scene, int32_t device, uint32_t first, uint32_t count,
+                                const float *d_tri, const float *d_tri_attr, const float *d_tri_tan, void *stream);
+/* Pure host function: the refit boxes of a view's triangles and topology.
+ * out_node: n_nodes x 8, with a and b copied. */
+int rt_refit_view(const rt_scene_view *view, float *out_node);
+/* Test / inspection entry: the device copy's arrays back in the host layout, nodes in build order.
+ * Any pointer may be NULL. */
+int rt_scene_read_device(rt_scene *scene, int32_t device, float *tri, float *tri_attr, float *tri_tan, float *node);
+
 /* --- render ----------------------------------------------------------------------- */
 /* Copies the scene to `device` (once per device; later calls reuse it).  One render per
  * (scene, device) may be in flight at a time; different devices render independently. */
@@ -482,7 +538,8 @@ int rt_write_ppm(const char *path, const uint8_t *rgb, int32_t width, int32_t he
  * is not on the device are RT_ERR_ARG; no such device or a HIP error RT_ERR_DEVICE.
  * Both only read the device copy of the scene and use none of its workspace, so they do not fall
  * under "one render per (scene, device) in flight": they may run beside a render or a pass of the
- * same scene on the same device (rt_gbuffer works on the default stream and waits for its copy). */
+ * same scene on the same device (rt_gbuffer works on the default stream and waits for its copy); but
+ * not beside rt_scene_update_tris*, which writes what they read. */
 #define RT_GBUFFER_WORDS 16
 int rt_gbuffer(rt_scene *scene, const rt_params *params, float *out);
 int rt_gbuffer_device(rt_scene *scene, const rt_params *params, float *d_out, void *stream);

@@ -247,6 +247,12 @@ ABI = {
     "rt_history_lengths": (ctypes.c_int, [ctypes.c_void_p, _c_f]),
     "rt_history_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "rt_history_free": (None, [ctypes.c_void_p]),
+    # movable geometry: triangle updates and the BVH refit
+    "rt_scene_update_tris": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, _c_f, _c_f, _c_f]),
+    "rt_scene_update_tris_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rt_refit_view": (ctypes.c_int, [ctypes.POINTER(RtSceneView), _c_f]),
+    "rt_scene_read_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_f, _c_f, _c_f, _c_f]),
 }
 
 _lib_handle = None
@@ -435,6 +441,79 @@ class Scene:
         c = make_camera(cur["pos"] if pos is None else pos, cur["axes"] if axes is None else axes,
                         cur["tan_half_fov"] if tan_half_fov is None else tan_half_fov)
         _check(lib().rt_scene_set_camera(self._h, ctypes.byref(c)))
+
+    def update_triangles(self, first, tri, attr=None, tan=None, device=None, stream_ptr=None):
+        """rt_scene_update_tris: replace triangles [first, first + len(tri)) (post-build order) and
+        refit every node box (csrc/rt_refit.h); the tree's topology is kept.  tri (n, 12), attr (n, 16)
+        or None (kept), tan (n, 12) or None (kept): numpy arrays.  With device given
+        (rt_scene_update_tris_device) they are torch tensors on that device (float32, contiguous; their
+        data_ptr() is passed), the scene must be on that device alone, and the work is enqueued on
+        stream_ptr.  Triangles of an emissive mesh are refused; an accumulator of the scene needs
+        reset() before it renders on.  Not while anything reads the scene's device copy."""
+        if device is not None:
+            def dev_ptr(t, words):
+                if t is None:
+                    return 0, None
+                if t.dtype.itemsize != 4 or not t.is_contiguous() or t.numel() % words:
+                    raise ValueError(f"update_triangles: a contiguous float32 tensor of n x {words} words is needed")
+                return t.data_ptr(), t.numel() // words
+            p_tri, n = dev_ptr(tri, 12)
+            p_attr, na = dev_ptr(attr, 16)
+            p_tan, nt = dev_ptr(tan, 12)
+            if n is None or any(k is not None and k != n for k in (na, nt)):
+                raise ValueError("update_triangles: tri is needed, and attr and tan must hold as many records")
+            _check(lib().rt_scene_update_tris_device(self._h, int(device), int(first), n, ctypes.c_void_p(p_tri),
+                                                     ctypes.c_void_p(p_attr), ctypes.c_void_p(p_tan),
+                                                     ctypes.c_void_p(stream_ptr or 0)))
+            return
+        if tri is None:
+            raise ValueError("update_triangles: tri is needed")
+        tri = np.ascontiguousarray(tri, np.float32).reshape(-1, 12)
+        n = len(tri)
+        attr = None if attr is None else np.ascontiguousarray(attr, np.float32).reshape(-1, 16)
+        tan = None if tan is None else np.ascontiguousarray(tan, np.float32).reshape(-1, 12)
+        if any(x is not None and len(x) != n for x in (attr, tan)):
+            raise ValueError("update_triangles: attr and tan must hold as many records as tri")
+        _check(lib().rt_scene_update_tris(self._h, int(first), n, tri.ctypes.data_as(_c_f),
+                                          attr.ctypes.data_as(_c_f) if attr is not None else None,
+                                          tan.ctypes.data_as(_c_f) if tan is not None else None))
+
+    def translated_records(self, mesh, offset, cover=False):
+        """The easy way to move an object: [(first, tri), ...], one entry per run of consecutive
+        triangles of `mesh`, with v0 + offset (one float32 add per component; U, V and the normals are
+        unchanged), for update_triangles.  An emissive mesh is refused (lights do not move).
+        cover=True: the post-build order scatters a mesh's triangles and every update refits the whole
+        tree, so the entries are instead the range from the mesh's first to its last triangle, cut only
+        at emissive triangles, with the other meshes' records in between as the scene holds them: the
+        same result in far fewer calls."""
+        v = self.view()
+        mesh = int(mesh)
+        if not 0 <= mesh < len(v["mesh_f"]):
+            raise ValueError(f"translated_records: no mesh {mesh}")
+        if np.any(v["mesh_f"][mesh, 3:6] != 0):
+            raise ValueError(f"translated_records: mesh {mesh} is emissive; moving lights are not supported")
+        ids = np.flatnonzero(v["tri_attr"][:, 15].view(np.int32) == mesh)
+        off = np.asarray(offset, np.float32).reshape(3)
+        mesh_of = v["tri_attr"][:, 15].view(np.int32)
+        mine = mesh_of == mesh
+        moved = v["tri"].copy()
+        moved[mine, 0:3] = moved[mine, 0:3] + off
+        if cover and len(ids):
+            lit = np.any(v["mesh_f"][:, 3:6] != 0, axis=1)[mesh_of]
+            span = np.arange(ids[0], ids[-1] + 1)
+            ids = span[~lit[span]]
+        return [(int(run[0]), moved[run]) for run in np.split(ids, np.flatnonzero(np.diff(ids) != 1) + 1)] if len(ids) else []
+
+    def read_device(self, device=0):
+        """rt_scene_read_device (test / inspection): the device copy's tri, tri_attr, tri_tan and node
+        arrays in the host layout (nodes in build order), as a dict."""
+        v = RtSceneView()
+        _check(lib().rt_scene_get_view(self._h, ctypes.byref(v)))
+        out = {"tri": np.zeros((v.n_tris, 12), np.float32), "tri_attr": np.zeros((v.n_tris, 16), np.float32),
+               "tri_tan": np.zeros((v.n_tris, 12), np.float32), "node": np.zeros((v.n_nodes, 8), np.float32)}
+        _check(lib().rt_scene_read_device(self._h, int(device), *[out[k].ctypes.data_as(_c_f)
+                                                                  for k in ("tri", "tri_attr", "tri_tan", "node")]))
+        return out
 
     def history(self, device=0):
         """rt_history_create: a reprojected temporal history of this scene's frame on `device`
@@ -887,6 +966,16 @@ def make_view(a):
     v.n_textures, v.tex_info = len(a["tex_info"]), ptr("tex_info", np.uint32, _c_u)
     v.texels, v.n_texel_bytes = ptr("texels", np.uint8, _c_b), int(np.asarray(a["texels"]).size)
     return v, keep
+
+
+def refit_view(arrays):
+    """rt_refit_view (a pure host function): the (n_nodes, 8) node array of the view's topology with
+    every box recomputed from its triangles by the refit rule (csrc/rt_refit.h); a and b copied."""
+    v, keep = make_view(arrays)
+    out = np.zeros((len(arrays["node"]), 8), np.float32)
+    _check(lib().rt_refit_view(ctypes.byref(v), out.ctypes.data_as(_c_f)))
+    del keep
+    return out
 
 
 def parse_scene_gltf(path, width, height, samples):

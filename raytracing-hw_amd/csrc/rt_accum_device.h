@@ -215,7 +215,7 @@ int accum_new(rt_scene *s, const rt_params *p, const char *who, rt_accum **out, 
     Shard sh;
     if (int rc = shard_of(s, p, who, sh)) return rc;
     rt_accum *a = new rt_accum();
-    a->scene = s, a->kind = kind, a->epoch = s->cam_epoch;
+    a->scene = s, a->kind = kind, a->epoch = s->view_epoch;
     a->p = *p;
     a->p.spp = 0, a->p.world = sh.world, a->p.row_block = sh.row_block;
     a->rows = sh.rows, a->n_pixels = sh.n_pixels, a->geom = sh.g;
@@ -249,11 +249,12 @@ int accum_wait(rt_accum *a) {
     return RT_OK;
 }
 
-// The scene's camera has moved since the accumulator's samples were rendered (rt_scene_set_camera):
-// only the read-outs of the old view still work; everything else asks for rt_accum_reset.
+// The scene's camera or triangles have moved since the accumulator's samples were rendered
+// (rt_scene_set_camera, rt_scene_update_tris*): only the read-outs of the old view still work;
+// everything else asks for rt_accum_reset.
 int accum_stale(const rt_accum *a, const std::string &who) {
-    if (a->epoch == a->scene->cam_epoch) return RT_OK;
-    return rt_fail(RT_ERR_ARG, who + ": the scene's camera has changed since this accumulator's samples were rendered; "
+    if (a->epoch == a->scene->view_epoch) return RT_OK;
+    return rt_fail(RT_ERR_ARG, who + ": the scene's camera or geometry has changed since this accumulator's samples were rendered; "
                                      "call rt_accum_reset (its sums, counts and moments still read out the old view)");
 }
 
@@ -676,7 +677,7 @@ int rt_accum_reset(rt_accum *a, void *stream) {
     static_cast<rtap::State &>(*a) = rtap::State{};
     a->fast_c = fast_c;
     a->gbuf_ready = false;
-    a->epoch = a->scene->cam_epoch;
+    a->epoch = a->scene->view_epoch;
     return RT_OK;
 }
 

@@ -6,10 +6,13 @@
 //
 //   bfs_nodes   same records renumbered breadth-first: siblings stay adjacent and the top
 //               levels become a prefix (the levels nearly every ray visits share lines).
+//               A child's id is larger than its parent's and a tree level is a contiguous id
+//               range; order_out (optional) receives the old ids in new order (rt_refit_plan.h).
 // Visits, counters and results do not depend on node numbering.
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 namespace rtd {
@@ -20,9 +23,10 @@ inline uint32_t node_word(const std::vector<float> &n, size_t id, int w) {
     return x;
 }
 
-inline std::vector<float> bfs_nodes(const std::vector<float> &node) {
+inline std::vector<float> bfs_nodes(const std::vector<float> &node, std::vector<uint32_t> *order_out = nullptr) {
     const size_t n = node.size() / 8;
     std::vector<float> out(node.size());
+    if (order_out) order_out->clear();
     if (n == 0) return out;
     std::vector<uint32_t> order;   // old ids in new order
     order.reserve(n);
@@ -46,6 +50,7 @@ inline std::vector<float> bfs_nodes(const std::vector<float> &node) {
             std::memcpy(&out[8 * k + 6], &na, 4);
         }
     }
+    if (order_out) *order_out = std::move(order);
     return out;
 }
 

@@ -70,6 +70,8 @@
 #include "rt_denoise.h"
 #include "rt_denoise_guided.h"
 #include "rt_temporal.h"
+#include "rt_refit.h"
+#include "rt_refit_plan.h"
 
 using rtd::Counters;
 using rtd::DevScene;
@@ -128,6 +130,9 @@ struct rt_device_scene {
     // pixel order of the current render (heaviest first, spread; see launch_order)
     void *order_buf = nullptr;
     size_t order_bytes = 0;
+    // rt_scene_update_tris: the new records on their way into the arrays (rt_refit_device.h)
+    void *refit_stage = nullptr;
+    size_t refit_stage_bytes = 0;
     // rt_render_frame's, kept between frames: the device's render and copy streams, two shard
     // buffers (float sums then 8-bit rows) and the events that order their reuse; on the root
     // device also the root buffer: staging, frame and row map (sizes and offsets: rt_frame_plan.h)
@@ -559,7 +564,7 @@ int ensure_blob(rt_scene *s) {
     b->o_tri = append(blob, s->tri);
     b->o_attr = append(blob, s->tri_attr);
     b->o_tan = append(blob, s->tri_tan);
-    b->o_node = append(blob, rtd::bfs_nodes(s->node), 32);
+    b->o_node = append(blob, rtd::bfs_nodes(s->node, &s->bfs_order), 32);   // (the order: rt_refit_plan.h)
     b->o_light = append(blob, s->light);
     b->o_lnode = append(blob, s->light_node);
     b->o_mf = append(blob, s->mesh_f);
@@ -603,7 +608,7 @@ void free_device_scene(rt_device_scene *d) {
         for (hipStream_t q : {d->fr.stream, d->fr.cp_stream})
             if (q) (void)hipStreamSynchronize(q);
         for (void *p : {d->buf, (void *)d->counters, (void *)d->queue, d->wf_buf, (void *)d->wf_count,
-                        (void *)d->wf_fetch, (void *)d->fast_part, d->order_buf, d->fr.buf[0], d->fr.buf[1], d->fr.root_buf})
+                        (void *)d->wf_fetch, (void *)d->fast_part, d->order_buf, d->refit_stage, d->fr.buf[0], d->fr.buf[1], d->fr.root_buf})
             if (p) (void)hipFree(p);
         if (d->wf_host_count) (void)hipHostFree(d->wf_host_count);
         for (hipEvent_t e : {d->fr.copied[0], d->fr.copied[1], d->fr.finished, d->fr.last})
@@ -1288,6 +1293,7 @@ int rt_render(rt_scene *s, const rt_params *p, float *out, rt_stats *st) {
 #include "rt_denoise_device.h"   // the feature buffer and the denoiser: kernels, launch functions, entries
 #include "rt_accum_device.h"     // rt_accum_*: the accumulator's kernels, helpers and entries
 #include "rt_temporal_device.h"  // rt_temporal_device, rt_history_*: the temporal step's kernel and the history object
+#include "rt_refit_device.h"     // rt_scene_update_tris*, rt_scene_read_device: the scatter and refit kernels and their entries
 
 // The whole frame as shards 0 .. n-1 of a (world n, row_block) split, shard r on device
 // devices[r] (include/rt_hw.h rt_render_frame).  rt_frame_plan.h defines the layout: which

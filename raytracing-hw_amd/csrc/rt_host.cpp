@@ -21,6 +21,8 @@
 #include "rt_denoise_guided.h"
 #include "rt_json.h"
 #include "rt_moments.h"
+#include "rt_refit.h"
+#include "rt_refit_plan.h"
 #include "rt_scene.h"
 #include "rt_select.h"
 #include "rt_temporal.h"
@@ -824,6 +826,7 @@ int rt_scene_get_view(const rt_scene *s, rt_scene_view *v) {
 void rt_scene_free(rt_scene *s) {
     if (!s) return;
     rt_device_scene_release(s);
+    delete s->refit_plan;
     delete s;
 }
 
@@ -850,10 +853,76 @@ int rt_scene_set_camera(rt_scene *s, const rt_camera *cam) {
     std::memcpy(s->cam_axes, cam->axes, sizeof s->cam_axes);
     std::memcpy(s->tan_half_fov, cam->tan_half_fov, sizeof s->tan_half_fov);
     for (int i = 0; i < 2; ++i) s->cam_fov[i] = 2.f * std::atan(s->tan_half_fov[i]);
-    ++s->cam_epoch;
+    ++s->view_epoch;
     rt_device_scene_set_camera(s);
     return RT_OK;
 }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------ movable geometry
+// (include/rt_hw.h rt_scene_update_tris*; the rule is csrc/rt_refit.h)
+const rtrp::Plan &rt_scene_refit_plan(rt_scene *s) {
+    if (!s->refit_plan) {
+        // the blob's builder keeps bfs_nodes' order; a scene that is on no device yet computes it here
+        s->refit_plan = s->bfs_order.size() == s->node.size() / 8 && !s->bfs_order.empty()
+                            ? new rtrp::Plan(rtrp::make_plan(s->node, s->bfs_order, s->mesh_f))
+                            : new rtrp::Plan(rtrp::make_plan(s->node, s->mesh_f));
+    }
+    return *s->refit_plan;
+}
+
+int rt_update_tris_check(rt_scene *s, const char *who, uint32_t first, uint32_t count, const float *tri) {
+    if (!s) return rt_fail(RT_ERR_ARG, std::string(who) + ": NULL scene");
+    if (!tri) return rt_fail(RT_ERR_ARG, std::string(who) + ": NULL tri");
+    const uint64_t n_tris = s->tri.size() / 12;
+    if ((uint64_t)first + count > n_tris)
+        return rt_fail(RT_ERR_ARG, std::string(who) + ": triangles [" + std::to_string(first) + ", " +
+                                       std::to_string((uint64_t)first + count) + ") beyond the scene's " + std::to_string(n_tris));
+    if (count == 0) return RT_OK;
+    const rtrp::Plan &plan = rt_scene_refit_plan(s);
+    for (uint32_t k = first; k < first + count; ++k) {
+        const uint32_t m = as_u32(s->tri_attr[16 * (size_t)k + 15]);
+        if (m < plan.mesh_emissive.size() && plan.mesh_emissive[m])
+            return rt_fail(RT_ERR_ARG, std::string(who) + ": triangle " + std::to_string(k) + " belongs to the emissive mesh " +
+                                           std::to_string(m) + "; moving lights are not supported (the light list and the "
+                                           "light BVH are not remapped)");
+    }
+    return RT_OK;
+}
+
+extern "C" {
+
+int rt_refit_view(const rt_scene_view *v, float *out_node) {
+    if (!v || !out_node || !v->node || (v->n_tris && !v->tri)) return rt_fail(RT_ERR_ARG, "rt_refit_view: NULL argument");
+    const size_t nn = v->n_nodes;
+    for (size_t i = 0; i < nn; ++i) {   // what the sweep relies on (rt_scene_from_view's checks)
+        const uint32_t a = as_u32(v->node[8 * i + 6]), b = as_u32(v->node[8 * i + 7]);
+        if (rtrf::is_leaf(b) ? (uint64_t)a + (b >> 2) > v->n_tris : (b > 2 || a <= i || (size_t)a + 1 >= nn))
+            return rt_fail(RT_ERR_ARG, "rt_refit_view: bad node " + std::to_string(i));
+    }
+    std::memcpy(out_node, v->node, nn * 8 * sizeof(float));
+    rtrf::refit_sweep(v->tri, out_node, nn);
+    return RT_OK;
+}
+
+int rt_scene_update_tris(rt_scene *s, uint32_t first, uint32_t count, const float *tri, const float *tri_attr,
+                         const float *tri_tan) {
+    if (int rc = rt_update_tris_check(s, "rt_scene_update_tris", first, count, tri)) return rc;
+    if (count == 0) return RT_OK;
+    std::memcpy(&s->tri[12 * (size_t)first], tri, (size_t)count * 12 * sizeof(float));
+    if (tri_attr)
+        for (uint32_t k = 0; k < count; ++k)   // (word 15, the mesh id, stays: a triangle never changes mesh)
+            std::memcpy(&s->tri_attr[16 * (size_t)(first + k)], tri_attr + 16 * (size_t)k, 15 * sizeof(float));
+    if (tri_tan) std::memcpy(&s->tri_tan[12 * (size_t)first], tri_tan, (size_t)count * 12 * sizeof(float));
+    rtrf::refit_sweep(s->tri.data(), s->node.data(), s->node.size() / 8);
+    ++s->view_epoch;
+    return rt_device_scene_update_tris(s, first, count, tri_attr != nullptr, tri_tan != nullptr);
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int64_t rt_shard_rows(int32_t height, int32_t rank, int32_t world, int32_t row_block, int32_t *rows_out) {
     return rt_shard_rows_impl(height, rank, world, row_block, rows_out);

@@ -66,11 +66,21 @@
 //                       or RT_DENOISE_GUIDED then filter the integrated mean at spp 1 with the
 //                       history's G-buffer.  A still camera gains nothing this way (parity frames of
 //                       one view are identical): RT_PASS_SPP is the tool for a still view.
+// Moving objects (rt_scene_update_tris; unset, every byte written is the one above):
+//   RT_MOVES=file       one frame per line, groups of four numbers `mesh dx dy dz`: the mesh's triangles
+//                       are drawn with v0 + (dx, dy, dz), an offset from the loaded position (a mesh a
+//                       line does not name is at its loaded position; empty lines and lines that start
+//                       with # are skipped).  Frames are written as RT_CAMERAS writes them
+//                       (out.0000.ppm, ...), and the exclusions are RT_CAMERAS'.  With RT_CAMERAS both
+//                       files must hold as many frames.  A malformed line, an unknown mesh and an
+//                       emissive mesh (lights do not move) are errors that name the line, reported
+//                       before anything is rendered.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <iostream>
 #include <iomanip>
@@ -392,6 +402,100 @@ static bool read_cameras(const char *path, std::vector<rt_camera> &cams, std::st
     return true;
 }
 
+// RT_MOVES: the file's frames (a frame: the meshes it names and their offsets), or false and why.
+struct Move {
+    uint32_t mesh;
+    float d[3];
+};
+static bool read_moves(const char *path, const rt_scene_view &view, std::vector<std::vector<Move>> &frames, std::string &why) {
+    std::ifstream f(path);
+    if (!f) {
+        why = std::string("RT_MOVES: cannot read ") + path;
+        return false;
+    }
+    std::string line;
+    for (int no = 1; std::getline(f, line); ++no) {
+        const size_t first = line.find_first_not_of(" \t\r");
+        if (first == std::string::npos || line[first] == '#') continue;
+        const std::string where = std::string("RT_MOVES: ") + path + " line " + std::to_string(no) + ": ";
+        std::istringstream in(line);
+        std::vector<std::string> tok;
+        for (std::string t; in >> t;) tok.push_back(t);
+        if (tok.size() % 4 != 0) {
+            why = where + "expected groups of four numbers: mesh dx dy dz";
+            return false;
+        }
+        std::vector<Move> frame;
+        for (size_t k = 0; k < tok.size(); k += 4) {
+            char *end = nullptr;
+            const long long m = std::strtoll(tok[k].c_str(), &end, 10);
+            if (end == tok[k].c_str() || *end != '\0') {
+                why = where + "expected groups of four numbers: mesh dx dy dz";
+                return false;
+            }
+            if (m < 0 || m >= (long long)view.n_meshes) {
+                why = where + "unknown mesh " + tok[k] + " (the scene has " + std::to_string(view.n_meshes) + ")";
+                return false;
+            }
+            const float *e = view.mesh_f + 12 * (size_t)m + 3;
+            if (e[0] != 0.f || e[1] != 0.f || e[2] != 0.f) {
+                why = where + "mesh " + tok[k] + " is emissive; moving lights are not supported";
+                return false;
+            }
+            Move mv{(uint32_t)m, {0.f, 0.f, 0.f}};
+            for (int c = 0; c < 3; ++c) {
+                const std::string &t = tok[k + 1 + (size_t)c];
+                mv.d[c] = std::strtof(t.c_str(), &end);
+                if (end == t.c_str() || *end != '\0' || !std::isfinite(mv.d[c])) {
+                    why = where + "expected groups of four numbers: mesh dx dy dz (finite offsets)";
+                    return false;
+                }
+            }
+            frame.push_back(mv);
+        }
+        frames.push_back(frame);
+    }
+    if (frames.empty()) {
+        why = std::string("RT_MOVES: no frame in ") + path;
+        return false;
+    }
+    return true;
+}
+
+// RT_MOVES: the scene's triangles as frame `now` places them, given what frame `before` (NULL: none)
+// had moved.  `base`: the loaded tri array.  A triangle of a mesh `now` names gets v0 = loaded v0 +
+// offset (one f32 add per component); every other one is at its loaded position.  A mesh's triangles
+// lie scattered in post-build order and every call refits the whole tree, so the update is the range
+// from the first to the last triangle of the meshes either frame names, cut only at emissive
+// triangles (which may not be touched): few calls, the other meshes' records in between as they are.
+static void apply_moves(rt_scene *scene, const std::vector<float> &base, const std::vector<uint32_t> &tri_mesh,
+                        const std::vector<uint8_t> &mesh_emissive, const std::vector<Move> *before, const std::vector<Move> &now) {
+    std::vector<const Move *> move_of(mesh_emissive.size(), nullptr);
+    std::vector<uint8_t> touched(mesh_emissive.size(), 0);
+    if (before)
+        for (const Move &m : *before) touched[m.mesh] = 1;
+    for (const Move &m : now) touched[m.mesh] = 1, move_of[m.mesh] = &m;   // (named twice: the last group holds)
+    const size_t n = tri_mesh.size();
+    size_t lo = n, hi = 0;
+    for (size_t t = 0; t < n; ++t)
+        if (touched[tri_mesh[t]]) lo = std::min(lo, t), hi = t + 1;
+    std::vector<float> rec;
+    for (size_t k = lo; k < hi;) {
+        if (mesh_emissive[tri_mesh[k]]) {
+            ++k;
+            continue;
+        }
+        size_t e = k;
+        while (e < hi && !mesh_emissive[tri_mesh[e]]) ++e;
+        rec.assign(base.begin() + 12 * (long)k, base.begin() + 12 * (long)e);
+        for (size_t t = k; t < e; ++t)
+            if (const Move *mv = move_of[tri_mesh[t]])
+                for (int c = 0; c < 3; ++c) rec[12 * (t - k) + (size_t)c] = rec[12 * (t - k) + (size_t)c] + mv->d[c];
+        check(rt_scene_update_tris(scene, (uint32_t)k, (uint32_t)(e - k), rec.data(), nullptr, nullptr));
+        k = e;
+    }
+}
+
 // out.ppm -> out.0003.ppm (a name without an extension: the index appended).
 static std::string indexed_name(const std::string &path, size_t k) {
     char idx[16];
@@ -401,11 +505,13 @@ static std::string indexed_name(const std::string &path, size_t k) {
     return path.substr(0, dot) + idx + path.substr(dot);
 }
 
-// RT_CAMERAS: one one-shot frame per camera through the existing frame path; with `temporal`
-// (RT_TEMPORAL) every frame's sums pass through a history on device 0 before the finish.
+// RT_CAMERAS, RT_MOVES: one one-shot frame per camera (`cams` empty: the scene's camera for every frame
+// of `moves`) through the existing frame path; `moves` (empty: nothing moves) places the objects
+// before each frame; with `temporal` (RT_TEMPORAL) every frame's sums pass through a history on
+// device 0 before the finish.
 static void render_cameras(rt_scene *scene, int width, int height, int samples, int n_gpus, int fast_chunk, Denoise &dn,
-                           const std::vector<rt_camera> &cams, const std::string &output, bool temporal, float alpha,
-                           const char *aov_out) {
+                           const std::vector<rt_camera> &cams, const std::vector<std::vector<Move>> &moves,
+                           const std::string &output, bool temporal, float alpha, const char *aov_out) {
     struct Held {   // (freed on every way out, before the scene)
         rt_history *h = nullptr;
         ~Held() { rt_history_free(h); }
@@ -420,8 +526,24 @@ static void render_cameras(rt_scene *scene, int width, int height, int samples, 
     rt_temporal_params tp{alpha, 0.f, 0.f, 0.f, 0};
     std::vector<uint8_t> rgb((size_t)width * height * 3);
     std::vector<float> sums;
-    for (size_t k = 0; k < cams.size(); ++k) {
-        check(rt_scene_set_camera(scene, &cams[k]));
+    std::vector<float> base;          // RT_MOVES: the loaded triangles and their meshes
+    std::vector<uint32_t> tri_mesh;
+    std::vector<uint8_t> mesh_emissive;
+    if (!moves.empty()) {
+        rt_scene_view v;
+        check(rt_scene_get_view(scene, &v));
+        base.assign(v.tri, v.tri + 12 * (size_t)v.n_tris);
+        tri_mesh.resize(v.n_tris);
+        for (size_t t = 0; t < v.n_tris; ++t) std::memcpy(&tri_mesh[t], v.tri_attr + 16 * t + 15, 4);
+        for (size_t m = 0; m < v.n_meshes; ++m) {
+            const float *e = v.mesh_f + 12 * m + 3;
+            mesh_emissive.push_back(e[0] != 0.f || e[1] != 0.f || e[2] != 0.f);
+        }
+    }
+    const size_t n_frames = cams.empty() ? moves.size() : cams.size();
+    for (size_t k = 0; k < n_frames; ++k) {
+        if (!cams.empty()) check(rt_scene_set_camera(scene, &cams[k]));
+        if (!moves.empty()) apply_moves(scene, base, tri_mesh, mesh_emissive, k ? &moves[k - 1] : nullptr, moves[k]);
         rt_stats st{};
         if (temporal || dn.on) {
             sums.resize((size_t)width * height * 3);
@@ -514,7 +636,9 @@ int main(int argc, char *argv[]) {
     }
     dn.measured = moments;
     const char *cams_env = std::getenv("RT_CAMERAS"), *temporal_env = std::getenv("RT_TEMPORAL");
+    const char *moves_env = std::getenv("RT_MOVES");
     const bool cams_on = cams_env && *cams_env, temporal_on = temporal_env && *temporal_env;
+    const bool moves_on = moves_env && *moves_env;
     if (temporal_on && !cams_on) {
         std::cerr << "rt_solution: RT_TEMPORAL needs RT_CAMERAS (a still view gains nothing from a history: use RT_PASS_SPP)" << std::endl;
         rt_scene_free(scene);
@@ -525,17 +649,35 @@ int main(int argc, char *argv[]) {
         rt_scene_free(scene);
         return 1;
     }
-    if (cams_on) {
+    if (moves_on && ((pass_env && *pass_env) || (ckpt && *ckpt) || adaptive)) {
+        std::cerr << "rt_solution: RT_MOVES excludes RT_PASS_SPP, RT_ADAPT and RT_CHECKPOINT (one one-shot frame per line)" << std::endl;
+        rt_scene_free(scene);
+        return 1;
+    }
+    if (cams_on || moves_on) {
         std::vector<rt_camera> cams;
+        std::vector<std::vector<Move>> moves;
         std::string why;
         const float alpha = temporal_on ? std::strtof(temporal_env, nullptr) : 0.f;
-        if (!read_cameras(cams_env, cams, why) || !(alpha >= 0.f && alpha <= 1.f)) {
+        bool ok = !cams_on || read_cameras(cams_env, cams, why);
+        if (ok && moves_on) {
+            rt_scene_view v;
+            check(rt_scene_get_view(scene, &v));
+            ok = read_moves(moves_env, v, moves, why);
+            if (ok && cams_on && cams.size() != moves.size()) {
+                why = "RT_CAMERAS holds " + std::to_string(cams.size()) + " frames and RT_MOVES " + std::to_string(moves.size()) +
+                      ": the line counts must be equal";
+                ok = false;
+            }
+        }
+        if (!ok || !(alpha >= 0.f && alpha <= 1.f)) {
             std::cerr << "rt_solution: " << (why.empty() ? std::string("RT_TEMPORAL must be in 0..1") : why) << std::endl;
             rt_scene_free(scene);
             return 1;
         }
+        const size_t n_frames = cams_on ? cams.size() : moves.size();
         try {
-            render_cameras(scene, width, height, samples, n_gpus, fast_chunk, dn, cams, output, temporal_on, alpha, aov_out);
+            render_cameras(scene, width, height, samples, n_gpus, fast_chunk, dn, cams, moves, output, temporal_on, alpha, aov_out);
         } catch (const std::exception &e) {
             std::cerr << "rt_solution: " << e.what() << std::endl;
             rt_scene_free(scene);
@@ -543,7 +685,7 @@ int main(int argc, char *argv[]) {
         }
         double total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::cout << "      " << total << " seconds (" << total * 1000 << " ms) elapsed." << std::endl;
-        std::cout << cams.size() << " frames drawn into " << indexed_name(output, 0) << " .. " << indexed_name(output, cams.size() - 1)
+        std::cout << n_frames << " frames drawn into " << indexed_name(output, 0) << " .. " << indexed_name(output, n_frames - 1)
                   << std::endl;
         rt_scene_free(scene);
         return 0;

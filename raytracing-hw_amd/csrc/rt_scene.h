@@ -8,6 +8,9 @@
 
 struct rt_device_scene;  // owned by rt_device.hip: one per device the scene is uploaded to
 struct rt_device_blob;   // owned by rt_device.hip: the device image of the scene, built once
+namespace rtrp {
+struct Plan;             // rt_refit_plan.h: owned by rt_host.cpp
+}
 
 constexpr int kRtMaxDevices = 64;
 
@@ -18,7 +21,7 @@ struct rt_scene {
     float cam_axes[9] = {0};
     float cam_fov[2] = {0, 0};
     float tan_half_fov[2] = {0, 0};
-    uint32_t cam_epoch = 0;   // rt_scene_set_camera calls so far (an accumulator remembers the one it renders)
+    uint32_t view_epoch = 0;   // rt_scene_set_camera and rt_scene_update_tris* calls so far (an accumulator remembers the one it renders)
 
     std::vector<float> tri, tri_attr, tri_tan, node;
     uint32_t bvh_depth = 0;
@@ -32,6 +35,8 @@ struct rt_scene {
 
     rt_device_scene *dev[kRtMaxDevices] = {};   // [HIP device id]
     rt_device_blob *blob = nullptr;
+    rtrp::Plan *refit_plan = nullptr;           // made by the first rt_scene_update_tris* (rt_refit_plan.h)
+    std::vector<uint32_t> bfs_order;            // build-order ids in the device's numbering, kept by the blob's builder
 };
 
 // error plumbing shared by rt_host.cpp and rt_device.hip
@@ -42,6 +47,15 @@ int rt_fail(int code, const std::string &msg);
 void rt_device_scene_release(rt_scene *s);
 // implemented in rt_device.hip: the scene's camera into the launch arguments of every device copy
 void rt_device_scene_set_camera(rt_scene *s);
+
+// movable geometry (include/rt_hw.h rt_scene_update_tris*), rt_host.cpp:
+// the scene's refit plan, made on first use
+const rtrp::Plan &rt_scene_refit_plan(rt_scene *s);
+// every refusal both entries share (NULL tri, the range, an emissive mesh's triangle); nothing is changed
+int rt_update_tris_check(rt_scene *s, const char *who, uint32_t first, uint32_t count, const float *tri);
+// implemented in rt_device.hip: after the host arrays took the new records and the refit boxes, the
+// cached device image is patched and every device copy takes the range and refits its own boxes; waits
+int rt_device_scene_update_tris(rt_scene *s, uint32_t first, uint32_t count, bool attr, bool tan);
 
 // argument checks of rt_denoise / rt_denoise_device (rt_host.cpp): RT_OK and the resolved
 // parameters (rt_denoise.h), or the failure as `who` reports it

@@ -23,6 +23,8 @@
 #   kt=N                 kernel trace of all N shards (tools/kt_shards.sh)  kt_shards_*.csv
 #   rehearsal=N          bench.py --gpus N as N ranks sharing one GPU       rehearsal_wN.json
 #   calib                FETCH_SIZE calibration of the kernel's load widths (tools/fetch_calib)
+#   refit[=REPS]         triangle update and refit against free + from_view + upload on the headline
+#                        scene (tools/refit_time.py), REPS repetitions (5)     refit_time.jsonl
 set -o pipefail
 cd "$(dirname "$0")/.."
 TAG=$1; shift
@@ -110,6 +112,10 @@ for step in "$@"; do
     calib)
       timeout -k 10 300 bash tools/fetch_calib.sh "$TAG" > "$OUT/calib.log" 2>&1 || fail calib "$OUT/calib.log"
       tail -12 "$OUT/calib.log" ;;
+    refit)
+      timeout -k 10 240 python3 tools/refit_time.py --reps "${arg:-5}" --label "$TAG" --out "$OUT/refit_time.jsonl" \
+        > "$OUT/refit_time.log" 2>&1 || fail refit "$OUT/refit_time.log"
+      tail -2 "$OUT/refit_time.jsonl" ;;
     *) echo "[steps] unknown step $step"; exit 2 ;;
   esac
 done
