@@ -240,7 +240,8 @@ int rt_scene_set_camera(rt_scene *scene, const rt_camera *cam);
  * waits.  The scene must be uploaded to `device` and to no other device.
  * Refusals, all before any launch or copy (nothing is left half made): NULL tri, a range beyond
  * n_tris, a triangle of the range that belongs to an emissive mesh (mesh_f emission not all zero;
- * moving lights are not supported: the light records and the light BVH are not remapped), and for the
+ * moving lights are not supported: the light records and the light BVH are not remapped; a scene that
+ * opted in with rt_scene_enable_light_updates, below, is not refused this), and for the
  * device entry a scene that is not on `device`, or also on another, or a misaligned pointer:
  * RT_ERR_ARG.  count == 0 is RT_OK and nothing happens.
  * Both fall under "one render per (scene, device) in flight", and so do rt_gbuffer*, rt_history_push and
@@ -266,6 +267,61 @@ int rt_refit_view(const rt_scene_view *view, float *out_node);
 /* Test / inspection entry: the device copy's arrays back in the host layout, nodes in build order.
  * Any pointer may be NULL. */
 int rt_scene_read_device(rt_scene *scene, int32_t device, float *tri, float *tri_attr, float *tri_tan, float *node);
+
+/* --- movable lights: emissive triangle updates, light list and light-BVH refit (additive in ABI 6) - */
+/* Opt-in: until rt_scene_enable_light_updates succeeds on a scene, everything above holds as written,
+ * the refusal of an emissive triangle included.  After it, rt_scene_update_tris* accept ranges that
+ * hold triangles of emissive meshes and keep the light list (`light`, 16 words per light) and the light
+ * BVH (`light_node`) in step; every other refusal stays.  csrc/rt_relight.h is the rule's text, shared
+ * by the host functions, the device kernels and the CPU tests:
+ *   record    words 0..11 of a light are its triangle's 12 words as given (the caller's geometric normal
+ *             in words 9..11 included; nothing is normalised); word 12 is the area 0.5f * length(cross(U, V)),
+ *             every operation one f32 rounding, no fused multiply-add:
+ *               cross(a, b) = (a.y*b.z - b.y*a.z, a.z*b.x - b.z*a.x, a.x*b.y - b.x*a.y)
+ *               length(v)   = sqrt(((0 + v.x*v.x) + v.y*v.y) + v.z*v.z), correctly rounded sqrt
+ *             words 13..15 are never written
+ *   boxes     the rule above over the light records: v0, U, V are words 0..8 of a 16-word record, a light
+ *             leaf folds lights first .. first + count - 1 in order, an internal node grow(left) then
+ *             grow(right), every fold from the empty box, the same selects
+ * These are the reference's light records and boxes for the same triangles in the same order
+ * (Primitive::get_geometric_normal primitive.cpp:77-84; the light list and its BVH random.cpp:156-168).
+ * The order of the lights and the light tree's topology are kept: a moved light keeps its index.
+ *
+ * The map.  Light k restates triangle tri_of_light[k]: the lights are walked in ascending index, and
+ * light k takes the lowest-numbered triangle of an emissive mesh (mesh_f emission not all zero) that is
+ * not yet taken and whose 12 words equal the light's words 0..11 bit for bit.  Both a loaded scene and
+ * one from rt_scene_from_view follow this rule.  rt_scene_enable_light_updates builds the map and the
+ * light tree's levels on the host (it works on a scene that is on no device, and is idempotent).  It
+ * fails with RT_ERR_ARG, naming the first such light or triangle, if a light finds no triangle or an
+ * emissive triangle is left without a light, or if the light tree is not what the refit relies on (leaf
+ * ranges within n_lights, children above their parents); the scene then stays as it was, not opted in.
+ * rt_scene_light_map copies tri_of_light (n_lights words); RT_ERR_ARG before the opt-in.
+ *
+ * Updates on an opted-in scene.  The host entry restates the light records of the range's light
+ * triangles and every light box in the host arrays, patches the cached image, and on every device copy
+ * launches, after the triangle scatter and the node refit, the light scatter (one thread per triangle of
+ * the range) and one launch per level of the light tree, deepest first; the kernel boundary is the only
+ * ordering.  The device entry does the same on `stream` and reads the light array and the light node
+ * array back into the host arrays and the image before it returns.  A range that holds no light triangle
+ * launches none of the light kernels and reads no light data back.  A device copy's first update after
+ * the opt-in puts the map and the level lists into a small allocation of that copy.
+ *
+ * Contract: after an update on an opted-in scene every entry named in the contract above behaves bit for
+ * bit as on rt_scene_from_view(the same arrays, node = rt_refit_view(...), light and light_node =
+ * rt_relight_view(...)).  One exception: where a light's area is NaN, host and device may store different
+ * NaN bit patterns (an invalid operation yields different default NaNs on the two); nothing is
+ * canonicalised.  The epoch rule is unchanged: an update bumps the scene's epoch.
+ * Limits: topology kept, no rebuild, and the light order kept (the reference picks a light uniformly by
+ * index; a fresh build of the moved scene might order the lights differently). */
+int rt_scene_enable_light_updates(rt_scene *scene);
+int rt_scene_light_map(const rt_scene *scene, uint32_t *tri_of_light);
+/* Pure host function, the twin of rt_refit_view: out_light (n_lights x 16) is the view's `light` with words
+ * 0..12 of every light restated from triangle tri_of_light[k] (words 13..15 copied); out_light_node
+ * (n_light_nodes x 8) is the view's `light_node` with every box recomputed by the sweep, a and b copied. */
+int rt_relight_view(const rt_scene_view *view, const uint32_t *tri_of_light, float *out_light, float *out_light_node);
+/* Test / inspection entry: the device copy's light and light_node arrays (the host layout).  Either
+ * pointer may be NULL. */
+int rt_scene_read_device_lights(rt_scene *scene, int32_t device, float *light, float *light_node);
 
 /* --- render ----------------------------------------------------------------------- */
 /* Copies the scene to `device` (once per device; later calls reuse it).  One render per

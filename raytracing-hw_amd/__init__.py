@@ -253,6 +253,11 @@ ABI = {
                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "rt_refit_view": (ctypes.c_int, [ctypes.POINTER(RtSceneView), _c_f]),
     "rt_scene_read_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_f, _c_f, _c_f, _c_f]),
+    # movable lights: the opt-in, the light map, the light list and light-BVH refit
+    "rt_scene_enable_light_updates": (ctypes.c_int, [ctypes.c_void_p]),
+    "rt_scene_light_map": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
+    "rt_relight_view": (ctypes.c_int, [ctypes.POINTER(RtSceneView), ctypes.POINTER(ctypes.c_uint32), _c_f, _c_f]),
+    "rt_scene_read_device_lights": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_f, _c_f]),
 }
 
 _lib_handle = None
@@ -478,10 +483,37 @@ class Scene:
                                           attr.ctypes.data_as(_c_f) if attr is not None else None,
                                           tan.ctypes.data_as(_c_f) if tan is not None else None))
 
-    def translated_records(self, mesh, offset, cover=False):
+    def enable_light_updates(self):
+        """rt_scene_enable_light_updates: from now on update_triangles accepts triangles of emissive
+        meshes and keeps the light list and the light BVH in step (csrc/rt_relight.h).  Idempotent;
+        raises, and leaves the scene as it was, where the light list does not restate the emissive
+        triangles one to one."""
+        _check(lib().rt_scene_enable_light_updates(self._h))
+
+    def light_map(self):
+        """rt_scene_light_map: tri_of_light, the triangle each light restates (needs the opt-in)."""
+        v = RtSceneView()
+        _check(lib().rt_scene_get_view(self._h, ctypes.byref(v)))
+        out = np.zeros(v.n_lights, np.uint32)
+        _check(lib().rt_scene_light_map(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        return out
+
+    def read_device_lights(self, device=0):
+        """rt_scene_read_device_lights (test / inspection): the device copy's light and light_node
+        arrays, as a dict."""
+        v = RtSceneView()
+        _check(lib().rt_scene_get_view(self._h, ctypes.byref(v)))
+        out = {"light": np.zeros((v.n_lights, 16), np.float32), "light_node": np.zeros((v.n_light_nodes, 8), np.float32)}
+        _check(lib().rt_scene_read_device_lights(self._h, int(device), out["light"].ctypes.data_as(_c_f),
+                                                 out["light_node"].ctypes.data_as(_c_f)))
+        return out
+
+    def translated_records(self, mesh, offset, cover=False, lights=False):
         """The easy way to move an object: [(first, tri), ...], one entry per run of consecutive
         triangles of `mesh`, with v0 + offset (one float32 add per component; U, V and the normals are
-        unchanged), for update_triangles.  An emissive mesh is refused (lights do not move).
+        unchanged), for update_triangles.  An emissive mesh is refused (lights do not move) unless
+        lights=True, which needs enable_light_updates() and then also lets a covering range run through
+        emissive triangles.
         cover=True: the post-build order scatters a mesh's triangles and every update refits the whole
         tree, so the entries are instead the range from the mesh's first to its last triangle, cut only
         at emissive triangles, with the other meshes' records in between as the scene holds them: the
@@ -490,7 +522,9 @@ class Scene:
         mesh = int(mesh)
         if not 0 <= mesh < len(v["mesh_f"]):
             raise ValueError(f"translated_records: no mesh {mesh}")
-        if np.any(v["mesh_f"][mesh, 3:6] != 0):
+        if lights:
+            self.light_map()   # (raises before the opt-in)
+        elif np.any(v["mesh_f"][mesh, 3:6] != 0):
             raise ValueError(f"translated_records: mesh {mesh} is emissive; moving lights are not supported")
         ids = np.flatnonzero(v["tri_attr"][:, 15].view(np.int32) == mesh)
         off = np.asarray(offset, np.float32).reshape(3)
@@ -501,7 +535,7 @@ class Scene:
         if cover and len(ids):
             lit = np.any(v["mesh_f"][:, 3:6] != 0, axis=1)[mesh_of]
             span = np.arange(ids[0], ids[-1] + 1)
-            ids = span[~lit[span]]
+            ids = span if lights else span[~lit[span]]
         return [(int(run[0]), moved[run]) for run in np.split(ids, np.flatnonzero(np.diff(ids) != 1) + 1)] if len(ids) else []
 
     def read_device(self, device=0):
@@ -976,6 +1010,22 @@ def refit_view(arrays):
     _check(lib().rt_refit_view(ctypes.byref(v), out.ctypes.data_as(_c_f)))
     del keep
     return out
+
+
+def relight_view(arrays, tri_of_light):
+    """rt_relight_view (a pure host function): (light, light_node) of the view with words 0..12 of every
+    light restated from triangle tri_of_light[k] and every light box recomputed (csrc/rt_relight.h);
+    words 13..15, a and b copied."""
+    v, keep = make_view(arrays)
+    tl = np.ascontiguousarray(tri_of_light, np.uint32)
+    if len(tl) != len(arrays["light"]):
+        raise ValueError("relight_view: tri_of_light must hold one triangle per light")
+    light = np.zeros((len(arrays["light"]), 16), np.float32)
+    lnode = np.zeros((len(arrays["light_node"]), 8), np.float32)
+    _check(lib().rt_relight_view(ctypes.byref(v), tl.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                 light.ctypes.data_as(_c_f), lnode.ctypes.data_as(_c_f)))
+    del keep
+    return light, lnode
 
 
 def parse_scene_gltf(path, width, height, samples):

@@ -72,6 +72,7 @@
 #include "rt_temporal.h"
 #include "rt_refit.h"
 #include "rt_refit_plan.h"
+#include "rt_relight.h"
 
 using rtd::Counters;
 using rtd::DevScene;
@@ -133,6 +134,7 @@ struct rt_device_scene {
     // rt_scene_update_tris: the new records on their way into the arrays (rt_refit_device.h)
     void *refit_stage = nullptr;
     size_t refit_stage_bytes = 0;
+    void *relight_buf = nullptr;       // movable lights: light_of_tri, then the light node ids by depth
     // rt_render_frame's, kept between frames: the device's render and copy streams, two shard
     // buffers (float sums then 8-bit rows) and the events that order their reuse; on the root
     // device also the root buffer: staging, frame and row map (sizes and offsets: rt_frame_plan.h)
@@ -608,7 +610,7 @@ void free_device_scene(rt_device_scene *d) {
         for (hipStream_t q : {d->fr.stream, d->fr.cp_stream})
             if (q) (void)hipStreamSynchronize(q);
         for (void *p : {d->buf, (void *)d->counters, (void *)d->queue, d->wf_buf, (void *)d->wf_count,
-                        (void *)d->wf_fetch, (void *)d->fast_part, d->order_buf, d->refit_stage, d->fr.buf[0], d->fr.buf[1], d->fr.root_buf})
+                        (void *)d->wf_fetch, (void *)d->fast_part, d->order_buf, d->refit_stage, d->relight_buf, d->fr.buf[0], d->fr.buf[1], d->fr.root_buf})
             if (p) (void)hipFree(p);
         if (d->wf_host_count) (void)hipHostFree(d->wf_host_count);
         for (hipEvent_t e : {d->fr.copied[0], d->fr.copied[1], d->fr.finished, d->fr.last})

@@ -23,6 +23,7 @@
 #include "rt_moments.h"
 #include "rt_refit.h"
 #include "rt_refit_plan.h"
+#include "rt_relight.h"
 #include "rt_scene.h"
 #include "rt_select.h"
 #include "rt_temporal.h"
@@ -827,6 +828,7 @@ void rt_scene_free(rt_scene *s) {
     if (!s) return;
     rt_device_scene_release(s);
     delete s->refit_plan;
+    delete s->light_plan;
     delete s;
 }
 
@@ -883,7 +885,7 @@ int rt_update_tris_check(rt_scene *s, const char *who, uint32_t first, uint32_t 
     const rtrp::Plan &plan = rt_scene_refit_plan(s);
     for (uint32_t k = first; k < first + count; ++k) {
         const uint32_t m = as_u32(s->tri_attr[16 * (size_t)k + 15]);
-        if (m < plan.mesh_emissive.size() && plan.mesh_emissive[m])
+        if (m < plan.mesh_emissive.size() && plan.mesh_emissive[m] && !s->light_plan)
             return rt_fail(RT_ERR_ARG, std::string(who) + ": triangle " + std::to_string(k) + " belongs to the emissive mesh " +
                                            std::to_string(m) + "; moving lights are not supported (the light list and the "
                                            "light BVH are not remapped)");
@@ -916,8 +918,52 @@ int rt_scene_update_tris(rt_scene *s, uint32_t first, uint32_t count, const floa
             std::memcpy(&s->tri_attr[16 * (size_t)(first + k)], tri_attr + 16 * (size_t)k, 15 * sizeof(float));
     if (tri_tan) std::memcpy(&s->tri_tan[12 * (size_t)first], tri_tan, (size_t)count * 12 * sizeof(float));
     rtrf::refit_sweep(s->tri.data(), s->node.data(), s->node.size() / 8);
+    const bool lights = s->light_plan && s->light_plan->touches(first, count);
+    if (lights) {   // the light records of the range's light triangles, then every light box (rt_relight.h)
+        for (uint32_t k = first; k < first + count; ++k)
+            if (const uint32_t l = s->light_plan->light_of_tri[k]; l != rtrp::LightPlan::kNone)
+                rtrl::light_from_tri(&s->tri[12 * (size_t)k], &s->light[16 * (size_t)l]);
+        rtrl::refit_sweep(s->light.data(), s->light_node.data(), s->light_node.size() / 8);
+    }
     ++s->view_epoch;
-    return rt_device_scene_update_tris(s, first, count, tri_attr != nullptr, tri_tan != nullptr);
+    return rt_device_scene_update_tris(s, first, count, tri_attr != nullptr, tri_tan != nullptr, lights);
+}
+
+// Movable lights (rt_relight.h, rt_refit_plan.h LightPlan).
+int rt_scene_enable_light_updates(rt_scene *s) {
+    if (!s) return rt_fail(RT_ERR_ARG, "rt_scene_enable_light_updates: NULL scene");
+    if (s->light_plan) return RT_OK;
+    rtrp::LightPlan lp;
+    const std::string why = rtrp::make_light_plan(s->tri, s->tri_attr, rt_scene_refit_plan(s).mesh_emissive, s->light, s->light_node, &lp);
+    if (!why.empty()) return rt_fail(RT_ERR_ARG, "rt_scene_enable_light_updates: " + why);
+    s->light_plan = new rtrp::LightPlan(std::move(lp));
+    return RT_OK;
+}
+
+int rt_scene_light_map(const rt_scene *s, uint32_t *tri_of_light) {
+    if (!s || !tri_of_light) return rt_fail(RT_ERR_ARG, "rt_scene_light_map: NULL argument");
+    if (!s->light_plan) return rt_fail(RT_ERR_ARG, "rt_scene_light_map: the scene has not enabled light updates");
+    std::memcpy(tri_of_light, s->light_plan->tri_of_light.data(), s->light_plan->tri_of_light.size() * sizeof(uint32_t));
+    return RT_OK;
+}
+
+int rt_relight_view(const rt_scene_view *v, const uint32_t *tri_of_light, float *out_light, float *out_light_node) {
+    if (!v || !out_light || !out_light_node || (v->n_lights && (!v->light || !tri_of_light || !v->tri)) ||
+        (v->n_light_nodes && !v->light_node))
+        return rt_fail(RT_ERR_ARG, "rt_relight_view: NULL argument");
+    const size_t nn = v->n_light_nodes;
+    for (size_t k = 0; k < v->n_lights; ++k)
+        if (tri_of_light[k] >= v->n_tris) return rt_fail(RT_ERR_ARG, "rt_relight_view: light " + std::to_string(k) + " names no triangle");
+    for (size_t i = 0; i < nn; ++i) {   // what the sweep relies on
+        const uint32_t a = as_u32(v->light_node[8 * i + 6]), b = as_u32(v->light_node[8 * i + 7]);
+        if (rtrf::is_leaf(b) ? (uint64_t)a + (b >> 2) > v->n_lights : (b > 2 || a <= i || (size_t)a + 1 >= nn))
+            return rt_fail(RT_ERR_ARG, "rt_relight_view: bad light node " + std::to_string(i));
+    }
+    if (v->n_lights) std::memcpy(out_light, v->light, (size_t)v->n_lights * 16 * sizeof(float));
+    if (nn) std::memcpy(out_light_node, v->light_node, nn * 8 * sizeof(float));
+    for (size_t k = 0; k < v->n_lights; ++k) rtrl::light_from_tri(v->tri + 12 * (size_t)tri_of_light[k], out_light + 16 * k);
+    rtrl::refit_sweep(out_light, out_light_node, nn);
+    return RT_OK;
 }
 
 }  // extern "C"

@@ -75,6 +75,9 @@
 //                       files must hold as many frames.  A malformed line, an unknown mesh and an
 //                       emissive mesh (lights do not move) are errors that name the line, reported
 //                       before anything is rendered.
+//   RT_MOVE_LIGHTS=1    (with RT_MOVES) the scene opts in to movable lights (rt_scene_enable_light_updates):
+//                       a line may name an emissive mesh, whose light records and light BVH boxes then
+//                       follow its triangles, and the covering ranges are not cut at emissive triangles.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -407,7 +410,8 @@ struct Move {
     uint32_t mesh;
     float d[3];
 };
-static bool read_moves(const char *path, const rt_scene_view &view, std::vector<std::vector<Move>> &frames, std::string &why) {
+static bool read_moves(const char *path, const rt_scene_view &view, bool move_lights, std::vector<std::vector<Move>> &frames,
+                       std::string &why) {
     std::ifstream f(path);
     if (!f) {
         why = std::string("RT_MOVES: cannot read ") + path;
@@ -438,7 +442,7 @@ static bool read_moves(const char *path, const rt_scene_view &view, std::vector<
                 return false;
             }
             const float *e = view.mesh_f + 12 * (size_t)m + 3;
-            if (e[0] != 0.f || e[1] != 0.f || e[2] != 0.f) {
+            if (!move_lights && (e[0] != 0.f || e[1] != 0.f || e[2] != 0.f)) {
                 why = where + "mesh " + tok[k] + " is emissive; moving lights are not supported";
                 return false;
             }
@@ -467,7 +471,8 @@ static bool read_moves(const char *path, const rt_scene_view &view, std::vector<
 // offset (one f32 add per component); every other one is at its loaded position.  A mesh's triangles
 // lie scattered in post-build order and every call refits the whole tree, so the update is the range
 // from the first to the last triangle of the meshes either frame names, cut only at emissive
-// triangles (which may not be touched): few calls, the other meshes' records in between as they are.
+// triangles (which may not be touched; with RT_MOVE_LIGHTS they may, and the caller passes no mesh as
+// emissive): few calls, the other meshes' records in between as they are.
 static void apply_moves(rt_scene *scene, const std::vector<float> &base, const std::vector<uint32_t> &tri_mesh,
                         const std::vector<uint8_t> &mesh_emissive, const std::vector<Move> *before, const std::vector<Move> &now) {
     std::vector<const Move *> move_of(mesh_emissive.size(), nullptr);
@@ -510,7 +515,7 @@ static std::string indexed_name(const std::string &path, size_t k) {
 // before each frame; with `temporal` (RT_TEMPORAL) every frame's sums pass through a history on
 // device 0 before the finish.
 static void render_cameras(rt_scene *scene, int width, int height, int samples, int n_gpus, int fast_chunk, Denoise &dn,
-                           const std::vector<rt_camera> &cams, const std::vector<std::vector<Move>> &moves,
+                           const std::vector<rt_camera> &cams, const std::vector<std::vector<Move>> &moves, bool move_lights,
                            const std::string &output, bool temporal, float alpha, const char *aov_out) {
     struct Held {   // (freed on every way out, before the scene)
         rt_history *h = nullptr;
@@ -537,7 +542,7 @@ static void render_cameras(rt_scene *scene, int width, int height, int samples, 
         for (size_t t = 0; t < v.n_tris; ++t) std::memcpy(&tri_mesh[t], v.tri_attr + 16 * t + 15, 4);
         for (size_t m = 0; m < v.n_meshes; ++m) {
             const float *e = v.mesh_f + 12 * m + 3;
-            mesh_emissive.push_back(e[0] != 0.f || e[1] != 0.f || e[2] != 0.f);
+            mesh_emissive.push_back(!move_lights && (e[0] != 0.f || e[1] != 0.f || e[2] != 0.f));
         }
     }
     const size_t n_frames = cams.empty() ? moves.size() : cams.size();
@@ -639,6 +644,8 @@ int main(int argc, char *argv[]) {
     const char *moves_env = std::getenv("RT_MOVES");
     const bool cams_on = cams_env && *cams_env, temporal_on = temporal_env && *temporal_env;
     const bool moves_on = moves_env && *moves_env;
+    const char *move_lights_env = std::getenv("RT_MOVE_LIGHTS");
+    const bool move_lights = moves_on && move_lights_env && std::atoi(move_lights_env) != 0;
     if (temporal_on && !cams_on) {
         std::cerr << "rt_solution: RT_TEMPORAL needs RT_CAMERAS (a still view gains nothing from a history: use RT_PASS_SPP)" << std::endl;
         rt_scene_free(scene);
@@ -663,7 +670,11 @@ int main(int argc, char *argv[]) {
         if (ok && moves_on) {
             rt_scene_view v;
             check(rt_scene_get_view(scene, &v));
-            ok = read_moves(moves_env, v, moves, why);
+            if (move_lights && rt_scene_enable_light_updates(scene) != RT_OK) {
+                why = std::string("RT_MOVE_LIGHTS: ") + rt_last_error();
+                ok = false;
+            }
+            ok = ok && read_moves(moves_env, v, move_lights, moves, why);
             if (ok && cams_on && cams.size() != moves.size()) {
                 why = "RT_CAMERAS holds " + std::to_string(cams.size()) + " frames and RT_MOVES " + std::to_string(moves.size()) +
                       ": the line counts must be equal";
@@ -677,7 +688,7 @@ int main(int argc, char *argv[]) {
         }
         const size_t n_frames = cams_on ? cams.size() : moves.size();
         try {
-            render_cameras(scene, width, height, samples, n_gpus, fast_chunk, dn, cams, moves, output, temporal_on, alpha, aov_out);
+            render_cameras(scene, width, height, samples, n_gpus, fast_chunk, dn, cams, moves, move_lights, output, temporal_on, alpha, aov_out);
         } catch (const std::exception &e) {
             std::cerr << "rt_solution: " << e.what() << std::endl;
             rt_scene_free(scene);

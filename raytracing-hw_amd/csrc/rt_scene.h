@@ -10,6 +10,7 @@ struct rt_device_scene;  // owned by rt_device.hip: one per device the scene is 
 struct rt_device_blob;   // owned by rt_device.hip: the device image of the scene, built once
 namespace rtrp {
 struct Plan;             // rt_refit_plan.h: owned by rt_host.cpp
+struct LightPlan;        // rt_refit_plan.h: owned by rt_host.cpp
 }
 
 constexpr int kRtMaxDevices = 64;
@@ -36,6 +37,7 @@ struct rt_scene {
     rt_device_scene *dev[kRtMaxDevices] = {};   // [HIP device id]
     rt_device_blob *blob = nullptr;
     rtrp::Plan *refit_plan = nullptr;           // made by the first rt_scene_update_tris* (rt_refit_plan.h)
+    rtrp::LightPlan *light_plan = nullptr;      // made by rt_scene_enable_light_updates; non-NULL: lights may move
     std::vector<uint32_t> bfs_order;            // build-order ids in the device's numbering, kept by the blob's builder
 };
 
@@ -51,11 +53,14 @@ void rt_device_scene_set_camera(rt_scene *s);
 // movable geometry (include/rt_hw.h rt_scene_update_tris*), rt_host.cpp:
 // the scene's refit plan, made on first use
 const rtrp::Plan &rt_scene_refit_plan(rt_scene *s);
-// every refusal both entries share (NULL tri, the range, an emissive mesh's triangle); nothing is changed
+// every refusal both entries share (NULL tri, the range, an emissive mesh's triangle unless the scene
+// opted in with rt_scene_enable_light_updates); nothing is changed
 int rt_update_tris_check(rt_scene *s, const char *who, uint32_t first, uint32_t count, const float *tri);
 // implemented in rt_device.hip: after the host arrays took the new records and the refit boxes, the
-// cached device image is patched and every device copy takes the range and refits its own boxes; waits
-int rt_device_scene_update_tris(rt_scene *s, uint32_t first, uint32_t count, bool attr, bool tan);
+// cached device image is patched and every device copy takes the range and refits its own boxes; waits.
+// `lights`: the range holds a light's triangle (the host light arrays are already the new ones): the
+// image's light arrays are patched and every copy restates its light records and light boxes too
+int rt_device_scene_update_tris(rt_scene *s, uint32_t first, uint32_t count, bool attr, bool tan, bool lights);
 
 // argument checks of rt_denoise / rt_denoise_device (rt_host.cpp): RT_OK and the resolved
 // parameters (rt_denoise.h), or the failure as `who` reports it

@@ -25,6 +25,8 @@
 #   calib                FETCH_SIZE calibration of the kernel's load widths (tools/fetch_calib)
 #   refit[=REPS]         triangle update and refit against free + from_view + upload on the headline
 #                        scene (tools/refit_time.py), REPS repetitions (5)     refit_time.jsonl
+#   relight[=REPS]       light updates on practice6_1 and the headline scene, with and without the
+#                        opt-in (tools/relight_time.py), REPS repetitions (5)  relight_time.jsonl
 set -o pipefail
 cd "$(dirname "$0")/.."
 TAG=$1; shift
@@ -116,6 +118,10 @@ for step in "$@"; do
       timeout -k 10 240 python3 tools/refit_time.py --reps "${arg:-5}" --label "$TAG" --out "$OUT/refit_time.jsonl" \
         > "$OUT/refit_time.log" 2>&1 || fail refit "$OUT/refit_time.log"
       tail -2 "$OUT/refit_time.jsonl" ;;
+    relight)
+      timeout -k 10 280 python3 tools/relight_time.py --reps "${arg:-5}" --label "$TAG" --out "$OUT/relight_time.jsonl" \
+        > "$OUT/relight_time.log" 2>&1 || fail relight "$OUT/relight_time.log"
+      tail -2 "$OUT/relight_time.jsonl" ;;
     *) echo "[steps] unknown step $step"; exit 2 ;;
   esac
 done
