@@ -254,7 +254,8 @@ int rt_scene_set_camera(rt_scene *scene, const rt_camera *cam);
  * rule and rt_accum_reset above apply unchanged.  A checkpoint's header holds no geometry: loading one
  * onto moved geometry is undetected, as it is for any other scene with equal counts.
  * rt_history: nothing changes in it; for a moved object its mesh, normal and plane tests accept or
- * reject as they stand, and there are no motion vectors (a known limit).
+ * reject as they stand.  A history that opted in with rt_history_enable_motion follows moved triangles
+ * through per-pixel motion records ("per-pixel motion records" below).
  * A refit keeps the topology: after large moves the tree is still correct, but its quality (overlap
  * of sibling boxes) is whatever the moves left; there is no rebuild. */
 int rt_scene_update_tris(rt_scene *scene, uint32_t first, uint32_t count,
@@ -934,6 +935,95 @@ const float *rt_history_gbuffer_device(rt_history *h);
 int rt_history_lengths(rt_history *h, float *out);
 int rt_history_reset(rt_history *h);
 void rt_history_free(rt_history *h);
+
+/* --- per-pixel motion records: the history follows moved geometry (additive in ABI 6) ----------
+ * Opt-in.  A history that has not called rt_history_enable_motion, and a call of rt_temporal*
+ * without motion records, behave in every bit as written above.  DESIGN.md 5.24.
+ *
+ * rt_temporal's look-up projects the pixel's current position P through the previous camera; for a
+ * surface that rt_scene_update_tris* moved between two frames that is the wrong point of the
+ * previous frame.  A motion record carries the point (and the shading normal) the pixel sees now
+ * back to where that point of that triangle was, from the triangle id of the first-hit record and
+ * the triangle array as it stood before (tri_prev).  csrc/rt_motion.h is the rule's text, shared by
+ * the host function, the device kernel and the CPU tests; the arithmetic rules are rt_denoise's
+ * (f32 +, -, *, /, comparisons and selects in the order written, nothing contracted, correctly
+ * rounded division) and no float is converted to an int.
+ *
+ * A motion plane is two 16-byte quads per pixel (RT_MOTION_WORDS words), pixel-major like the
+ * G-buffer: quad 0 (P_prev.xyz, state as int bits), quad 1 (N_prev.xyz, 0).  States:
+ *   0  static   the record is the pixel's own P and N, bit for bit
+ *   1  carried
+ *   2  lost     no history may be taken for this pixel; P_prev and N_prev are zero words
+ * The rule, per pixel with record (N, t, id, P), T = tri[id], T' = tri_prev[id] (words 0..8 of a
+ * triangle are used: v0, U, V; primed letters are T' 's):
+ *   miss      id < 0 or id >= n_tris (tested, never indexed): state 0 with the record's own words
+ *             (zero words for a miss).
+ *   unmoved   words 0..8 of T and T' equal as bit patterns: state 0, P_prev = P, N_prev = N.
+ *   moved     e = P - v0 per component.  With dot(x, y) = (x.x * y.x + x.y * y.y) + x.z * y.z:
+ *               a = dot(U, U); b = dot(U, V); c = dot(V, V); det = a * c - b * b
+ *             state 2 unless det > (a * c) * 0x1p-20f and det is finite (a zero edge, parallel edges, and
+ *             a sliver whose edges meet at less than 0.06 degrees, where the rounding of det, a few
+ *             2^-24 of a * c, would decide: a NaN fails).  d = dot(U, e); f = dot(V, e);
+ *               u = (c * d - b * f) / det;  v = (a * f - b * d) / det
+ *               dv0 = v0' - v0;  dU = U' - U;  dV = V' - V      per component
+ *               P_prev = P + ((dv0 + u * dU) + v * dV)          per component
+ *             In exact arithmetic that is v0' + u U' + v V' plus P's own distance from its triangle's
+ *             plane; written as a displacement its error scales with the motion, not with the
+ *             coordinates, and a translation whose offset is exact in f32 is carried exactly.
+ *   normal    W = cross(U, V), W' = cross(U', V') (x = a.y * b.z - b.y * a.z, and cyclically).
+ *               dn = dot(U, N); fn = dot(V, N); al = (c * dn - b * fn) / det; be = (a * fn - b * dn) / det
+ *               ga = dot(W, N) / dot(W, W);  dW = W' - W
+ *               N_prev = N + ((al * dU + be * dV) + ga * dW)    per component
+ *             For a rigid motion that is the rotated normal up to rounding; for a deforming triangle
+ *             it is an approximation.  It is not renormalised.
+ *   lost      any non-finite word of P_prev or N_prev: state 2.  Non-finite and degenerate triangles
+ *             and a non-finite P end here or at det.  Otherwise state 1.
+ * The look-up with motion is step 2 of rt_temporal with: state 0 (and motion NULL) the pixel's own
+ * values, exactly as written there; state 1: P_prev in Pp's place for the projection through
+ * cam_prev, and ((N_prev, tp), P_prev, sigma_plane * tp) as the centre of the normal and plane
+ * tests (tp the pixel's own hit distance); any other state: no history.  Steps 0, 1, 3, 4 as above.
+ *
+ * rt_motion runs on the host.  rt_motion_device runs on the current HIP device, asynchronously on
+ * `stream`, with the host function's bits: one kernel, every pointer a 16-byte aligned device
+ * pointer.  With n_tris == 0 tri and tri_prev may be NULL.  rt_temporal_motion(_device) are
+ * rt_temporal(_device) with the motion plane as a further argument; NULL is rt_temporal(_device)
+ * exactly.  Refusals, all before any launch: those of rt_temporal; a NULL argument, a bad frame size
+ * (RT_ERR_ARG), width * height above 2^31 - 1 (RT_ERR_LIMIT), a misaligned device pointer, and motion
+ * given while history_prev is NULL (RT_ERR_ARG).
+ *
+ * rt_history_enable_motion allocates a copy of the scene's triangles (n_tris x 12 floats) and one
+ * motion plane on the history's device.  It is allowed before the first push or directly after
+ * rt_history_reset, RT_ERR_ARG otherwise; a failed allocation leaves the history as it was; a second
+ * call is RT_OK.  The scene counts its rt_scene_update_tris* calls (a counter of its own, not the
+ * epoch the camera also bumps).  A push of such a history, all on the caller's stream: the G-buffer;
+ * if there is a previous push and the counter differs from the one the snapshot was taken at, the
+ * motion kernel against the snapshot and the step with its records, otherwise exactly the one launch
+ * of a history without motion (an unmoved scene pays nothing); then, if the counter differs or there
+ * is no snapshot yet, a device-to-device copy of the scene's triangles into the snapshot.  Several
+ * updates between two pushes are one motion.  The snapshot copy reads the scene's device copy on the
+ * caller's stream: as for every entry, no update may run while it is in flight.
+ * rt_history_motion_device: the last push's motion plane on the device, NULL when that push ran
+ * without one (the first, an unmoved one, a history that has not opted in).  rt_history_motion: that
+ * plane to host memory (W * H * RT_MOTION_WORDS floats); waits; RT_ERR_ARG when there is none.
+ * Limits: a triangle is followed by its id, so a changed topology is not followed (there is no
+ * rebuild); textures and materials are taken as unmoved. */
+#define RT_MOTION_WORDS 8
+int rt_motion(const float *gbuffer, int32_t width, int32_t height, const float *tri, const float *tri_prev,
+              uint32_t n_tris, float *out_motion);
+int rt_motion_device(const float *d_gbuffer, int32_t width, int32_t height, const float *d_tri,
+                     const float *d_tri_prev, uint32_t n_tris, float *d_out_motion, void *stream);
+int rt_temporal_motion(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
+                       const float *gbuffer, const rt_camera *cam_prev, const float *gbuffer_prev,
+                       const float *history_prev, const rt_temporal_params *params,
+                       float *history_out, float *out_mean, float *out_variance, const float *motion);
+int rt_temporal_motion_device(const float *d_sums, const int32_t *d_counts, int32_t spp, int32_t width, int32_t height,
+                              const float *d_gbuffer, const rt_camera *cam_prev, const float *d_gbuffer_prev,
+                              const float *d_history_prev, const rt_temporal_params *params,
+                              float *d_history_out, float *d_out_mean, float *d_out_variance,
+                              const float *d_motion, void *stream);
+int rt_history_enable_motion(rt_history *h);
+const float *rt_history_motion_device(rt_history *h);
+int rt_history_motion(rt_history *h, float *out);
 
 /* --- misc --------------------------------------------------------------------------- */
 const char *rt_last_error(void);

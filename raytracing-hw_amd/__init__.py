@@ -112,6 +112,7 @@ def _camera_arg(cam):
     return make_camera(cam["pos"], cam["axes"], cam["tan_half_fov"])
 
 
+MOTION_WORDS = 8         # RT_MOTION_WORDS: 32-bit words of a pixel's motion record (two quads)
 HISTORY_WORDS = 12       # RT_HISTORY_WORDS: 32-bit words of a pixel's temporal history (three planes of quads)
 
 
@@ -247,6 +248,19 @@ ABI = {
     "rt_history_lengths": (ctypes.c_int, [ctypes.c_void_p, _c_f]),
     "rt_history_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "rt_history_free": (None, [ctypes.c_void_p]),
+    # per-pixel motion records: the history follows moved geometry
+    "rt_motion": (ctypes.c_int, [_c_f, ctypes.c_int32, ctypes.c_int32, _c_f, _c_f, ctypes.c_uint32, _c_f]),
+    "rt_motion_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    "rt_temporal_motion": (ctypes.c_int, [_c_f, _c_i, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_f, ctypes.POINTER(RtCamera),
+                                          _c_f, _c_f, ctypes.POINTER(RtTemporalParams), _c_f, _c_f, _c_f, _c_f]),
+    "rt_temporal_motion_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                 ctypes.c_void_p, ctypes.POINTER(RtCamera), ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.POINTER(RtTemporalParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p]),
+    "rt_history_enable_motion": (ctypes.c_int, [ctypes.c_void_p]),
+    "rt_history_motion_device": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "rt_history_motion": (ctypes.c_int, [ctypes.c_void_p, _c_f]),
     # movable geometry: triangle updates and the BVH refit
     "rt_scene_update_tris": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, _c_f, _c_f, _c_f]),
     "rt_scene_update_tris_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32,
@@ -549,13 +563,17 @@ class Scene:
                                                                   for k in ("tri", "tri_attr", "tri_tan", "node")]))
         return out
 
-    def history(self, device=0):
+    def history(self, device=0, motion=False):
         """rt_history_create: a reprojected temporal history of this scene's frame on `device`
-        (uploaded here if need be)."""
+        (uploaded here if need be).  motion=True: rt_history_enable_motion, the history follows
+        triangles that update_triangles moved between two pushes."""
         self.upload(device)
         h = ctypes.c_void_p()
         _check(lib().rt_history_create(self._h, device, ctypes.byref(h)))
-        return History(self, h.value)
+        hist = History(self, h.value)
+        if motion:
+            hist.enable_motion()
+        return hist
 
     def upload(self, device=0):
         _check(lib().rt_scene_upload(self._h, device))
@@ -956,6 +974,25 @@ class History:
         """The device records of the last push's view (0 before one), for denoise*_device."""
         return int(lib().rt_history_gbuffer_device(self._h) or 0)
 
+    def enable_motion(self):
+        """rt_history_enable_motion: before the first push or directly after reset()."""
+        _check(lib().rt_history_enable_motion(self._h))
+
+    def motion_ptr(self):
+        """The device motion plane of the last push (0 when it ran without one)."""
+        return int(lib().rt_history_motion_device(self._h) or 0)
+
+    def motion(self):
+        """The last push's motion records on the host, as motion() returns them, or None when that
+        push ran without them (waits for the device)."""
+        ptr = self.motion_ptr()
+        if not ptr:
+            return None
+        h, w = self._scene.height, self._scene.width
+        out = np.zeros((h, w, MOTION_WORDS), np.float32)
+        _check(lib().rt_history_motion(self._h, out.ctypes.data_as(_c_f)))
+        return motion_unpack(out)
+
     def reset(self):
         _check(lib().rt_history_reset(self._h))
 
@@ -1126,10 +1163,44 @@ def denoise_device(d_sums_ptr, d_counts_ptr, spp, width, height, d_gbuffer_ptr, 
                                    ctypes.c_void_p(stream_ptr or 0)))
 
 
-def temporal(sums, counts_or_spp, gbuffer, cam_prev=None, gbuffer_prev=None, history_prev=None, **params):
+def motion_unpack(records):
+    """(H, W, 8) motion records as a dict: prev_position, prev_normal (H, W, 3) and state (H, W) int32."""
+    rec = np.ascontiguousarray(records, np.float32)
+    return {"prev_position": rec[..., 0:3].copy(), "prev_normal": rec[..., 4:7].copy(),
+            "state": rec.view(np.int32)[..., 3].copy(), "records": rec}
+
+
+def _motion_arg(motion, h, w):
+    if motion is None:
+        return None
+    rec = np.ascontiguousarray(motion["records"] if isinstance(motion, dict) else motion, np.float32)
+    if rec.size != h * w * MOTION_WORDS:
+        raise ValueError("motion must have two quads per pixel")
+    return rec
+
+
+def motion(gbuffer, tri, tri_prev):
+    """rt_motion (the host function): every pixel's motion record from its first-hit record, the
+    triangles as they stand (n x 12) and as they stood.  Returns a dict: prev_position, prev_normal,
+    state (0 static, 1 carried, 2 lost) and the packed (H, W, 8) `records` temporal(motion=) takes."""
+    rec = gbuffer_pack(gbuffer)
+    if rec.ndim != 3:
+        raise ValueError("gbuffer must be (H, W, 16) records")
+    h, w = rec.shape[0], rec.shape[1]
+    tri, tri_prev = np.ascontiguousarray(tri, np.float32), np.ascontiguousarray(tri_prev, np.float32)
+    if tri.size % 12 or tri.size != tri_prev.size:
+        raise ValueError("tri and tri_prev must hold the same number of 12-word records")
+    out = np.zeros((h, w, MOTION_WORDS), np.float32)
+    _check(lib().rt_motion(rec.ctypes.data_as(_c_f), w, h, tri.ctypes.data_as(_c_f), tri_prev.ctypes.data_as(_c_f), tri.size // 12,
+                           out.ctypes.data_as(_c_f)))
+    return motion_unpack(out)
+
+
+def temporal(sums, counts_or_spp, gbuffer, cam_prev=None, gbuffer_prev=None, history_prev=None, motion=None, **params):
     """rt_temporal (the host function): one step of the reprojected temporal history.  cam_prev (a
     Scene.camera() dict or RtCamera), gbuffer_prev and history_prev ((3, H, W, 4) float32) describe
-    the previous frame; all None: a first frame.  Returns (history (3, H, W, 4), mean (H, W, 3),
+    the previous frame; all None: a first frame.  motion: motion()'s result or its packed records
+    (rt_temporal_motion); None: rt_temporal.  Returns (history (3, H, W, 4), mean (H, W, 3),
     variance (H, W)).  params: temporal_params' arguments."""
     sums, counts, spp, rec = _denoise_inputs(sums, counts_or_spp, gbuffer)
     h, w = sums.shape[0], sums.shape[1]
@@ -1145,6 +1216,15 @@ def temporal(sums, counts_or_spp, gbuffer, cam_prev=None, gbuffer_prev=None, his
             raise ValueError("history_prev must have three planes of one quad per pixel")
     hist, mean, var = np.zeros((3, h, w, 4), np.float32), np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
     tp = temporal_params(**params)
+    mo = _motion_arg(motion, h, w)
+    if mo is not None:
+        _check(lib().rt_temporal_motion(sums.ctypes.data_as(_c_f), counts.ctypes.data_as(_c_i) if counts is not None else None, spp, w, h,
+                                        rec.ctypes.data_as(_c_f), ctypes.byref(cam) if cam is not None else None,
+                                        gp.ctypes.data_as(_c_f) if gp is not None else None,
+                                        hp.ctypes.data_as(_c_f) if hp is not None else None, ctypes.byref(tp),
+                                        hist.ctypes.data_as(_c_f), mean.ctypes.data_as(_c_f), var.ctypes.data_as(_c_f),
+                                        mo.ctypes.data_as(_c_f)))
+        return hist, mean, var
     _check(lib().rt_temporal(sums.ctypes.data_as(_c_f), counts.ctypes.data_as(_c_i) if counts is not None else None, spp, w, h,
                              rec.ctypes.data_as(_c_f), ctypes.byref(cam) if cam is not None else None,
                              gp.ctypes.data_as(_c_f) if gp is not None else None, hp.ctypes.data_as(_c_f) if hp is not None else None,
@@ -1152,13 +1232,27 @@ def temporal(sums, counts_or_spp, gbuffer, cam_prev=None, gbuffer_prev=None, his
     return hist, mean, var
 
 
+def motion_device(d_gbuffer_ptr, width, height, d_tri_ptr, d_tri_prev_ptr, n_tris, d_out_ptr, stream_ptr=None):
+    """rt_motion_device: the motion records on the current HIP device (16-byte aligned device
+    pointers), asynchronous on the stream."""
+    V = ctypes.c_void_p
+    _check(lib().rt_motion_device(V(d_gbuffer_ptr), width, height, V(d_tri_ptr or 0), V(d_tri_prev_ptr or 0), int(n_tris), V(d_out_ptr),
+                                  V(stream_ptr or 0)))
+
+
 def temporal_device(d_sums_ptr, d_counts_ptr, spp, width, height, d_gbuffer_ptr, d_history_out_ptr, d_out_ptr=0, d_var_ptr=0,
-                    cam_prev=None, d_gbuffer_prev_ptr=0, d_history_prev_ptr=0, stream_ptr=None, **params):
+                    cam_prev=None, d_gbuffer_prev_ptr=0, d_history_prev_ptr=0, stream_ptr=None, d_motion_ptr=None, **params):
     """rt_temporal_device: the same step on the current HIP device (device pointers; 0 / None: not
-    given), asynchronous on the stream."""
+    given), asynchronous on the stream.  d_motion_ptr given: rt_temporal_motion_device."""
     cam = _camera_arg(cam_prev)
     tp = temporal_params(**params)
     V = ctypes.c_void_p
+    if d_motion_ptr:
+        _check(lib().rt_temporal_motion_device(V(d_sums_ptr), V(d_counts_ptr or 0), int(spp), width, height, V(d_gbuffer_ptr),
+                                               ctypes.byref(cam) if cam is not None else None, V(d_gbuffer_prev_ptr or 0),
+                                               V(d_history_prev_ptr or 0), ctypes.byref(tp), V(d_history_out_ptr), V(d_out_ptr or 0),
+                                               V(d_var_ptr or 0), V(d_motion_ptr), V(stream_ptr or 0)))
+        return
     _check(lib().rt_temporal_device(V(d_sums_ptr), V(d_counts_ptr or 0), int(spp), width, height, V(d_gbuffer_ptr),
                                     ctypes.byref(cam) if cam is not None else None, V(d_gbuffer_prev_ptr or 0),
                                     V(d_history_prev_ptr or 0), ctypes.byref(tp), V(d_history_out_ptr), V(d_out_ptr or 0),

@@ -70,6 +70,7 @@
 #include "rt_denoise.h"
 #include "rt_denoise_guided.h"
 #include "rt_temporal.h"
+#include "rt_motion.h"
 #include "rt_refit.h"
 #include "rt_refit_plan.h"
 #include "rt_relight.h"
@@ -1294,6 +1295,7 @@ int rt_render(rt_scene *s, const rt_params *p, float *out, rt_stats *st) {
 // ------------------------------------------------------------------------ feature buffer, denoiser, accumulator
 #include "rt_denoise_device.h"   // the feature buffer and the denoiser: kernels, launch functions, entries
 #include "rt_accum_device.h"     // rt_accum_*: the accumulator's kernels, helpers and entries
+#include "rt_motion_device.h"    // rt_motion_device: the motion records' kernel
 #include "rt_temporal_device.h"  // rt_temporal_device, rt_history_*: the temporal step's kernel and the history object
 #include "rt_refit_device.h"     // rt_scene_update_tris*, rt_scene_read_device: the scatter and refit kernels and their entries
 

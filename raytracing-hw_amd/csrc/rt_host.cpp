@@ -27,6 +27,7 @@
 #include "rt_scene.h"
 #include "rt_select.h"
 #include "rt_temporal.h"
+#include "rt_motion.h"
 #include "rt_vec.h"
 
 using rtv::V2;
@@ -926,6 +927,7 @@ int rt_scene_update_tris(rt_scene *s, uint32_t first, uint32_t count, const floa
         rtrl::refit_sweep(s->light.data(), s->light_node.data(), s->light_node.size() / 8);
     }
     ++s->view_epoch;
+    ++s->geom_epoch;
     return rt_device_scene_update_tris(s, first, count, tri_attr != nullptr, tri_tan != nullptr, lights);
 }
 
@@ -1100,17 +1102,23 @@ int rt_denoise_guided(const float *sums, const int32_t *counts, int32_t spp, int
 
 // The temporal step on the host (rt_temporal.h is its text; include/rt_hw.h its rule): per pixel,
 // against the previous frame's records and history.
-int rt_temporal(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height, const float *gbuffer,
-                const rt_camera *cam_prev, const float *gbuffer_prev, const float *history_prev, const rt_temporal_params *params,
-                float *history_out, float *out_mean, float *out_variance) {
+static int temporal_host(const char *who, const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
+                         const float *gbuffer, const rt_camera *cam_prev, const float *gbuffer_prev, const float *history_prev,
+                         const rt_temporal_params *params, float *history_out, float *out_mean, float *out_variance,
+                         const float *motion) {
     rttm::Params tp;
-    if (int rc = rt_temporal_check("rt_temporal", sums, counts, spp, width, height, gbuffer, cam_prev, gbuffer_prev, history_prev,
-                                   params, history_out, &tp))
+    if (int rc = rt_temporal_check(who, sums, counts, spp, width, height, gbuffer, cam_prev, gbuffer_prev, history_prev, params,
+                                   history_out, &tp))
         return rc;
+    if (motion && !history_prev) return rt_fail(RT_ERR_ARG, std::string(who) + ": motion records need a previous history");
     const int64_t n = (int64_t)width * height;
     // (the caller's arrays need not be 16-byte aligned)
-    std::vector<rtdn::Q> g((size_t)n * 4), gp, hp, ho((size_t)n * rttm::kHistoryQuads);
+    std::vector<rtdn::Q> g((size_t)n * 4), gp, hp, ho((size_t)n * rttm::kHistoryQuads), mo;
     std::memcpy(g.data(), gbuffer, (size_t)n * 64);
+    if (motion) {
+        mo.resize((size_t)n * rtmo::kMotionQuads);
+        std::memcpy(mo.data(), motion, (size_t)n * rtmo::kMotionQuads * 16);
+    }
     rttm::Camera cam{};
     if (history_prev) {
         gp.resize((size_t)n * 4);
@@ -1122,13 +1130,50 @@ int rt_temporal(const float *sums, const int32_t *counts, int32_t spp, int32_t w
     const rttm::PlainSrc prev{hp.data(), gp.data(), width, n};
     for (int64_t p = 0; p < n; ++p) {
         const rttm::Pixel r = rttm::temporal_pixel(prev, history_prev != nullptr, cam, sums + 3 * p, counts ? counts[p] : spp,
-                                                   &g[4 * p], width, height, tp);
+                                                   &g[4 * p], width, height, tp, motion ? &mo[rtmo::kMotionQuads * p] : nullptr);
         for (int k = 0; k < rttm::kHistoryQuads; ++k) ho[(size_t)(k * n + p)] = r.h[k];
         if (out_mean)
             for (int c = 0; c < 3; ++c) out_mean[3 * p + c] = r.mean[c];
         if (out_variance) out_variance[p] = r.variance;
     }
     std::memcpy(history_out, ho.data(), (size_t)n * rttm::kHistoryQuads * 16);
+    return RT_OK;
+}
+
+int rt_temporal(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height, const float *gbuffer,
+                const rt_camera *cam_prev, const float *gbuffer_prev, const float *history_prev, const rt_temporal_params *params,
+                float *history_out, float *out_mean, float *out_variance) {
+    return temporal_host("rt_temporal", sums, counts, spp, width, height, gbuffer, cam_prev, gbuffer_prev, history_prev, params,
+                         history_out, out_mean, out_variance, nullptr);
+}
+
+// The same with the pixels' motion records (rt_motion.h); motion NULL: rt_temporal.
+int rt_temporal_motion(const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height, const float *gbuffer,
+                       const rt_camera *cam_prev, const float *gbuffer_prev, const float *history_prev,
+                       const rt_temporal_params *params, float *history_out, float *out_mean, float *out_variance,
+                       const float *motion) {
+    return temporal_host("rt_temporal_motion", sums, counts, spp, width, height, gbuffer, cam_prev, gbuffer_prev, history_prev, params,
+                         history_out, out_mean, out_variance, motion);
+}
+
+// The motion records on the host (rt_motion.h is their text; include/rt_hw.h their rule).
+int rt_motion(const float *gbuffer, int32_t width, int32_t height, const float *tri, const float *tri_prev, uint32_t n_tris,
+              float *out_motion) {
+    if (int rc = rt_motion_check("rt_motion", gbuffer, width, height, tri, tri_prev, n_tris, out_motion)) return rc;
+    const int64_t n = (int64_t)width * height;
+    // (the caller's arrays need not be 16-byte aligned)
+    std::vector<rtdn::Q> g((size_t)n * 4), t((size_t)n_tris * 3), tp((size_t)n_tris * 3), mo((size_t)n * rtmo::kMotionQuads);
+    std::memcpy(g.data(), gbuffer, (size_t)n * 64);
+    if (n_tris) {
+        std::memcpy(t.data(), tri, (size_t)n_tris * 48);
+        std::memcpy(tp.data(), tri_prev, (size_t)n_tris * 48);
+    }
+    for (int64_t p = 0; p < n; ++p) {
+        const rtmo::Motion m = rtmo::carry_pixel(g[4 * p], g[4 * p + 1], g[4 * p + 3], t.data(), tp.data(), n_tris);
+        mo[(size_t)(2 * p)] = m.p;
+        mo[(size_t)(2 * p + 1)] = m.n;
+    }
+    std::memcpy(out_motion, mo.data(), (size_t)n * rtmo::kMotionQuads * 16);
     return RT_OK;
 }
 
@@ -1207,6 +1252,12 @@ int rt_temporal_check(const char *who, const float *sums, const int32_t *counts,
         return rt_fail(RT_ERR_ARG, w + ": alpha or alpha_moments above 1, max_history above " + std::to_string(rttm::kMaxMaxHistory) +
                                        " or a non-finite parameter");
     return RT_OK;
+}
+
+int rt_motion_check(const char *who, const float *gbuffer, int32_t width, int32_t height, const float *tri, const float *tri_prev,
+                    uint32_t n_tris, const float *out_motion) {
+    // (spp 1 stands in for the sample count the other checks test: a motion record has none)
+    return frame_check(who, !gbuffer || !out_motion || (n_tris && (!tri || !tri_prev)), nullptr, 1, width, height);
 }
 
 int rt_variance_check(const char *who, const float *sums, const float *moments, const int32_t *counts, int32_t spp, int32_t width,

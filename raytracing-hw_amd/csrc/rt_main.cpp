@@ -75,6 +75,10 @@
 //                       files must hold as many frames.  A malformed line, an unknown mesh and an
 //                       emissive mesh (lights do not move) are errors that name the line, reported
 //                       before anything is rendered.
+//   RT_MOTION=1         (needs RT_MOVES and RT_TEMPORAL; RT_CAMERAS is then optional) the history opts in to
+//                       per-pixel motion records (rt_history_enable_motion): a moved object keeps its
+//                       history instead of restarting or smearing it.  Without it every message and
+//                       refusal is as above.
 //   RT_MOVE_LIGHTS=1    (with RT_MOVES) the scene opts in to movable lights (rt_scene_enable_light_updates):
 //                       a line may name an emissive mesh, whose light records and light BVH boxes then
 //                       follow its triangles, and the covering ranges are not cut at emissive triangles.
@@ -516,7 +520,7 @@ static std::string indexed_name(const std::string &path, size_t k) {
 // device 0 before the finish.
 static void render_cameras(rt_scene *scene, int width, int height, int samples, int n_gpus, int fast_chunk, Denoise &dn,
                            const std::vector<rt_camera> &cams, const std::vector<std::vector<Move>> &moves, bool move_lights,
-                           const std::string &output, bool temporal, float alpha, const char *aov_out) {
+                           const std::string &output, bool temporal, float alpha, const char *aov_out, bool motion) {
     struct Held {   // (freed on every way out, before the scene)
         rt_history *h = nullptr;
         ~Held() { rt_history_free(h); }
@@ -555,7 +559,10 @@ static void render_cameras(rt_scene *scene, int width, int height, int samples, 
             check(rt_render_frame(scene, &p, n_gpus, nullptr, nullptr, sums.data(), &st));
         }
         if (temporal) {
-            if (!held.h) check(rt_history_create(scene, 0, &held.h));   // (the frame has uploaded the scene to device 0)
+            if (!held.h) {
+                check(rt_history_create(scene, 0, &held.h));   // (the frame has uploaded the scene to device 0)
+                if (motion) check(rt_history_enable_motion(held.h));
+            }
             check(rt_history_push_frame_u8(held.h, sums.data(), nullptr, samples, &tp, dn.on && !dn.guided ? &dn.params : nullptr,
                                            dn.guided ? &dn.guided_params : nullptr, rgb.data()));
         } else if (dn.on) {
@@ -646,7 +653,15 @@ int main(int argc, char *argv[]) {
     const bool moves_on = moves_env && *moves_env;
     const char *move_lights_env = std::getenv("RT_MOVE_LIGHTS");
     const bool move_lights = moves_on && move_lights_env && std::atoi(move_lights_env) != 0;
-    if (temporal_on && !cams_on) {
+    const char *motion_env = std::getenv("RT_MOTION");
+    const bool motion_on = motion_env && *motion_env && std::atoi(motion_env) != 0;
+    if (motion_on && (!temporal_on || !moves_on)) {
+        std::cerr << "rt_solution: RT_MOTION needs " << (!temporal_on ? "RT_TEMPORAL" : "RT_MOVES")
+                  << " (motion records carry a temporal history along moved objects)" << std::endl;
+        rt_scene_free(scene);
+        return 1;
+    }
+    if (temporal_on && !cams_on && !motion_on) {
         std::cerr << "rt_solution: RT_TEMPORAL needs RT_CAMERAS (a still view gains nothing from a history: use RT_PASS_SPP)" << std::endl;
         rt_scene_free(scene);
         return 1;
@@ -688,7 +703,8 @@ int main(int argc, char *argv[]) {
         }
         const size_t n_frames = cams_on ? cams.size() : moves.size();
         try {
-            render_cameras(scene, width, height, samples, n_gpus, fast_chunk, dn, cams, moves, move_lights, output, temporal_on, alpha, aov_out);
+            render_cameras(scene, width, height, samples, n_gpus, fast_chunk, dn, cams, moves, move_lights, output, temporal_on, alpha, aov_out,
+                           motion_on);
         } catch (const std::exception &e) {
             std::cerr << "rt_solution: " << e.what() << std::endl;
             rt_scene_free(scene);

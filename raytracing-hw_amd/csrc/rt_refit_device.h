@@ -256,6 +256,7 @@ int rt_scene_update_tris_device(rt_scene *s, int32_t device, uint32_t first, uin
     const size_t nn = s->node.size() / 8;
     std::vector<float> bfs(8 * nn);
     ++s->view_epoch;
+    ++s->geom_epoch;
     const bool lights = s->light_plan && s->light_plan->touches(first, count);
     if (int rc = refit_enqueue(s, d, first, count, d_tri, d_tri_attr, d_tri_tan, lights, q)) return rc;
     // the host mirror and the cached image follow the device: the changed range and every box

@@ -23,6 +23,7 @@ struct rt_scene {
     float cam_fov[2] = {0, 0};
     float tan_half_fov[2] = {0, 0};
     uint32_t view_epoch = 0;   // rt_scene_set_camera and rt_scene_update_tris* calls so far (an accumulator remembers the one it renders)
+    uint32_t geom_epoch = 0;   // rt_scene_update_tris* calls alone (a history that carries motion remembers the one it saw)
 
     std::vector<float> tri, tri_attr, tri_tan, node;
     uint32_t bvh_depth = 0;
@@ -87,6 +88,11 @@ struct Params;
 int rt_temporal_check(const char *who, const float *sums, const int32_t *counts, int32_t spp, int32_t width, int32_t height,
                       const float *gbuffer, const rt_camera *cam_prev, const float *gbuffer_prev, const float *history_prev,
                       const rt_temporal_params *params, const float *history_out, rttm::Params *resolved);
+
+// the same for rt_motion and its device form (rt_motion.h), which have no parameters; with n_tris == 0
+// the two triangle arrays may be NULL (every record is then a miss's)
+int rt_motion_check(const char *who, const float *gbuffer, int32_t width, int32_t height, const float *tri, const float *tri_prev,
+                    uint32_t n_tris, const float *out_motion);
 
 // row partition helper (rt_host.cpp)
 int64_t rt_shard_rows_impl(int32_t height, int32_t rank, int32_t world, int32_t row_block, int32_t *rows_out);

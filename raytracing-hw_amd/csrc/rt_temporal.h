@@ -81,7 +81,8 @@ RT_HD int floor_of(float f, float &frac) {
 RT_HD float max_of(float a, float b) { return a > b ? a : b; }
 
 // The look-up: the previous frame's history at the point the pixel sees, over the bilinear taps
-// that show the same surface.  nt, pp: the pixel's (N, t) and (P, 0); mesh: its mesh id.
+// that show the same surface.  nt, pp: the centre, (N, t) and (P, 0): the pixel's own, or its motion
+// record's carried normal and position with the pixel's t (temporal_pixel); mesh: its mesh id.
 // hq: (Lh, Nh), (M1h, 0), (M2h, 0).  False: no history.
 template <class Src>
 RT_HD bool lookup(const Src &prev, const Camera &cam, const Q &nt, const Q &pp, int32_t mesh, int W, int H, const Params &tp,
@@ -131,9 +132,13 @@ RT_HD bool lookup(const Src &prev, const Camera &cam, const Q &nt, const Q &pp, 
 
 // The whole step at pixel (x, y) of a W x H frame.  S: its three sums; n: its sample count; g: its
 // first-hit record (4 x Q); has_prev: a previous frame exists (prev and cam are read only then).
+// mo: the pixel's motion record (rt_motion.h: (P_prev, state), (N_prev, 0)) or null.  Null and
+// state 0: the look-up from the pixel's own (N, t) and P; state 1: from ((N_prev, t), P_prev), which
+// are then the projected point and the centre of the normal and plane tests; any other state: no
+// history.
 template <class Src>
 RT_HD Pixel temporal_pixel(const Src &prev, bool has_prev, const Camera &cam, const float *S, int n, const Q *g, int W, int H,
-                           const Params &tp) {
+                           const Params &tp, const Q *mo = nullptr) {
     Pixel r;
     r.h[0] = r.h[1] = r.h[2] = Q{0.f, 0.f, 0.f, 0.f};
     r.variance = 0.f;
@@ -145,7 +150,17 @@ RT_HD Pixel temporal_pixel(const Src &prev, bool has_prev, const Camera &cam, co
         return r;
     }
     Q hq[kHistoryQuads];
-    const bool have = has_prev && lookup(prev, cam, nt, pp, (int32_t)rtm::f2u(g[2].w), W, H, tp, hq);
+    // (one call for both centres: the pixels of a wave that carry and those that do not look up together)
+    Q cn = nt, cp = pp;
+    bool look = has_prev;
+    if (mo) {
+        const uint32_t state = rtm::f2u(mo[0].w);
+        if (state == 1u)
+            cn = Q{mo[1].x, mo[1].y, mo[1].z, nt.w}, cp = Q{mo[0].x, mo[0].y, mo[0].z, 0.f};
+        else if (state != 0u)
+            look = false;
+    }
+    const bool have = look && lookup(prev, cam, cn, cp, (int32_t)rtm::f2u(g[2].w), W, H, tp, hq);
     const float L[3] = {a.x, a.y, a.z};
     float N1 = 0.f, L1[3] = {0.f, 0.f, 0.f}, M1[3] = {0.f, 0.f, 0.f}, M2[3] = {0.f, 0.f, 0.f};
     bool done = false;

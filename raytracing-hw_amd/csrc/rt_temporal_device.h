@@ -9,18 +9,30 @@
 // §5.18).  Every history and record access is a whole 16-byte quad (of a previous
 // record only quads 0, 2 and 3 are read); the three history planes, the mean and the variance are
 // plain vector stores.  No LDS, no atomics.  prev_h == nullptr: a first frame.
+// kMotion: the pixel's two motion quads (rt_motion.h) are read as well and give the look-up its
+// centre; without it `motion` is not read and the code is the one this kernel had before it took
+// the argument (DESIGN.md §5.24 has the comparison of the two listings).
+template <bool kMotion>
 __global__ void __launch_bounds__(256) rt_temporal_kernel(const float *__restrict__ sums, const int32_t *__restrict__ counts, int spp,
                                                            const rtdn::Q *__restrict__ g, const rtdn::Q *__restrict__ prev_h,
                                                            const rtdn::Q *__restrict__ prev_g, rttm::Camera cam, rttm::Params tp,
                                                            int W, int H, int tiles_x, rtdn::Q *__restrict__ hist_out,
-                                                           float *__restrict__ out_mean, float *__restrict__ out_var) {
+                                                           float *__restrict__ out_mean, float *__restrict__ out_var,
+                                                           const rtdn::Q *__restrict__ motion) {
     const DnLane l = dn_lane(tiles_x);
     if (l.x >= W || l.y >= H) return;
     const long long n = (long long)W * H, p = (long long)l.y * W + l.x;
     const rtdn::Q rec[4] = {g[4 * p], g[4 * p + 1], g[4 * p + 2], g[4 * p + 3]};
     const float S[3] = {sums[3 * p], sums[3 * p + 1], sums[3 * p + 2]};
-    const rttm::Pixel r = rttm::temporal_pixel(rttm::PlainSrc{prev_h, prev_g, W, n}, prev_h != nullptr, cam, S,
-                                               counts ? counts[p] : spp, rec, W, H, tp);
+    rttm::Pixel r;
+    if constexpr (kMotion) {
+        const rtdn::Q mo[2] = {motion[2 * p], motion[2 * p + 1]};
+        r = rttm::temporal_pixel(rttm::PlainSrc{prev_h, prev_g, W, n}, prev_h != nullptr, cam, S, counts ? counts[p] : spp, rec, W, H,
+                                 tp, mo);
+    } else {
+        r = rttm::temporal_pixel(rttm::PlainSrc{prev_h, prev_g, W, n}, prev_h != nullptr, cam, S, counts ? counts[p] : spp, rec, W, H,
+                                 tp);
+    }
 #pragma unroll
     for (int k = 0; k < rttm::kHistoryQuads; ++k) hist_out[k * n + p] = r.h[k];
     if (out_mean) {
@@ -33,17 +45,23 @@ __global__ void __launch_bounds__(256) rt_temporal_kernel(const float *__restric
 
 namespace {
 
-// The step on the current device (d_hist_prev == nullptr: a first frame).
+// The step on the current device (d_hist_prev == nullptr: a first frame; d_motion == nullptr: the
+// kernel without motion records).
 int temporal_launch(const float *d_sums, const int32_t *d_counts, int spp, int W, int H, const float *d_g, const rt_camera *cam_prev,
                     const float *d_g_prev, const float *d_hist_prev, const rttm::Params &tp, float *d_hist_out, float *d_out_mean,
-                    float *d_out_var, hipStream_t stream) {
+                    float *d_out_var, hipStream_t stream, const float *d_motion = nullptr) {
     rttm::Camera cam{};
     if (d_hist_prev) std::memcpy(&cam, cam_prev, sizeof cam);
     const int tiles_x = (W + kDnTileW - 1) / kDnTileW;
     const dim3 tiles((unsigned)((long long)tiles_x * ((H + kDnTileH - 1) / kDnTileH)));
-    hipLaunchKernelGGL(rt_temporal_kernel, tiles, dim3(256), 0, stream, d_sums, d_counts, spp, (const rtdn::Q *)d_g,
-                       (const rtdn::Q *)d_hist_prev, (const rtdn::Q *)(d_hist_prev ? d_g_prev : nullptr), cam, tp, W, H, tiles_x,
-                       (rtdn::Q *)d_hist_out, d_out_mean, d_out_var);
+    if (d_motion)
+        hipLaunchKernelGGL(rt_temporal_kernel<true>, tiles, dim3(256), 0, stream, d_sums, d_counts, spp, (const rtdn::Q *)d_g,
+                           (const rtdn::Q *)d_hist_prev, (const rtdn::Q *)(d_hist_prev ? d_g_prev : nullptr), cam, tp, W, H, tiles_x,
+                           (rtdn::Q *)d_hist_out, d_out_mean, d_out_var, (const rtdn::Q *)d_motion);
+    else
+        hipLaunchKernelGGL(rt_temporal_kernel<false>, tiles, dim3(256), 0, stream, d_sums, d_counts, spp, (const rtdn::Q *)d_g,
+                           (const rtdn::Q *)d_hist_prev, (const rtdn::Q *)(d_hist_prev ? d_g_prev : nullptr), cam, tp, W, H, tiles_x,
+                           (rtdn::Q *)d_hist_out, d_out_mean, d_out_var, (const rtdn::Q *)nullptr);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
@@ -63,6 +81,11 @@ struct rt_history {
     bool has_prev = false;
     rt_camera cam_prev{};
     hipStream_t stream = nullptr;   // the last push's (host reads wait for it)
+    // motion records (rt_history_enable_motion): the scene's triangles as they stood at the last push,
+    // the geometry counter they were copied at, and the last push's records
+    bool motion_on = false, has_snapshot = false, motion_valid = false;
+    uint32_t geom_seen = 0;
+    float *tri_prev = nullptr, *motion = nullptr;
 };
 
 extern "C" {
@@ -79,10 +102,24 @@ int rt_temporal_device(const float *d_sums, const int32_t *d_counts, int32_t spp
                            d_history_out, d_out_mean, d_out_variance, (hipStream_t)stream);
 }
 
+int rt_temporal_motion_device(const float *d_sums, const int32_t *d_counts, int32_t spp, int32_t width, int32_t height,
+                              const float *d_gbuffer, const rt_camera *cam_prev, const float *d_gbuffer_prev,
+                              const float *d_history_prev, const rt_temporal_params *params, float *d_history_out, float *d_out_mean,
+                              float *d_out_variance, const float *d_motion, void *stream) {
+    rttm::Params tp;
+    if (int rc = rt_temporal_check("rt_temporal_motion_device", d_sums, d_counts, spp, width, height, d_gbuffer, cam_prev,
+                                   d_gbuffer_prev, d_history_prev, params, d_history_out, &tp))
+        return rc;
+    if (d_motion && !d_history_prev) return rt_fail(RT_ERR_ARG, "rt_temporal_motion_device: motion records need a previous history");
+    if (!quad_aligned(d_motion)) return rt_fail(RT_ERR_ARG, "rt_temporal_motion_device: device pointers must be 16-byte aligned");
+    return temporal_launch(d_sums, d_counts, spp, width, height, d_gbuffer, cam_prev, d_gbuffer_prev, d_history_prev, tp,
+                           d_history_out, d_out_mean, d_out_variance, (hipStream_t)stream, d_motion);
+}
+
 void rt_history_free(rt_history *h) {
     if (!h) return;
     DeviceGuard guard(h->device);
-    for (void *b : {(void *)h->hist[0], (void *)h->hist[1], (void *)h->gbuf[0], (void *)h->gbuf[1]})
+    for (void *b : {(void *)h->hist[0], (void *)h->hist[1], (void *)h->gbuf[0], (void *)h->gbuf[1], (void *)h->tri_prev, (void *)h->motion})
         if (b) (void)hipFree(b);
     delete h;
 }
@@ -129,9 +166,25 @@ int rt_history_push(rt_history *h, const float *d_sums, const int32_t *d_counts,
     if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
     h->stream = (hipStream_t)stream;
     if (int rc = gbuffer_launch(d, h->geom, h->gbuf[c], h->stream)) return rc;
+    // with motion records: the triangles moved since the snapshot was taken (several updates between
+    // two pushes are one motion); an unmoved scene runs exactly the launch below
+    const bool moved = h->motion_on && h->has_prev && h->has_snapshot && h->geom_seen != h->scene->geom_epoch;
+    h->motion_valid = false;
+    if (moved) {
+        if (int rc = motion_launch((const float *)h->gbuf[c], h->W, h->H, (const float *)d->ds.tri, h->tri_prev, (uint32_t)d->ds.n_tris,
+                                   h->motion, h->stream))
+            return rc;
+        h->motion_valid = true;
+    }
     if (int rc = temporal_launch(d_sums, d_counts, spp, h->W, h->H, (const float *)h->gbuf[c], &h->cam_prev, g_prev, h_prev, tp,
-                                 h->hist[c], d_out_mean, d_out_variance, h->stream))
+                                 h->hist[c], d_out_mean, d_out_variance, h->stream, moved ? h->motion : nullptr))
         return rc;
+    if (h->motion_on && (!h->has_snapshot || h->geom_seen != h->scene->geom_epoch)) {
+        if (d->ds.n_tris)
+            HIP_TRY(hipMemcpyAsync(h->tri_prev, d->ds.tri, (size_t)d->ds.n_tris * 12 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        h->geom_seen = h->scene->geom_epoch;
+        h->has_snapshot = true;
+    }
     (void)rt_scene_get_camera(h->scene, &h->cam_prev);
     h->cur = o;
     h->has_prev = true;
@@ -189,6 +242,38 @@ int rt_history_push_frame_u8(rt_history *h, const float *sums, const int32_t *co
 
 const float *rt_history_gbuffer_device(rt_history *h) { return h && h->has_prev ? (const float *)h->gbuf[h->cur ^ 1] : nullptr; }
 
+int rt_history_enable_motion(rt_history *h) {
+    if (!h) return rt_fail(RT_ERR_ARG, "rt_history_enable_motion: NULL history");
+    if (h->has_prev) return rt_fail(RT_ERR_ARG, "rt_history_enable_motion: only before the first push or directly after rt_history_reset");
+    if (h->motion_on) return RT_OK;
+    rt_device_scene *d = h->scene->dev[h->device];
+    if (!d) return rt_fail(RT_ERR_ARG, "rt_history_enable_motion: scene not uploaded to device " + std::to_string(h->device));
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    float *tri_prev = nullptr, *motion = nullptr;
+    const size_t tri_bytes = (size_t)d->ds.n_tris * 12 * sizeof(float);
+    hipError_t e = hipMalloc((void **)&tri_prev, tri_bytes ? tri_bytes : 16);
+    if (e == hipSuccess) e = hipMalloc((void **)&motion, (size_t)(h->n ? h->n : 1) * RT_MOTION_WORDS * sizeof(float));
+    if (e != hipSuccess) {   // the history stays as it was
+        if (tri_prev) (void)hipFree(tri_prev);
+        return rt_fail(RT_ERR_DEVICE, std::string("rt_history_enable_motion: ") + hipGetErrorString(e));
+    }
+    h->tri_prev = tri_prev, h->motion = motion, h->motion_on = true, h->has_snapshot = false, h->motion_valid = false;
+    return RT_OK;
+}
+
+const float *rt_history_motion_device(rt_history *h) { return h && h->has_prev && h->motion_valid ? h->motion : nullptr; }
+
+int rt_history_motion(rt_history *h, float *out) {
+    if (!h || !out) return rt_fail(RT_ERR_ARG, "rt_history_motion: NULL argument");
+    if (!rt_history_motion_device(h)) return rt_fail(RT_ERR_ARG, "rt_history_motion: the last push ran without motion records");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return rt_fail(RT_ERR_DEVICE, "hipSetDevice failed");
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->n) HIP_TRY(hipMemcpy(out, h->motion, (size_t)h->n * RT_MOTION_WORDS * sizeof(float), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 int rt_history_lengths(rt_history *h, float *out) {
     if (!h || !out) return rt_fail(RT_ERR_ARG, "rt_history_lengths: NULL argument");
     if (!h->has_prev) {
@@ -207,6 +292,7 @@ int rt_history_lengths(rt_history *h, float *out) {
 int rt_history_reset(rt_history *h) {
     if (!h) return rt_fail(RT_ERR_ARG, "rt_history_reset: NULL history");
     h->has_prev = false;   // (the slots' contents are never read before the next push has written one)
+    h->has_snapshot = false, h->motion_valid = false;   // (the next push takes a new snapshot of the triangles)
     return RT_OK;
 }
 
