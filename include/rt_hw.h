@@ -45,7 +45,8 @@ enum rt_status {
     RT_ERR_IO = -2,       /* file missing or unreadable */
     RT_ERR_FORMAT = -3,   /* glTF / image content not supported (reference throws the same) */
     RT_ERR_DEVICE = -4,   /* HIP runtime error or no device */
-    RT_ERR_LIMIT = -5     /* scene exceeds a device limit (e.g. BVH deeper than the stack) */
+    RT_ERR_LIMIT = -5,    /* scene exceeds a device limit (e.g. BVH deeper than the stack) */
+    RT_ERR_STATE = -6     /* the scene is not in the state the call needs (posable meshes: no rest data, poses not enabled) */
 };
 
 typedef struct rt_scene rt_scene; /* opaque: host arrays + lazily uploaded device copies */
@@ -323,6 +324,69 @@ int rt_relight_view(const rt_scene_view *view, const uint32_t *tri_of_light, flo
 /* Test / inspection entry: the device copy's light and light_node arrays (the host layout).  Either
  * pointer may be NULL. */
 int rt_scene_read_device_lights(rt_scene *scene, int32_t device, float *light, float *light_node);
+
+/* --- posable meshes: per-mesh node matrices, applied on the device (additive in ABI 6) ------------- */
+/* A mesh posed with matrix M holds, triangle for triangle, the records the loader makes of the same glTF
+ * whose node carries M — and the loader's are the reference's (tests/test_loader.py).  csrc/rt_pose.h is
+ * the rule's text, shared by the loader's triangle loop, the host functions, the device kernel and the
+ * CPU tests.  M is a matrix4<double> in column storage: element (row i, column j) is m[4 * j + i].
+ *   positions  v0 = M q0, U = M q1 - v0, V.x = (M q2).x - v0.x with M q the reference's multiply (float
+ *              accumulators, every add in double and rounded to float); V.y, V.z are differences of the
+ *              once-rounded dots of q2 and q0 (the shipped binary's loop)
+ *   normals    normal(NT n), x and y rounded once, z per add; NT = inverse(transpose(M)), the cofactor
+ *              inverse, computed on the host once per posed mesh
+ *   tri 9..11  normal(cross(U, V)); a light's area follows as in the movable-lights rule above
+ * tri_attr words 9..15 and tri_tan do not depend on M and are never written: tangents stay in object
+ * space and shading carries them with the mesh's mesh_normal_transform, which therefore follows the pose
+ * in the host arrays, in the cached image and on every device copy.
+ *
+ * Rest data.  rt_scene_load_gltf keeps, per triangle in post-build order, the rest record (18 floats: the
+ * object-space positions q0 q1 q2 and normals n0 n1 n2; (0,0,1) where the primitive has no NORMAL) and
+ * tri_source, the triangle's index in load order (node, primitive, triangle), and per mesh the loaded node
+ * matrix.  A scene from rt_scene_from_view holds none until rt_scene_set_rest hands the same three arrays
+ * in (tri_source must be a permutation; RT_ERR_STATE once poses are enabled).  rt_scene_get_rest copies
+ * them out (any pointer may be NULL) and rt_scene_tri_source copies tri_source alone; RT_ERR_STATE where
+ * the scene holds none.
+ *
+ * rt_scene_enable_poses: idempotent; RT_ERR_STATE without rest data, the scene untouched.  It puts the rest
+ * records (padded to five 16-byte quads each) on every device the scene is on; a device it is uploaded to
+ * later takes them then.  rt_scene_get_mesh_transform: the mesh's current matrix (the loaded one until it
+ * is posed).
+ *
+ * rt_scene_pose_meshes gives each of the n named meshes its whole node matrix (16 doubles each; not an
+ * offset from the loaded one).  The host twin restates the meshes' records, every node box (the refit
+ * rule above), and, where an emissive mesh is posed, the light records of the covering range and every
+ * light box; it patches the cached image.  On every device copy a table goes up (per posed mesh M and NT,
+ * and a slot per mesh), the posed meshes' mesh_normal_transform is rewritten, one kernel recomputes the
+ * records of the covering range's posed triangles from the copy's own rest records (one thread per
+ * triangle; tri as three 16-byte stores and words 0..8 of tri_attr), and the refit launches and, for an
+ * emissive mesh, the light launches follow; the call waits.  No record crosses the bus.
+ * Refusals, all before any launch or copy, the scene left exactly as it was: poses not enabled
+ * (RT_ERR_STATE); n == 0 or a NULL pointer, a mesh id beyond n_meshes, a mesh named twice, a matrix whose
+ * determinant (as the cofactor inverse computes it) is zero, an emissive mesh on a scene without
+ * rt_scene_enable_light_updates (RT_ERR_ARG).  A matrix with a NaN or infinite entry and a non-zero
+ * determinant is not refused: the records are whatever the rule gives and the boxes follow the refit rule
+ * (a NaN component is never taken); where a word is NaN, host and device may hold different NaN bits.
+ * Contract: as for rt_scene_update_tris — every entry then behaves as on rt_scene_from_view(the same
+ * arrays).  The call bumps the scene's epochs as an update does: accumulators go stale, and a history with
+ * motion records follows the posed triangles.
+ * Limits: topology kept (a rotation degrades the tree more than a translation does; no rebuild); one level
+ * (a pose is the mesh's world matrix, there is no node hierarchy); checkpoints hold no pose.
+ *
+ * rt_pose_view: pure host function, the twin of rt_refit_view: out_tri (n_tris x 12), out_tri_attr
+ * (n_tris x 16) and out_mesh_nt (n_meshes x 16) are the view's with the named meshes posed; rest is
+ * n_tris x 18.  The refusals that need no scene apply (RT_ERR_ARG).
+ * rt_trs_matrix: matrix4::TRS as the loader computes a node's (float arithmetic, stored to double);
+ * r is the quaternion x y z w. */
+int rt_scene_set_rest(rt_scene *scene, const float *rest, const uint32_t *tri_source, const double *mesh_matrix);
+int rt_scene_get_rest(const rt_scene *scene, float *rest, uint32_t *tri_source, double *mesh_matrix);
+int rt_scene_tri_source(const rt_scene *scene, uint32_t *out);
+int rt_scene_enable_poses(rt_scene *scene);
+int rt_scene_get_mesh_transform(const rt_scene *scene, uint32_t mesh, double m[16]);
+int rt_scene_pose_meshes(rt_scene *scene, uint32_t n, const uint32_t *mesh, const double *m);
+int rt_pose_view(const rt_scene_view *view, const float *rest, uint32_t n, const uint32_t *mesh, const double *m,
+                 float *out_tri, float *out_tri_attr, double *out_mesh_nt);
+int rt_trs_matrix(const float t[3], const float r[4], const float s[3], double out[16]);
 
 /* --- render ----------------------------------------------------------------------- */
 /* Copies the scene to `device` (once per device; later calls reuse it).  One render per

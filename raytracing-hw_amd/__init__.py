@@ -272,6 +272,16 @@ ABI = {
     "rt_scene_light_map": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
     "rt_relight_view": (ctypes.c_int, [ctypes.POINTER(RtSceneView), ctypes.POINTER(ctypes.c_uint32), _c_f, _c_f]),
     "rt_scene_read_device_lights": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_f, _c_f]),
+    # posable meshes: rest data, per-mesh node matrices, the pose on the device
+    "rt_scene_set_rest": (ctypes.c_int, [ctypes.c_void_p, _c_f, ctypes.POINTER(ctypes.c_uint32), _c_d]),
+    "rt_scene_get_rest": (ctypes.c_int, [ctypes.c_void_p, _c_f, ctypes.POINTER(ctypes.c_uint32), _c_d]),
+    "rt_scene_tri_source": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
+    "rt_scene_enable_poses": (ctypes.c_int, [ctypes.c_void_p]),
+    "rt_scene_get_mesh_transform": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, _c_d]),
+    "rt_scene_pose_meshes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), _c_d]),
+    "rt_pose_view": (ctypes.c_int, [ctypes.POINTER(RtSceneView), _c_f, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), _c_d,
+                                    _c_f, _c_f, _c_d]),
+    "rt_trs_matrix": (ctypes.c_int, [_c_f, _c_f, _c_f, _c_d]),
 }
 
 _lib_handle = None
@@ -333,9 +343,14 @@ class RtError(RuntimeError):
     pass
 
 
+ERR_ARG, ERR_STATE = -1, -6   # include/rt_hw.h rt_status: what RtError.code holds
+
+
 def _check(rc):
     if rc != 0:
-        raise RtError(lib().rt_last_error().decode())
+        e = RtError(lib().rt_last_error().decode())
+        e.code = rc
+        raise e
 
 
 def shard_rows(height, rank=0, world=1, row_block=8):
@@ -521,6 +536,64 @@ class Scene:
         _check(lib().rt_scene_read_device_lights(self._h, int(device), out["light"].ctypes.data_as(_c_f),
                                                  out["light_node"].ctypes.data_as(_c_f)))
         return out
+
+    def _counts(self):
+        v = RtSceneView()
+        _check(lib().rt_scene_get_view(self._h, ctypes.byref(v)))
+        return int(v.n_tris), int(v.n_meshes)
+
+    def rest(self):
+        """rt_scene_get_rest: {"rest": (n_tris, 18) object-space q0 q1 q2 n0 n1 n2 per triangle in post-build
+        order, "tri_source": (n_tris,) the triangle's index in load order, "mesh_matrix": (n_meshes, 16) the
+        meshes' current node matrices (column storage)}.  Raises (code ERR_STATE) on a scene without rest data."""
+        nt, nm = self._counts()
+        out = {"rest": np.zeros((nt, 18), np.float32), "tri_source": np.zeros(nt, np.uint32),
+               "mesh_matrix": np.zeros((nm, 16), np.float64)}
+        _check(lib().rt_scene_get_rest(self._h, out["rest"].ctypes.data_as(_c_f), out["tri_source"].ctypes.data_as(_c_u),
+                                       out["mesh_matrix"].ctypes.data_as(_c_d)))
+        return out
+
+    def set_rest(self, rest, tri_source=None, mesh_matrix=None):
+        """rt_scene_set_rest: hand a from_view scene the rest data of the load its arrays came from; `rest`
+        may be the dict rest() returns."""
+        if isinstance(rest, dict):
+            rest, tri_source, mesh_matrix = rest["rest"], rest["tri_source"], rest["mesh_matrix"]
+        nt, nm = self._counts()
+        rest = np.ascontiguousarray(rest, np.float32).reshape(-1)
+        src = np.ascontiguousarray(tri_source, np.uint32).reshape(-1)
+        mm = np.ascontiguousarray(mesh_matrix, np.float64).reshape(-1)
+        if len(rest) != 18 * nt or len(src) != nt or len(mm) != 16 * nm:
+            raise ValueError("set_rest: rest (n_tris, 18), tri_source (n_tris,) and mesh_matrix (n_meshes, 16) are needed")
+        _check(lib().rt_scene_set_rest(self._h, rest.ctypes.data_as(_c_f), src.ctypes.data_as(_c_u), mm.ctypes.data_as(_c_d)))
+
+    def tri_source(self):
+        """rt_scene_tri_source: for every triangle (post-build order) its index in load order."""
+        out = np.zeros(self._counts()[0], np.uint32)
+        _check(lib().rt_scene_tri_source(self._h, out.ctypes.data_as(_c_u)))
+        return out
+
+    def enable_poses(self):
+        """rt_scene_enable_poses: from now on pose() may give meshes other node matrices; the rest records
+        go to every device copy.  Idempotent; raises (code ERR_STATE), the scene untouched, without rest data."""
+        _check(lib().rt_scene_enable_poses(self._h))
+
+    def mesh_transform(self, mesh):
+        """rt_scene_get_mesh_transform: the mesh's current node matrix, 16 doubles in column storage."""
+        m = np.zeros(16, np.float64)
+        _check(lib().rt_scene_get_mesh_transform(self._h, int(mesh), m.ctypes.data_as(_c_d)))
+        return m
+
+    def pose(self, poses):
+        """rt_scene_pose_meshes: {mesh: M, ...}, M the mesh's whole node matrix (16 doubles, column
+        storage; trs() makes one).  The records, the boxes, mesh_normal_transform and, for an emissive
+        mesh on a scene with enable_light_updates(), the lights follow on the host and on every device
+        copy (csrc/rt_pose.h); the tree's topology is kept.  An accumulator of the scene needs reset()
+        before it renders on.  Not while anything reads the scene's device copy."""
+        ids = np.array([int(k) for k in poses], np.uint32)
+        if len(ids) and min(int(k) for k in poses) < 0:
+            raise ValueError("pose: negative mesh id")
+        m = np.ascontiguousarray([np.asarray(poses[k], np.float64).reshape(16) for k in poses], np.float64).reshape(-1)
+        _check(lib().rt_scene_pose_meshes(self._h, len(ids), ids.ctypes.data_as(_c_u), m.ctypes.data_as(_c_d)))
 
     def translated_records(self, mesh, offset, cover=False, lights=False):
         """The easy way to move an object: [(first, tri), ...], one entry per run of consecutive
@@ -1063,6 +1136,36 @@ def relight_view(arrays, tri_of_light):
                                  light.ctypes.data_as(_c_f), lnode.ctypes.data_as(_c_f)))
     del keep
     return light, lnode
+
+
+def pose_view(arrays, rest, poses):
+    """rt_pose_view (a pure host function): (tri, tri_attr, mesh_normal_transform) of the view with the
+    meshes of `poses` ({mesh: M}) under their matrices (csrc/rt_pose.h); rest is (n_tris, 18).  Words
+    9..15 of tri_attr and every other mesh's records are copied."""
+    v, keep = make_view(arrays)
+    nt, nm = len(arrays["tri"]), len(arrays["mesh_f"])
+    rest = np.ascontiguousarray(rest, np.float32).reshape(-1)
+    if len(rest) != 18 * nt:
+        raise ValueError("pose_view: rest must hold 18 words per triangle")
+    ids = np.array([int(k) for k in poses], np.uint32)
+    m = np.ascontiguousarray([np.asarray(poses[k], np.float64).reshape(16) for k in poses], np.float64).reshape(-1)
+    tri = np.zeros((nt, 12), np.float32)
+    attr = np.zeros((nt, 16), np.float32)
+    mnt = np.zeros((nm, 16), np.float64)
+    _check(lib().rt_pose_view(ctypes.byref(v), rest.ctypes.data_as(_c_f), len(ids), ids.ctypes.data_as(_c_u),
+                              m.ctypes.data_as(_c_d), tri.ctypes.data_as(_c_f), attr.ctypes.data_as(_c_f),
+                              mnt.ctypes.data_as(_c_d)))
+    del keep
+    return tri, attr, mnt
+
+
+def trs(t=(0, 0, 0), r=(0, 0, 0, 1), s=(1, 1, 1)):
+    """rt_trs_matrix: the node matrix the loader makes of a glTF translation, rotation (quaternion
+    x y z w) and scale (float32 arithmetic, stored to double): 16 doubles in column storage."""
+    t, r, s = (np.ascontiguousarray(x, np.float32).reshape(k) for x, k in ((t, 3), (r, 4), (s, 3)))
+    out = np.zeros(16, np.float64)
+    _check(lib().rt_trs_matrix(t.ctypes.data_as(_c_f), r.ctypes.data_as(_c_f), s.ctypes.data_as(_c_f), out.ctypes.data_as(_c_d)))
+    return out
 
 
 def parse_scene_gltf(path, width, height, samples):

@@ -74,6 +74,7 @@
 #include "rt_refit.h"
 #include "rt_refit_plan.h"
 #include "rt_relight.h"
+#include "rt_pose.h"
 
 using rtd::Counters;
 using rtd::DevScene;
@@ -136,6 +137,10 @@ struct rt_device_scene {
     void *refit_stage = nullptr;
     size_t refit_stage_bytes = 0;
     void *relight_buf = nullptr;       // movable lights: light_of_tri, then the light node ids by depth
+    // posable meshes (rt_pose_device.h): the rest records (five quads per triangle), and the last call's table
+    void *pose_rest = nullptr;
+    void *pose_table = nullptr;
+    size_t pose_table_bytes = 0;
     // rt_render_frame's, kept between frames: the device's render and copy streams, two shard
     // buffers (float sums then 8-bit rows) and the events that order their reuse; on the root
     // device also the root buffer: staging, frame and row map (sizes and offsets: rt_frame_plan.h)
@@ -611,7 +616,7 @@ void free_device_scene(rt_device_scene *d) {
         for (hipStream_t q : {d->fr.stream, d->fr.cp_stream})
             if (q) (void)hipStreamSynchronize(q);
         for (void *p : {d->buf, (void *)d->counters, (void *)d->queue, d->wf_buf, (void *)d->wf_count,
-                        (void *)d->wf_fetch, (void *)d->fast_part, d->order_buf, d->refit_stage, d->relight_buf, d->fr.buf[0], d->fr.buf[1], d->fr.root_buf})
+                        (void *)d->wf_fetch, (void *)d->fast_part, d->order_buf, d->refit_stage, d->relight_buf, d->pose_rest, d->pose_table, d->fr.buf[0], d->fr.buf[1], d->fr.root_buf})
             if (p) (void)hipFree(p);
         if (d->wf_host_count) (void)hipHostFree(d->wf_host_count);
         for (hipEvent_t e : {d->fr.copied[0], d->fr.copied[1], d->fr.finished, d->fr.last})
@@ -631,6 +636,8 @@ hipError_t ensure_frame_streams(rt_device_scene *d) {
         if (e == hipSuccess && !*ev) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
     return e;
 }
+
+int pose_rest_upload(rt_scene *s, rt_device_scene *d);   // rt_pose_device.h
 
 int ensure_device_scene(rt_scene *s, int device) {
     if (device < 0 || device >= kRtMaxDevices) return rt_fail(RT_ERR_DEVICE, "no HIP device " + std::to_string(device));
@@ -689,6 +696,11 @@ int ensure_device_scene(rt_scene *s, int device) {
     std::memcpy(ds.cam_pos, s->cam_pos, sizeof ds.cam_pos);
     std::memcpy(ds.cam_axes, s->cam_axes, sizeof ds.cam_axes);
     std::memcpy(ds.tan_fov, s->tan_half_fov, sizeof ds.tan_fov);
+    if (s->poses_on)   // a posable scene's copy holds the rest records from the start
+        if (int prc = pose_rest_upload(s, d)) {
+            free_device_scene(d);
+            return prc;
+        }
     s->dev[device] = d;
     {
         std::lock_guard<std::mutex> lk(g_live_mu);
@@ -1298,6 +1310,7 @@ int rt_render(rt_scene *s, const rt_params *p, float *out, rt_stats *st) {
 #include "rt_motion_device.h"    // rt_motion_device: the motion records' kernel
 #include "rt_temporal_device.h"  // rt_temporal_device, rt_history_*: the temporal step's kernel and the history object
 #include "rt_refit_device.h"     // rt_scene_update_tris*, rt_scene_read_device: the scatter and refit kernels and their entries
+#include "rt_pose_device.h"      // rt_scene_pose_meshes' device half: the rest records, the pose kernel
 
 // The whole frame as shards 0 .. n-1 of a (world n, row_block) split, shard r on device
 // devices[r] (include/rt_hw.h rt_render_frame).  rt_frame_plan.h defines the layout: which

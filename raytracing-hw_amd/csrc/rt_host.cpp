@@ -28,6 +28,7 @@
 #include "rt_select.h"
 #include "rt_temporal.h"
 #include "rt_motion.h"
+#include "rt_pose.h"
 #include "rt_vec.h"
 
 using rtv::V2;
@@ -159,7 +160,6 @@ V4 m4_mul_v4(const M4 &m, V4 t) {
     return {res[0], res[1], res[2], res[3]};
 }
 V3 m4_mul_point(const M4 &m, V3 p) { return rtv::reduce(m4_mul_v4(m, {p.x, p.y, p.z, 1.f})); }
-V3 m4_mul_vector(const M4 &m, V3 p) { return rtv::reduce(m4_mul_v4(m, {p.x, p.y, p.z, 0.f})); }
 
 // The same products as the shipped reference binary computes them inside parse_scene_gltf's
 // triangle loop (scene_parser.cpp:300-319).  GCC 11 at -O3 (the reference's CMake build)
@@ -171,57 +171,17 @@ V3 m4_mul_vector(const M4 &m, V3 p) { return rtv::reduce(m4_mul_v4(m, {p.x, p.y,
 //               v2 and v0 (x as the source says);
 //   normals:    multiplyVector(normal_transform, n) with x and y rounded once, z per add.
 // Meshes whose transforms make every product exact (identity, scale, axis swaps) are the
-// same either way.
-float m4_dot_once(const M4 &m, int i, V3 p, float w) {
-    return (float)(m.d[i] * (double)p.x + m.d[4 + i] * (double)p.y + m.d[8 + i] * (double)p.z + m.d[12 + i] * (double)w);
-}
-V3 m4_mul_vector_gcc(const M4 &m, V3 p) {
-    const V3 r = m4_mul_vector(m, p);
-    return {m4_dot_once(m, 0, p, 0.f), m4_dot_once(m, 1, p, 0.f), r.z};
+// same either way.  The text of that rule, of the transpose and of the cofactor inverse
+// (matrix.h:88-217) is rt_pose.h's: a posed mesh (rt_scene_pose_meshes) is the loaded one.
+M4 m4_inverse(const M4 &mat) {
+    M4 res;
+    if (!rtps::inverse(mat.d, res.d)) throw rt_error(RT_ERR_FORMAT, "Zero determinant");
+    return res;
 }
 M4 m4_transpose(const M4 &m) {
     M4 r;
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) r.d[4 * i + j] = m.d[4 * j + i];
+    rtps::transpose(m.d, r.d);
     return r;
-}
-// Cofactor inverse (matrix.h:88-217).  Each cofactor is six signed triple products summed
-// left to right; the table lists (sign, a, b, c) for inv[k] = sum sign * m[a]*m[b]*m[c].
-M4 m4_inverse(const M4 &mat) {
-    static const int8_t T[16][6][4] = {
-        {{+1, 5, 10, 15}, {-1, 5, 11, 14}, {-1, 9, 6, 15}, {+1, 9, 7, 14}, {+1, 13, 6, 11}, {-1, 13, 7, 10}},
-        {{-1, 1, 10, 15}, {+1, 1, 11, 14}, {+1, 9, 2, 15}, {-1, 9, 3, 14}, {-1, 13, 2, 11}, {+1, 13, 3, 10}},
-        {{+1, 1, 6, 15}, {-1, 1, 7, 14}, {-1, 5, 2, 15}, {+1, 5, 3, 14}, {+1, 13, 2, 7}, {-1, 13, 3, 6}},
-        {{-1, 1, 6, 11}, {+1, 1, 7, 10}, {+1, 5, 2, 11}, {-1, 5, 3, 10}, {-1, 9, 2, 7}, {+1, 9, 3, 6}},
-        {{-1, 4, 10, 15}, {+1, 4, 11, 14}, {+1, 8, 6, 15}, {-1, 8, 7, 14}, {-1, 12, 6, 11}, {+1, 12, 7, 10}},
-        {{+1, 0, 10, 15}, {-1, 0, 11, 14}, {-1, 8, 2, 15}, {+1, 8, 3, 14}, {+1, 12, 2, 11}, {-1, 12, 3, 10}},
-        {{-1, 0, 6, 15}, {+1, 0, 7, 14}, {+1, 4, 2, 15}, {-1, 4, 3, 14}, {-1, 12, 2, 7}, {+1, 12, 3, 6}},
-        {{+1, 0, 6, 11}, {-1, 0, 7, 10}, {-1, 4, 2, 11}, {+1, 4, 3, 10}, {+1, 8, 2, 7}, {-1, 8, 3, 6}},
-        {{+1, 4, 9, 15}, {-1, 4, 11, 13}, {-1, 8, 5, 15}, {+1, 8, 7, 13}, {+1, 12, 5, 11}, {-1, 12, 7, 9}},
-        {{-1, 0, 9, 15}, {+1, 0, 11, 13}, {+1, 8, 1, 15}, {-1, 8, 3, 13}, {-1, 12, 1, 11}, {+1, 12, 3, 9}},
-        {{+1, 0, 5, 15}, {-1, 0, 7, 13}, {-1, 4, 1, 15}, {+1, 4, 3, 13}, {+1, 12, 1, 7}, {-1, 12, 3, 5}},
-        {{-1, 0, 5, 11}, {+1, 0, 7, 9}, {+1, 4, 1, 11}, {-1, 4, 3, 9}, {-1, 8, 1, 7}, {+1, 8, 3, 5}},
-        {{-1, 4, 9, 14}, {+1, 4, 10, 13}, {+1, 8, 5, 14}, {-1, 8, 6, 13}, {-1, 12, 5, 10}, {+1, 12, 6, 9}},
-        {{+1, 0, 9, 14}, {-1, 0, 10, 13}, {-1, 8, 1, 14}, {+1, 8, 2, 13}, {+1, 12, 1, 10}, {-1, 12, 2, 9}},
-        {{-1, 0, 5, 14}, {+1, 0, 6, 13}, {+1, 4, 1, 14}, {-1, 4, 2, 13}, {-1, 12, 1, 6}, {+1, 12, 2, 5}},
-        {{+1, 0, 5, 10}, {-1, 0, 6, 9}, {-1, 4, 1, 10}, {+1, 4, 2, 9}, {+1, 8, 1, 6}, {-1, 8, 2, 5}},
-    };
-    const double *m = mat.d;
-    M4 res;
-    for (int k = 0; k < 16; ++k) {
-        const int8_t(*t)[4] = T[k];
-        double acc = (t[0][0] < 0 ? -m[t[0][1]] : m[t[0][1]]) * m[t[0][2]] * m[t[0][3]];
-        for (int q = 1; q < 6; ++q) {
-            double p = m[t[q][1]] * m[t[q][2]] * m[t[q][3]];
-            acc = t[q][0] < 0 ? acc - p : acc + p;
-        }
-        res.d[k] = acc;
-    }
-    double det = m[0] * res.d[0] + m[1] * res.d[4] + m[2] * res.d[8] + m[3] * res.d[12];
-    if (det == 0) throw rt_error(RT_ERR_FORMAT, "Zero determinant");
-    det = 1.0 / det;
-    for (int i = 0; i < 16; ++i) res.d[i] *= det;
-    return res;
 }
 
 // ---------------------------------------------------------------- primitives and boxes
@@ -244,6 +204,7 @@ struct Prim {  // Primitive (primitive.h:96-134)
     V4 tan[3];
     V2 tc[3];
     int mesh_id = 0;
+    float rest[rtps::kRestWords];   // the object-space positions and normals the record was made of (rt_pose.h)
     Box box;   // Primitive::aabb() (primitive.cpp:63-75)
     V3 center;
 };
@@ -254,6 +215,7 @@ struct MeshRec {
     float metallic = 1.f, roughness2 = 1.f, alpha = 1.f, ior = 1.f;
     int tex[4] = {-1, -1, -1, -1};  // base_color, normal, metallic_roughness, emission
     M4 normal_transform;
+    M4 matrix;   // the node's, which normal_transform is made of
 };
 
 // ---------------------------------------------------------------- BVH build
@@ -389,11 +351,7 @@ uint32_t flatten_nodes(const std::vector<BuildNode> &nodes, std::vector<float> &
     return maxd;
 }
 
-V3 geometric_normal(const Prim &p, float &area) {  // Primitive::get_geometric_normal (primitive.cpp:77-84)
-    V3 n = rtv::cross(p.pos[1], p.pos[2]);
-    area = 0.5f * rtv::length(n);
-    return rtv::normal(n);
-}
+V3 geometric_normal(const Prim &p, float &area) { return rtps::geometric_normal(p.pos[1], p.pos[2], area); }
 
 // ---------------------------------------------------------------- glTF ingest
 struct AccessorView {
@@ -561,6 +519,7 @@ static void load_gltf(rt_scene &S, const std::string &path, int width, int heigh
             meshes.emplace_back();
             MeshRec &mesh = meshes.back();
             M4 transform = m4_from(node_matrix[ni]);
+            mesh.matrix = transform;
             mesh.normal_transform = m4_inverse(m4_transpose(transform));
             int mat = p["material"].integer(-1);
             if (mat != -1) {
@@ -637,21 +596,19 @@ static void load_gltf(rt_scene &S, const std::string &path, int width, int heigh
                 }
                 Prim pr;
                 pr.mesh_id = mesh_id;
+                // the rest record, then the triangle under the node's matrix (rt_pose.h: the rule
+                // rt_scene_pose_meshes applies to the same rest record later)
                 V3 q[3];
                 for (int v = 0; v < 3; ++v) {
                     q[v] = V3{pos_v[index[v] * 3], pos_v[index[v] * 3 + 1], pos_v[index[v] * 3 + 2]};
-                    pr.pos[v] = m4_mul_point(transform, q[v]);
+                    const V3 n = nrm_v ? V3{nrm_v[index[v] * 3], nrm_v[index[v] * 3 + 1], nrm_v[index[v] * 3 + 2]}
+                                       : V3{0.f, 0.f, 1.f};
+                    float *r = pr.rest;
+                    r[3 * v] = q[v].x, r[3 * v + 1] = q[v].y, r[3 * v + 2] = q[v].z;
+                    r[9 + 3 * v] = n.x, r[10 + 3 * v] = n.y, r[11 + 3 * v] = n.z;
+                    pr.nrm[v] = rtps::shading_normal(mesh.normal_transform.d, n);
                 }
-                // (the reference binary's v2 - v0: see m4_mul_vector_gcc)
-                const float y0 = m4_dot_once(transform, 1, q[0], 1.f), z0 = m4_dot_once(transform, 2, q[0], 1.f);
-                const float y2 = m4_dot_once(transform, 1, q[2], 1.f), z2 = m4_dot_once(transform, 2, q[2], 1.f);
-                pr.pos[1] = rtv::sub(pr.pos[1], pr.pos[0]);
-                pr.pos[2] = V3{pr.pos[2].x - pr.pos[0].x, y2 - y0, z2 - z0};
-                for (int v = 0; v < 3; ++v) {
-                    V3 n = nrm_v ? V3{nrm_v[index[v] * 3], nrm_v[index[v] * 3 + 1], nrm_v[index[v] * 3 + 2]}
-                                 : V3{0.f, 0.f, 1.f};
-                    pr.nrm[v] = rtv::normal(m4_mul_vector_gcc(mesh.normal_transform, n));
-                }
+                rtps::positions(transform.d, q[0], q[1], q[2], pr.pos[0], pr.pos[1], pr.pos[2]);
                 for (int v = 0; v < 3; ++v) {
                     pr.tc[v] = tc_v ? V2{tc_v[index[v] * 2], tc_v[index[v] * 2 + 1]} : V2{0.f, 0.f};
                     pr.tan[v] = tan_v ? V4{tan_v[index[v] * 4], tan_v[index[v] * 4 + 1], tan_v[index[v] * 4 + 2],
@@ -677,9 +634,12 @@ static void load_gltf(rt_scene &S, const std::string &path, int width, int heigh
     S.tri.resize(nt * 12);
     S.tri_attr.resize(nt * 16);
     S.tri_tan.resize(nt * 12);
+    S.rest.resize(nt * rtps::kRestWords);
+    S.tri_source = order;   // post-build place -> load order (node, primitive, triangle)
     std::vector<Prim> lights;
     for (size_t k = 0; k < nt; ++k) {
         const Prim &p = prims[order[k]];
+        std::memcpy(&S.rest[rtps::kRestWords * k], p.rest, sizeof p.rest);
         float area = 0.f;
         V3 g = geometric_normal(p, area);
         float *o = &S.tri[12 * k];
@@ -717,6 +677,7 @@ static void load_gltf(rt_scene &S, const std::string &path, int width, int heigh
         S.mesh_f.insert(S.mesh_f.end(), f, f + 12);
         S.mesh_tex.insert(S.mesh_tex.end(), m.tex, m.tex + 4);
         S.mesh_nt.insert(S.mesh_nt.end(), m.normal_transform.d, m.normal_transform.d + 16);
+        S.mesh_matrix.insert(S.mesh_matrix.end(), m.matrix.d, m.matrix.d + 16);
         for (int t = 0; t < 4; ++t)
             if (m.tex[t] >= (int)(S.tex_info.size() / 4)) throw rt_error(RT_ERR_FORMAT, "texture index out of range");
     }
@@ -965,6 +926,176 @@ int rt_relight_view(const rt_scene_view *v, const uint32_t *tri_of_light, float 
     if (nn) std::memcpy(out_light_node, v->light_node, nn * 8 * sizeof(float));
     for (size_t k = 0; k < v->n_lights; ++k) rtrl::light_from_tri(v->tri + 12 * (size_t)tri_of_light[k], out_light + 16 * k);
     rtrl::refit_sweep(out_light, out_light_node, nn);
+    return RT_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------ posable meshes
+// (include/rt_hw.h rt_scene_pose_meshes; the rule is csrc/rt_pose.h)
+namespace {
+
+// What a pose call names, checked: slot_of_mesh[mesh] = its place in the call or -1, table = per
+// place M then NT (32 doubles).  "" or what is wrong.
+struct PoseTable {
+    std::vector<int32_t> slot_of_mesh;
+    std::vector<double> table;
+};
+std::string make_pose_table(uint32_t n_meshes, uint32_t n, const uint32_t *mesh, const double *m, PoseTable *out) {
+    if (n == 0) return "no mesh named";
+    if (!mesh || !m) return "NULL argument";
+    PoseTable t;
+    t.slot_of_mesh.assign(n_meshes, -1);
+    t.table.resize(32 * (size_t)n);
+    for (uint32_t k = 0; k < n; ++k) {
+        if (mesh[k] >= n_meshes) return "no mesh " + std::to_string(mesh[k]);
+        if (t.slot_of_mesh[mesh[k]] >= 0) return "mesh " + std::to_string(mesh[k]) + " named twice";
+        t.slot_of_mesh[mesh[k]] = (int32_t)k;
+        std::memcpy(&t.table[32 * (size_t)k], m + 16 * (size_t)k, 16 * sizeof(double));
+        if (!rtps::normal_transform(m + 16 * (size_t)k, &t.table[32 * (size_t)k + 16]))
+            return "the matrix of mesh " + std::to_string(mesh[k]) + " has a zero determinant";
+    }
+    *out = std::move(t);
+    return "";
+}
+
+// The host twin's triangle loop: the records of the table's meshes within [first, first + count).
+void pose_range(const PoseTable &t, const float *rest, uint32_t first, uint32_t count, float *tri, float *tri_attr) {
+    for (size_t k = first; k < (size_t)first + count; ++k) {
+        const uint32_t mesh = as_u32(tri_attr[16 * k + 15]);
+        const int32_t slot = mesh < t.slot_of_mesh.size() ? t.slot_of_mesh[mesh] : -1;
+        if (slot < 0) continue;
+        const double *M = &t.table[32 * (size_t)slot];
+        rtps::pose_record(M, M + 16, rest + rtps::kRestWords * k, tri + 12 * k, tri_attr + 16 * k);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_scene_set_rest(rt_scene *s, const float *rest, const uint32_t *tri_source, const double *mesh_matrix) {
+    if (!s || !rest || !tri_source || !mesh_matrix) return rt_fail(RT_ERR_ARG, "rt_scene_set_rest: NULL argument");
+    if (s->poses_on) return rt_fail(RT_ERR_STATE, "rt_scene_set_rest: poses are already enabled on this scene");
+    const size_t nt = s->tri.size() / 12, nm = s->mesh_f.size() / 12;
+    std::vector<uint8_t> seen(nt, 0);
+    for (size_t k = 0; k < nt; ++k) {   // a permutation: every triangle of the load, once
+        if (tri_source[k] >= nt || seen[tri_source[k]])
+            return rt_fail(RT_ERR_ARG, "rt_scene_set_rest: tri_source is not a permutation of the triangles (entry " + std::to_string(k) + ")");
+        seen[tri_source[k]] = 1;
+    }
+    s->rest.assign(rest, rest + nt * rtps::kRestWords);
+    s->tri_source.assign(tri_source, tri_source + nt);
+    s->mesh_matrix.assign(mesh_matrix, mesh_matrix + nm * 16);
+    return RT_OK;
+}
+
+int rt_scene_get_rest(const rt_scene *s, float *rest, uint32_t *tri_source, double *mesh_matrix) {
+    if (!s) return rt_fail(RT_ERR_ARG, "rt_scene_get_rest: NULL scene");
+    if (s->tri_source.size() != s->tri.size() / 12 || s->mesh_matrix.size() != s->mesh_nt.size())
+        return rt_fail(RT_ERR_STATE, "rt_scene_get_rest: the scene holds no rest data (rt_scene_set_rest)");
+    if (rest && !s->rest.empty()) std::memcpy(rest, s->rest.data(), s->rest.size() * sizeof(float));
+    if (tri_source && !s->tri_source.empty()) std::memcpy(tri_source, s->tri_source.data(), s->tri_source.size() * sizeof(uint32_t));
+    if (mesh_matrix && !s->mesh_matrix.empty()) std::memcpy(mesh_matrix, s->mesh_matrix.data(), s->mesh_matrix.size() * sizeof(double));
+    return RT_OK;
+}
+
+int rt_scene_tri_source(const rt_scene *s, uint32_t *out) {
+    if (!s || !out) return rt_fail(RT_ERR_ARG, "rt_scene_tri_source: NULL argument");
+    return rt_scene_get_rest(s, nullptr, out, nullptr);
+}
+
+int rt_scene_enable_poses(rt_scene *s) {
+    if (!s) return rt_fail(RT_ERR_ARG, "rt_scene_enable_poses: NULL scene");
+    if (s->poses_on) return RT_OK;
+    const size_t nt = s->tri.size() / 12, nm = s->mesh_f.size() / 12;
+    if (s->rest.size() != nt * rtps::kRestWords || s->tri_source.size() != nt || s->mesh_matrix.size() != nm * 16)
+        return rt_fail(RT_ERR_STATE, "rt_scene_enable_poses: the scene holds no rest data (rt_scene_set_rest)");
+    std::vector<uint32_t> first(nm, 1), last(nm, 0);
+    for (size_t k = 0; k < nt; ++k) {
+        const uint32_t m = as_u32(s->tri_attr[16 * k + 15]);
+        if (first[m] > last[m]) first[m] = (uint32_t)k;
+        last[m] = (uint32_t)k;
+    }
+    (void)rt_scene_refit_plan(s);
+    if (int rc = rt_device_scene_enable_poses(s)) return rc;   // (a failed upload leaves the scene not opted in)
+    s->mesh_first = std::move(first), s->mesh_last = std::move(last);
+    s->poses_on = true;
+    return RT_OK;
+}
+
+int rt_scene_get_mesh_transform(const rt_scene *s, uint32_t mesh, double m[16]) {
+    if (!s || !m) return rt_fail(RT_ERR_ARG, "rt_scene_get_mesh_transform: NULL argument");
+    if (s->mesh_matrix.size() != s->mesh_nt.size() || s->mesh_matrix.empty())
+        return rt_fail(RT_ERR_STATE, "rt_scene_get_mesh_transform: the scene holds no rest data (rt_scene_set_rest)");
+    if (mesh >= s->mesh_matrix.size() / 16) return rt_fail(RT_ERR_ARG, "rt_scene_get_mesh_transform: no mesh " + std::to_string(mesh));
+    std::memcpy(m, &s->mesh_matrix[16 * (size_t)mesh], 16 * sizeof(double));
+    return RT_OK;
+}
+
+int rt_scene_pose_meshes(rt_scene *s, uint32_t n, const uint32_t *mesh, const double *m) {
+    const std::string who = "rt_scene_pose_meshes: ";
+    if (!s) return rt_fail(RT_ERR_ARG, who + "NULL scene");
+    if (!s->poses_on) return rt_fail(RT_ERR_STATE, who + "poses are not enabled on this scene (rt_scene_enable_poses)");
+    const uint32_t nm = (uint32_t)(s->mesh_f.size() / 12);
+    PoseTable t;
+    const std::string why = make_pose_table(nm, n, mesh, m, &t);
+    if (!why.empty()) return rt_fail(RT_ERR_ARG, who + why);
+    const rtrp::Plan &plan = rt_scene_refit_plan(s);
+    bool lights = false;
+    for (uint32_t k = 0; k < n; ++k)
+        if (plan.mesh_emissive[mesh[k]]) {
+            if (!s->light_plan)
+                return rt_fail(RT_ERR_ARG, who + "mesh " + std::to_string(mesh[k]) +
+                                               " is emissive and the scene has not enabled light updates");
+            lights = true;
+        }
+    // the covering range of the posed meshes' triangles, from the plan
+    uint32_t first = 0xFFFFFFFFu, last = 0;
+    for (uint32_t k = 0; k < n; ++k)
+        if (s->mesh_first[mesh[k]] <= s->mesh_last[mesh[k]])
+            first = std::min(first, s->mesh_first[mesh[k]]), last = std::max(last, s->mesh_last[mesh[k]]);
+    const uint32_t count = first <= last ? last - first + 1 : 0;
+    // the host twin: the matrices, the records, the boxes, the lights
+    for (uint32_t k = 0; k < n; ++k) {
+        std::memcpy(&s->mesh_matrix[16 * (size_t)mesh[k]], &t.table[32 * (size_t)k], 16 * sizeof(double));
+        std::memcpy(&s->mesh_nt[16 * (size_t)mesh[k]], &t.table[32 * (size_t)k + 16], 16 * sizeof(double));
+    }
+    if (count) {
+        pose_range(t, s->rest.data(), first, count, s->tri.data(), s->tri_attr.data());
+        rtrf::refit_sweep(s->tri.data(), s->node.data(), s->node.size() / 8);
+        if (lights) {
+            for (uint32_t k = first; k <= last; ++k)
+                if (const uint32_t l = s->light_plan->light_of_tri[k]; l != rtrp::LightPlan::kNone)
+                    rtrl::light_from_tri(&s->tri[12 * (size_t)k], &s->light[16 * (size_t)l]);
+            rtrl::refit_sweep(s->light.data(), s->light_node.data(), s->light_node.size() / 8);
+        }
+    }
+    ++s->view_epoch;
+    ++s->geom_epoch;
+    return rt_device_scene_pose(s, n, mesh, t.table.data(), first <= last ? first : 0, count, lights && count);
+}
+
+int rt_pose_view(const rt_scene_view *v, const float *rest, uint32_t n, const uint32_t *mesh, const double *m, float *out_tri,
+                 float *out_tri_attr, double *out_mesh_nt) {
+    if (!v || !rest || !out_tri || !out_tri_attr || !out_mesh_nt || (v->n_tris && (!v->tri || !v->tri_attr)) ||
+        (v->n_meshes && !v->mesh_normal_transform))
+        return rt_fail(RT_ERR_ARG, "rt_pose_view: NULL argument");
+    PoseTable t;
+    const std::string why = make_pose_table(v->n_meshes, n, mesh, m, &t);
+    if (!why.empty()) return rt_fail(RT_ERR_ARG, "rt_pose_view: " + why);
+    std::memcpy(out_tri, v->tri, (size_t)v->n_tris * 12 * sizeof(float));
+    std::memcpy(out_tri_attr, v->tri_attr, (size_t)v->n_tris * 16 * sizeof(float));
+    std::memcpy(out_mesh_nt, v->mesh_normal_transform, (size_t)v->n_meshes * 16 * sizeof(double));
+    for (uint32_t k = 0; k < n; ++k) std::memcpy(out_mesh_nt + 16 * (size_t)mesh[k], &t.table[32 * (size_t)k + 16], 16 * sizeof(double));
+    pose_range(t, rest, 0, v->n_tris, out_tri, out_tri_attr);
+    return RT_OK;
+}
+
+int rt_trs_matrix(const float t[3], const float r[4], const float s[3], double out[16]) {
+    if (!t || !r || !s || !out) return rt_fail(RT_ERR_ARG, "rt_trs_matrix: NULL argument");
+    const M4 m = m4_trs({t[0], t[1], t[2]}, {r[0], r[1], r[2], r[3]}, {s[0], s[1], s[2]});
+    std::memcpy(out, m.d, sizeof m.d);
     return RT_OK;
 }
 

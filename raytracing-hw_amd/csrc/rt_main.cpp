@@ -82,6 +82,14 @@
 //   RT_MOVE_LIGHTS=1    (with RT_MOVES) the scene opts in to movable lights (rt_scene_enable_light_updates):
 //                       a line may name an emissive mesh, whose light records and light BVH boxes then
 //                       follow its triangles, and the covering ranges are not cut at emissive triangles.
+// Posed objects (rt_scene_pose_meshes; unset, every byte written is the one above):
+//   RT_POSES=file       one frame per line, groups of eleven numbers `mesh tx ty tz qx qy qz qw sx sy sz`:
+//                       the mesh's whole node matrix is matrix4::TRS of them (rt_trs_matrix), not an offset
+//                       from the loaded one, and its triangles are recomputed on the device from the
+//                       object-space vertices; a mesh a line does not name keeps its last pose.  Frames,
+//                       exclusions and errors are RT_MOVES'; RT_CAMERAS, RT_TEMPORAL, RT_MOTION,
+//                       RT_MOVE_LIGHTS and the denoisers combine with it as with RT_MOVES.  Setting both
+//                       RT_POSES and RT_MOVES is an error.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -470,6 +478,86 @@ static bool read_moves(const char *path, const rt_scene_view &view, bool move_li
     return true;
 }
 
+// RT_POSES: the file's frames (a frame: the meshes it names and their node matrices), or false and why.
+struct Pose {
+    uint32_t mesh;
+    double m[16];
+};
+static bool read_poses(const char *path, const rt_scene_view &view, bool move_lights, std::vector<std::vector<Pose>> &frames,
+                       std::string &why) {
+    std::ifstream f(path);
+    if (!f) {
+        why = std::string("RT_POSES: cannot read ") + path;
+        return false;
+    }
+    const char *shape = "expected groups of eleven numbers: mesh tx ty tz qx qy qz qw sx sy sz";
+    std::string line;
+    for (int no = 1; std::getline(f, line); ++no) {
+        const size_t first = line.find_first_not_of(" \t\r");
+        if (first == std::string::npos || line[first] == '#') continue;
+        const std::string where = std::string("RT_POSES: ") + path + " line " + std::to_string(no) + ": ";
+        std::istringstream in(line);
+        std::vector<std::string> tok;
+        for (std::string t; in >> t;) tok.push_back(t);
+        if (tok.size() % 11 != 0) {
+            why = where + shape;
+            return false;
+        }
+        std::vector<Pose> frame;
+        for (size_t k = 0; k < tok.size(); k += 11) {
+            char *end = nullptr;
+            const long long m = std::strtoll(tok[k].c_str(), &end, 10);
+            if (end == tok[k].c_str() || *end != '\0') {
+                why = where + shape;
+                return false;
+            }
+            if (m < 0 || m >= (long long)view.n_meshes) {
+                why = where + "unknown mesh " + tok[k] + " (the scene has " + std::to_string(view.n_meshes) + ")";
+                return false;
+            }
+            const float *e = view.mesh_f + 12 * (size_t)m + 3;
+            if (!move_lights && (e[0] != 0.f || e[1] != 0.f || e[2] != 0.f)) {
+                why = where + "mesh " + tok[k] + " is emissive; posing a light needs RT_MOVE_LIGHTS=1";
+                return false;
+            }
+            float w[10];
+            for (int c = 0; c < 10; ++c) {
+                const std::string &t = tok[k + 1 + (size_t)c];
+                w[c] = std::strtof(t.c_str(), &end);
+                if (end == t.c_str() || *end != '\0' || !std::isfinite(w[c])) {
+                    why = where + shape + " (finite)";
+                    return false;
+                }
+            }
+            Pose p{(uint32_t)m, {0}};
+            check(rt_trs_matrix(w, w + 3, w + 7, p.m));
+            for (const Pose &q : frame)
+                if (q.mesh == p.mesh) {
+                    why = where + "mesh " + tok[k] + " named twice";
+                    return false;
+                }
+            frame.push_back(p);
+        }
+        frames.push_back(frame);
+    }
+    if (frames.empty()) {
+        why = std::string("RT_POSES: no frame in ") + path;
+        return false;
+    }
+    return true;
+}
+
+// RT_POSES: one rt_scene_pose_meshes call per frame; a mesh the frame does not name keeps its last pose.
+static void apply_poses(rt_scene *scene, const std::vector<Pose> &now) {
+    std::vector<uint32_t> mesh;
+    std::vector<double> m;
+    for (const Pose &p : now) {
+        mesh.push_back(p.mesh);
+        m.insert(m.end(), p.m, p.m + 16);
+    }
+    check(rt_scene_pose_meshes(scene, (uint32_t)mesh.size(), mesh.data(), m.data()));
+}
+
 // RT_MOVES: the scene's triangles as frame `now` places them, given what frame `before` (NULL: none)
 // had moved.  `base`: the loaded tri array.  A triangle of a mesh `now` names gets v0 = loaded v0 +
 // offset (one f32 add per component); every other one is at its loaded position.  A mesh's triangles
@@ -514,13 +602,13 @@ static std::string indexed_name(const std::string &path, size_t k) {
     return path.substr(0, dot) + idx + path.substr(dot);
 }
 
-// RT_CAMERAS, RT_MOVES: one one-shot frame per camera (`cams` empty: the scene's camera for every frame
-// of `moves`) through the existing frame path; `moves` (empty: nothing moves) places the objects
-// before each frame; with `temporal` (RT_TEMPORAL) every frame's sums pass through a history on
+// RT_CAMERAS, RT_MOVES, RT_POSES: one one-shot frame per camera (`cams` empty: the scene's camera for
+// every frame of `moves` or `poses`) through the existing frame path; `moves` or `poses` (both empty:
+// nothing moves; never both) place the objects before each frame; with `temporal` (RT_TEMPORAL) every frame's sums pass through a history on
 // device 0 before the finish.
 static void render_cameras(rt_scene *scene, int width, int height, int samples, int n_gpus, int fast_chunk, Denoise &dn,
-                           const std::vector<rt_camera> &cams, const std::vector<std::vector<Move>> &moves, bool move_lights,
-                           const std::string &output, bool temporal, float alpha, const char *aov_out, bool motion) {
+                           const std::vector<rt_camera> &cams, const std::vector<std::vector<Move>> &moves,
+                           const std::vector<std::vector<Pose>> &poses, bool move_lights, const std::string &output, bool temporal, float alpha, const char *aov_out, bool motion) {
     struct Held {   // (freed on every way out, before the scene)
         rt_history *h = nullptr;
         ~Held() { rt_history_free(h); }
@@ -549,9 +637,10 @@ static void render_cameras(rt_scene *scene, int width, int height, int samples, 
             mesh_emissive.push_back(!move_lights && (e[0] != 0.f || e[1] != 0.f || e[2] != 0.f));
         }
     }
-    const size_t n_frames = cams.empty() ? moves.size() : cams.size();
+    const size_t n_frames = !cams.empty() ? cams.size() : !poses.empty() ? poses.size() : moves.size();
     for (size_t k = 0; k < n_frames; ++k) {
         if (!cams.empty()) check(rt_scene_set_camera(scene, &cams[k]));
+        if (!poses.empty()) apply_poses(scene, poses[k]);
         if (!moves.empty()) apply_moves(scene, base, tri_mesh, mesh_emissive, k ? &moves[k - 1] : nullptr, moves[k]);
         rt_stats st{};
         if (temporal || dn.on) {
@@ -650,13 +739,20 @@ int main(int argc, char *argv[]) {
     const char *cams_env = std::getenv("RT_CAMERAS"), *temporal_env = std::getenv("RT_TEMPORAL");
     const char *moves_env = std::getenv("RT_MOVES");
     const bool cams_on = cams_env && *cams_env, temporal_on = temporal_env && *temporal_env;
-    const bool moves_on = moves_env && *moves_env;
+    const char *poses_env = std::getenv("RT_POSES");
+    const bool poses_on = poses_env && *poses_env;
+    if (poses_on && moves_env && *moves_env) {
+        std::cerr << "rt_solution: RT_POSES and RT_MOVES are both set; choose one way to move the meshes" << std::endl;
+        rt_scene_free(scene);
+        return 1;
+    }
+    const bool moves_on = (moves_env && *moves_env) || poses_on;   // (a frame per line, either way)
     const char *move_lights_env = std::getenv("RT_MOVE_LIGHTS");
     const bool move_lights = moves_on && move_lights_env && std::atoi(move_lights_env) != 0;
     const char *motion_env = std::getenv("RT_MOTION");
     const bool motion_on = motion_env && *motion_env && std::atoi(motion_env) != 0;
     if (motion_on && (!temporal_on || !moves_on)) {
-        std::cerr << "rt_solution: RT_MOTION needs " << (!temporal_on ? "RT_TEMPORAL" : "RT_MOVES")
+        std::cerr << "rt_solution: RT_MOTION needs " << (!temporal_on ? "RT_TEMPORAL" : "RT_MOVES or RT_POSES")
                   << " (motion records carry a temporal history along moved objects)" << std::endl;
         rt_scene_free(scene);
         return 1;
@@ -672,13 +768,14 @@ int main(int argc, char *argv[]) {
         return 1;
     }
     if (moves_on && ((pass_env && *pass_env) || (ckpt && *ckpt) || adaptive)) {
-        std::cerr << "rt_solution: RT_MOVES excludes RT_PASS_SPP, RT_ADAPT and RT_CHECKPOINT (one one-shot frame per line)" << std::endl;
+        std::cerr << "rt_solution: " << (poses_on ? "RT_POSES" : "RT_MOVES") << " excludes RT_PASS_SPP, RT_ADAPT and RT_CHECKPOINT (one one-shot frame per line)" << std::endl;
         rt_scene_free(scene);
         return 1;
     }
     if (cams_on || moves_on) {
         std::vector<rt_camera> cams;
         std::vector<std::vector<Move>> moves;
+        std::vector<std::vector<Pose>> poses;
         std::string why;
         const float alpha = temporal_on ? std::strtof(temporal_env, nullptr) : 0.f;
         bool ok = !cams_on || read_cameras(cams_env, cams, why);
@@ -689,9 +786,14 @@ int main(int argc, char *argv[]) {
                 why = std::string("RT_MOVE_LIGHTS: ") + rt_last_error();
                 ok = false;
             }
-            ok = ok && read_moves(moves_env, v, move_lights, moves, why);
-            if (ok && cams_on && cams.size() != moves.size()) {
-                why = "RT_CAMERAS holds " + std::to_string(cams.size()) + " frames and RT_MOVES " + std::to_string(moves.size()) +
+            if (ok && poses_on && rt_scene_enable_poses(scene) != RT_OK) {
+                why = std::string("RT_POSES: ") + rt_last_error();
+                ok = false;
+            }
+            ok = ok && (poses_on ? read_poses(poses_env, v, move_lights, poses, why) : read_moves(moves_env, v, move_lights, moves, why));
+            const size_t n_lines = poses_on ? poses.size() : moves.size();
+            if (ok && cams_on && cams.size() != n_lines) {
+                why = "RT_CAMERAS holds " + std::to_string(cams.size()) + " frames and " + (poses_on ? "RT_POSES " : "RT_MOVES ") + std::to_string(n_lines) +
                       ": the line counts must be equal";
                 ok = false;
             }
@@ -701,9 +803,9 @@ int main(int argc, char *argv[]) {
             rt_scene_free(scene);
             return 1;
         }
-        const size_t n_frames = cams_on ? cams.size() : moves.size();
+        const size_t n_frames = cams_on ? cams.size() : poses_on ? poses.size() : moves.size();
         try {
-            render_cameras(scene, width, height, samples, n_gpus, fast_chunk, dn, cams, moves, move_lights, output, temporal_on, alpha, aov_out,
+            render_cameras(scene, width, height, samples, n_gpus, fast_chunk, dn, cams, moves, poses, move_lights, output, temporal_on, alpha, aov_out,
                            motion_on);
         } catch (const std::exception &e) {
             std::cerr << "rt_solution: " << e.what() << std::endl;

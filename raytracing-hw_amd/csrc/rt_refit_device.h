@@ -144,9 +144,10 @@ int relight_ensure(rt_scene *s, rt_device_scene *d) {
 // sources are device pointers (16-byte aligned); d_attr and d_tan may be NULL (kept).  `lights`: the
 // range holds a light's triangle; then the light scatter and one launch per level of the light tree
 // follow (a range without one launches none of them).
+int refit_levels_enqueue(rt_scene *s, rt_device_scene *d, uint32_t first, uint32_t count, bool lights, hipStream_t stream);
+
 int refit_enqueue(rt_scene *s, rt_device_scene *d, uint32_t first, uint32_t count, const float *d_tri, const float *d_attr,
                   const float *d_tan, bool lights, hipStream_t stream) {
-    const rtrp::Plan &plan = rt_scene_refit_plan(s);
     if (s->light_plan)
         if (int rc = relight_ensure(s, d)) return rc;
     const RefitArrays A = refit_arrays(s, d);
@@ -154,6 +155,15 @@ int refit_enqueue(rt_scene *s, rt_device_scene *d, uint32_t first, uint32_t coun
     hipLaunchKernelGGL(rt_tris_scatter_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream, A.tri, A.attr, A.tan,
                        (const float4 *)d_tri, (const float4 *)d_attr, (const float4 *)d_tan, (long long)first, (long long)count);
     HIP_TRY(hipGetLastError());
+    return refit_levels_enqueue(s, d, first, count, lights, stream);
+}
+
+// What follows new triangle records in a device copy's arrays, however they got there (the scatter
+// above, or the pose kernel of rt_pose_device.h): the refit's launches, and with `lights` the light
+// scatter over [first, first + count) and the light tree's launches (relight_ensure has run).
+int refit_levels_enqueue(rt_scene *s, rt_device_scene *d, uint32_t first, uint32_t count, bool lights, hipStream_t stream) {
+    const rtrp::Plan &plan = rt_scene_refit_plan(s);
+    const RefitArrays A = refit_arrays(s, d);
     for (size_t l = plan.levels(); l-- > 0;) {
         const unsigned id0 = plan.level_first[l], n = plan.level_first[l + 1] - id0;
         hipLaunchKernelGGL(rt_refit_level_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const float4 *)A.tri, A.node,
@@ -194,6 +204,14 @@ void refit_adopt_nodes(rt_scene *s, const float *bfs) {
     }
 }
 
+// The image's boxes: the host's, in the device numbering (what the device kernels give too).
+void refit_patch_image_nodes(rt_scene *s) {
+    const rtrp::Plan &plan = rt_scene_refit_plan(s);
+    float *img = (float *)(s->blob->bytes.data() + s->blob->o_node);
+    for (size_t k = 0; k < plan.build_of_bfs.size(); ++k)
+        std::memcpy(img + 8 * k, &s->node[8 * (size_t)plan.build_of_bfs[k]], 6 * sizeof(float));
+}
+
 // The host arrays' triangle range into the cached image.
 void refit_patch_image(rt_scene *s, uint32_t first, uint32_t count) {
     rt_device_blob &b = *s->blob;
@@ -210,12 +228,7 @@ int rt_device_scene_update_tris(rt_scene *s, uint32_t first, uint32_t count, boo
     if (!s->blob) return RT_OK;   // on no device yet: the image is built from the host arrays when one is needed
     refit_patch_image(s, first, count);
     if (lights) relight_patch_image(s);
-    {   // the image's boxes: the host's, in the device numbering (what the device kernels give too)
-        const rtrp::Plan &plan = rt_scene_refit_plan(s);
-        float *img = (float *)(s->blob->bytes.data() + s->blob->o_node);
-        for (size_t k = 0; k < plan.build_of_bfs.size(); ++k)
-            std::memcpy(img + 8 * k, &s->node[8 * (size_t)plan.build_of_bfs[k]], 6 * sizeof(float));
-    }
+    refit_patch_image_nodes(s);
     const size_t bt = 48 * (size_t)count, ba = attr ? 64 * (size_t)count : 0, bn = tan ? 48 * (size_t)count : 0;
     for (rt_device_scene *d : s->dev) {
         if (!d) continue;

@@ -40,6 +40,13 @@ struct rt_scene {
     rtrp::Plan *refit_plan = nullptr;           // made by the first rt_scene_update_tris* (rt_refit_plan.h)
     rtrp::LightPlan *light_plan = nullptr;      // made by rt_scene_enable_light_updates; non-NULL: lights may move
     std::vector<uint32_t> bfs_order;            // build-order ids in the device's numbering, kept by the blob's builder
+
+    // posable meshes (rt_pose.h): what the loader keeps, or rt_scene_set_rest hands in; empty: no rest data
+    std::vector<float> rest;                    // n_tris x 18: object-space q0 q1 q2, n0 n1 n2 (post-build order)
+    std::vector<uint32_t> tri_source;           // n_tris: the triangle's index in load order
+    std::vector<double> mesh_matrix;            // n_meshes x 16: the mesh's current node matrix
+    bool poses_on = false;                      // rt_scene_enable_poses succeeded
+    std::vector<uint32_t> mesh_first, mesh_last;   // [mesh]: its first and last triangle (first > last: none); with poses_on
 };
 
 // error plumbing shared by rt_host.cpp and rt_device.hip
@@ -62,6 +69,16 @@ int rt_update_tris_check(rt_scene *s, const char *who, uint32_t first, uint32_t 
 // `lights`: the range holds a light's triangle (the host light arrays are already the new ones): the
 // image's light arrays are patched and every copy restates its light records and light boxes too
 int rt_device_scene_update_tris(rt_scene *s, uint32_t first, uint32_t count, bool attr, bool tan, bool lights);
+
+// posable meshes (include/rt_hw.h rt_scene_pose_meshes), implemented in rt_device.hip (rt_pose_device.h):
+// the rest records onto every device copy that exists (later copies take them when they are made)
+int rt_device_scene_enable_poses(rt_scene *s);
+// after the host twin brought the host arrays up to date: the cached image is patched, and every device
+// copy takes the table (per posed mesh: id, M, NT; `table`: 32 doubles each), rewrites those meshes'
+// mesh_nt, recomputes the records of their triangles within [first, first + count) from its own rest
+// records and refits its boxes (and, with `lights`, its light records and light boxes); waits
+int rt_device_scene_pose(rt_scene *s, uint32_t n, const uint32_t *mesh, const double *table, uint32_t first, uint32_t count,
+                         bool lights);
 
 // argument checks of rt_denoise / rt_denoise_device (rt_host.cpp): RT_OK and the resolved
 // parameters (rt_denoise.h), or the failure as `who` reports it
